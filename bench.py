@@ -14,7 +14,16 @@ model by this package's gen_rts_from_cdf (density grid on the GPU, dt=1e-3).
 One step = one wiener_like call (wfpt.pyx:54-76 semantics) over the resident
 shard. value = trials processed by all ranks / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it builds the resident
+dataset, runs W warm-up and K timed steps, and prints the result line.
+--dump-outputs DIR then writes what the last timed step returned to its caller
+(DIR/logp.npy: the call's summed log-likelihood, float64, shape (1,)); the
+data are seeded, so two builds given the same arguments score the same trials.
+--full adds everything else to the line: the pdf_sv evaluation count, the
+dominant kernel's per-launch time and roofline, the stress-set, C2, C5-on-one-
+GPU and C4 figures and the CPU baseline (each of which --no-* can drop).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process launches
 `torch.distributed.run` with N ranks itself (it never touches the GPU) and
@@ -380,6 +389,43 @@ def pmc_summary(lib_path, name="traffic.json"):
     return t
 
 
+def roofline_line(ctx, step, steps, n):
+    """The headline's K calls again, after the timed region, with HIP events
+    recorded on the library's stream around the dominant kernel (the level-0
+    pass): its per-launch duration, and its executed-work fraction when
+    profiles/traffic.json was measured on this build."""
+    from hddm_amd import _lib
+    ctx.profile(ctx.PROF_EVENTS)
+    ctx.profile_read(reset=True)
+    for _ in range(steps):
+        step()
+    ctx.synchronize()
+    k_ms, launches, _ = ctx.profile_read(reset=True)
+    ctx.profile(0)
+    k_avg_s = (k_ms / 1e3) / max(launches, 1)
+    pmc = pmc_summary(_lib.LIB_PATH)
+    roof = {"bound": "valu-fp64", "peak": PEAK_LANE_OPS / 1e12, "unit": "T fp64-lane-ops/s",
+            "achieved": None, "frac": None, "traffic": None,
+            "kernel": "wfpt::lean_kernel<3, false, 0> (level-0 pass)",
+            "kernel_ms_avg": k_avg_s * 1e3, "kernel_launches": launches}
+    if pmc and pmc.get("matches_build"):
+        # executed fp64 VALU lane-ops per trial of this kernel (rocprofv3
+        # SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64 x 64 lanes, same build and dataset)
+        # over its live per-launch time
+        w = float(pmc["fp64_lane_ops_per_trial"])
+        achieved = n * w / k_avg_s / 1e12
+        traffic = pmc.get("hbm_bytes_per_trial")
+        roof.update(achieved=achieved, frac=achieved / (PEAK_LANE_OPS / 1e12),
+                    traffic=traffic * n if traffic is not None else None,
+                    fp64_lane_ops_per_trial=w,
+                    valu_issue_utilisation=pmc.get("valu_issue_utilisation"),
+                    algorithmic_bytes=8.0 * n, pmc_source=pmc.get("source"))
+    else:
+        roof["note"] = ("profiles/traffic.json was not measured on this library build / size; "
+                        "run tools/gpu_profile.sh + tools/summarize_profile.py")
+    return roof
+
+
 def launch_ranks(a):
     """--gpus N > 1 without a torch.distributed environment: run this script
     under torch.distributed.run with N ranks (one process per GPU)."""
@@ -401,15 +447,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--trials", type=int, default=None,
                     help="trials per GPU (default: C3 1M at N=1, C5 100M/N at N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as "
+                         "DIR/logp.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the evaluation count, the kernel / roofline figures, "
+                         "the stress, C2, C5-on-one-GPU and C4 figures and the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-stress", action="store_true",
-                    help="skip the secondary stress-set figure (N = 1 only)")
+                    help="with --full: skip the secondary stress-set figure (N = 1 only)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the C2 and C5-on-one-GPU figures (N = 1 only)")
+                    help="with --full: skip the C2 and C5-on-one-GPU figures (N = 1 only)")
     ap.add_argument("--no-c4", action="store_true",
-                    help="skip the config-4 sample(2000) figures (N = 1 only)")
+                    help="with --full: skip the config-4 sample(2000) figures (N = 1 only)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a))
@@ -447,11 +502,12 @@ def main():
     else:
         step = lambda: ds.wiener_like(*args_tuple(), *knobs_tuple())
 
-    # untimed pass: count pdf_sv evaluations on this dataset
-    ctx.profile(ctx.PROF_EVALS)
-    val = step()
-    _, _, n_evals = ctx.profile_read(reset=True)
-    ctx.profile(0)
+    if a.full:
+        # untimed pass: count pdf_sv evaluations on this dataset
+        ctx.profile(ctx.PROF_EVALS)
+        val = step()
+        _, _, n_evals = ctx.profile_read(reset=True)
+        ctx.profile(0)
     for _ in range(a.warmup):
         step()
 
@@ -469,15 +525,12 @@ def main():
     ctx.synchronize()
     el = time.perf_counter() - t0
     barrier()
-    # the same K calls again with HIP events recorded on the library's stream
-    # around the dominant kernel (the level-0 pass): its per-launch duration
-    ctx.profile(ctx.PROF_EVENTS)
-    ctx.profile_read(reset=True)
-    for _ in range(a.steps):
-        step()
-    ctx.synchronize()
-    k_ms, launches, _ = ctx.profile_read(reset=True)
-    ctx.profile(0)
+    if a.dump_outputs is not None and rank == 0:
+        # what the last timed call returned (at N > 1 every rank holds the same sum)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "logp.npy"), np.array([val], dtype=np.float64))
+    if a.full:
+        roof = roofline_line(ctx, step, a.steps, n)
     if world > 1:
         import torch
         import torch.distributed as dist
@@ -487,27 +540,6 @@ def main():
 
     glob = n * world
     value = glob * a.steps / el
-    k_avg_s = (k_ms / 1e3) / max(launches, 1)
-    pmc = pmc_summary(_lib.LIB_PATH)
-    roof = {"bound": "valu-fp64", "peak": PEAK_LANE_OPS / 1e12, "unit": "T fp64-lane-ops/s",
-            "achieved": None, "frac": None, "traffic": None,
-            "kernel": "wfpt::lean_kernel<3, false, 0> (level-0 pass)",
-            "kernel_ms_avg": k_avg_s * 1e3, "kernel_launches": launches}
-    if pmc and pmc.get("matches_build"):
-        # executed fp64 VALU lane-ops per trial of this kernel (rocprofv3
-        # SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64 x 64 lanes, same build and dataset)
-        # over its live per-launch time
-        w = float(pmc["fp64_lane_ops_per_trial"])
-        achieved = n * w / k_avg_s / 1e12
-        traffic = pmc.get("hbm_bytes_per_trial")
-        roof.update(achieved=achieved, frac=achieved / (PEAK_LANE_OPS / 1e12),
-                    traffic=traffic * n if traffic is not None else None,
-                    fp64_lane_ops_per_trial=w,
-                    valu_issue_utilisation=pmc.get("valu_issue_utilisation"),
-                    algorithmic_bytes=8.0 * n, pmc_source=pmc.get("source"))
-    else:
-        roof["note"] = ("profiles/traffic.json was not measured on this library build / size; "
-                        "run tools/gpu_profile.sh + tools/summarize_profile.py")
     out = {
         "metric": METRIC,
         "value": value,
@@ -531,21 +563,22 @@ def main():
                    "trials_per_gpu": n, "global_trials": glob,
                    "parallelism": f"trial-shard x{world}" + (" + RCCL all-reduce"
                                                               if world > 1 else ""),
-                   "pdf_sv_evals_per_trial": n_evals / n,
                    "logp": val},
-        "roofline": roof,
     }
-    if world == 1 and not a.no_stress:
+    if a.full:
+        out["config"]["pdf_sv_evals_per_trial"] = n_evals / n
+        out["roofline"] = roof
+    if a.full and world == 1 and not a.no_stress:
         out["stress"] = stress_line(ctx, a.steps, a.warmup, _lib.LIB_PATH)
-    if world == 1 and not a.no_extra:
+    if a.full and world == 1 and not a.no_extra:
         ds.close()
         out["c2"] = c2_line(ctx, a.steps, a.warmup, _lib.LIB_PATH)
         out["c5_n1"] = c5_n1_line(ctx, a.steps, a.warmup)
         out["config"]["c5_n1_speedup_basis"] = (
             "value at N > 1 / c5_n1.value = the speed-up on config 5's one 100M workload")
-    if world == 1 and not a.no_c4:
+    if a.full and world == 1 and not a.no_c4:
         out["c4"] = c4_line()
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(x, a.cpu_seconds)
     if rank == 0:
         print(json.dumps(out), flush=True)

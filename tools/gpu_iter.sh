@@ -7,7 +7,7 @@ O=gpurun_out/iter
 mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --timeout 150 --timeout-method thread > $O/pytest.log 2>&1 || { echo "TESTS_FAIL rc=$?"; grep -E "FAIL|Error|assert" $O/pytest.log | tail -30; exit 1; }
 tail -1 $O/pytest.log
-timeout -k 10 300 python bench.py --cpu-seconds 4 > $O/bench.log 2>&1 || { echo "BENCH_FAIL rc=$?"; tail -20 $O/bench.log; exit 1; }
+timeout -k 10 300 python bench.py --full --cpu-seconds 4 > $O/bench.log 2>&1 || { echo "BENCH_FAIL rc=$?"; tail -20 $O/bench.log; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$O/bench.log').read().strip().splitlines()[-1])
 print('bench', d['value'], d['ms_per_step'], d['roofline']['kernel_ms_avg'], 'stress', d['stress']['trials_per_s'], d['stress']['kernel_ms_avg'])"
@@ -23,7 +23,7 @@ for r in list(csv.DictReader(open(f)))[:14]: print('  ', r['Name'][:60], r['Call
 "
 done
 rm -rf $O/trace_bench
-timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -o t -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline > $O/trace_bench.log 2>&1 || { echo "TRACE_FAIL rc=$?"; exit 1; }
+timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -o t -- python3 bench.py --steps 20 --warmup 2 --full --no-cpu-baseline > $O/trace_bench.log 2>&1 || { echo "TRACE_FAIL rc=$?"; exit 1; }
 python3 -c "
 import csv,glob
 f=glob.glob('$O/trace_bench/**/*kernel_stats.csv',recursive=True)[0]

@@ -12,7 +12,7 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -v -p no:cacheprovider --time
 tail -1 $O/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "SMOKE_FAIL rc=$?"; tail -5 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 600 python -u bench.py > $O/bench.log 2>&1 || { echo "BENCH_FAIL rc=$?"; tail -5 $O/bench.log; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench.log 2>&1 || { echo "BENCH_FAIL rc=$?"; tail -5 $O/bench.log; exit 1; }
 tail -1 $O/bench.log | cut -c1-400
 timeout -k 10 300 python -u tools/node_call_probe.py --reps 300 > $O/node_call_probe.log 2>&1 || { echo "PROBE_FAIL"; exit 1; }
 timeout -k 10 300 python -u tools/node_multi_probe.py --reps 60 --tables 1,2,4,8,16 > $O/node_multi.log 2>&1 || { echo "MULTI_FAIL"; exit 1; }

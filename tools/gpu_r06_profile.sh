@@ -25,7 +25,7 @@ run_passes() {  # name, command
 W=${WHICH:-c3 stress c2 nodes8}
 for w in $W; do
   case $w in
-    c3) run_passes c3 python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-stress --no-extra --no-c4 || exit 1 ;;
+    c3) run_passes c3 python3 bench.py --steps 20 --warmup 2 --full --no-cpu-baseline --no-stress --no-extra --no-c4 || exit 1 ;;
     stress) run_passes stress python3 tools/stress_probe.py --reps 5 --engine-only || exit 1 ;;
     c2) run_passes c2 python3 tools/c2_probe.py --reps 20 || exit 1 ;;
     nodes8) run_passes nodes8 python3 tools/node_multi_probe.py --reps 20 --tables 8 --full-only || exit 1 ;;

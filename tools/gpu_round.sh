@@ -16,7 +16,7 @@ fi
 if [ "$STAGE" = all ] || [ "$STAGE" = bench ]; then
   timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo "SMOKE_FAIL rc=$?"; tail -5 $OUT/smoke.log; exit 1; }
   tail -1 $OUT/smoke.log
-  timeout -k 10 300 python bench.py > $OUT/bench.log 2>&1 || { echo "BENCH_FAIL rc=$?"; tail -20 $OUT/bench.log; exit 1; }
+  timeout -k 10 300 python bench.py --full > $OUT/bench.log 2>&1 || { echo "BENCH_FAIL rc=$?"; tail -20 $OUT/bench.log; exit 1; }
   tail -1 $OUT/bench.log
 fi
 echo round-done
