@@ -95,9 +95,9 @@ def build(force=False, verbose=False, defines=(), out=None):
 
 
 # Diagnostic builds that tests load in a child process (WFPT_AMD_LIB); never
-# the product. pubdiag: segment_publish_kernel's non-last blocks store their
-# sums after the completion word (tests/test_parity_trials.py:
-# test_stale_check_detects_late_publication).
+# the product. pubdiag: segment_publish_diag_kernel publishes the node sums;
+# its non-last blocks store theirs after the completion word
+# (tests/test_parity_trials.py: test_stale_check_detects_late_publication).
 VARIANTS = {"pubdiag": ["WFPT_PUB_DIAG=1"]}
 
 

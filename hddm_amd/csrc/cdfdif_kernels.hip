@@ -104,26 +104,16 @@ __device__ inline void cdf_setup(const CdfPar& P, CdfShared& S) {
 }
 
 // Lane l's value broadcast to the wave through scalar registers (a constant l:
-// two v_readlane_b32, no LDS round trip); WFPT_CDF_READLANE=0: __shfl.
-#ifndef WFPT_CDF_READLANE
-#define WFPT_CDF_READLANE 1
-#endif
+// two v_readlane_b32, no LDS round trip, unlike __shfl).
 __device__ inline double bcast_lane(double v, int l) {
-#if WFPT_CDF_READLANE
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l);
   const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-#else
-  return __shfl(v, l, 64);
-#endif
 }
 
-// Lane base + k's value within a group of G lanes. G = 4 with WFPT_CDF_DPP:
-// a quad_perm DPP move per half (no LDS round trip), else __shfl.
-#ifndef WFPT_CDF_DPP
-#define WFPT_CDF_DPP 1
-#endif
+// Lane k's value within its quad of lanes (a trial's group, kCdfGroup = 4): a
+// quad_perm DPP move per half (no LDS round trip, unlike __shfl).
 template <int K>
 __device__ inline double quad_bcast(double v) {
   constexpr int ctrl = K | (K << 2) | (K << 4) | (K << 6);  // quad_perm [K, K, K, K]
@@ -132,17 +122,13 @@ __device__ inline double quad_bcast(double v) {
   const unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(b >> 32), ctrl, 0xF, 0xF, false);
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
-template <int G>
-__device__ inline double group_bcast(double v, int base, int k) {
-  if (WFPT_CDF_DPP && G == 4) {
-    switch (k) {
-      case 0: return quad_bcast<0>(v);
-      case 1: return quad_bcast<1>(v);
-      case 2: return quad_bcast<2>(v);
-      default: return quad_bcast<3>(v);
-    }
+__device__ inline double group_bcast(double v, int k) {
+  switch (k) {
+    case 0: return quad_bcast<0>(v);
+    case 1: return quad_bcast<1>(v);
+    case 2: return quad_bcast<2>(v);
+    default: return quad_bcast<3>(v);
   }
-  return __shfl(v, base + k, 64);
 }
 
 // Series convergence test shared by the three series (cdfdif.c:144-146, 177-179, 202-204).
@@ -267,9 +253,6 @@ struct CdfWinTable {
 // series terms from one exp per drift node, the same operations as
 // beyond_term (bit-identical terms).
 constexpr int kBeyTerms = 512;
-#ifndef WFPT_CDF_BEY
-#define WFPT_CDF_BEY 1
-#endif
 struct CdfBeyTable {
   double dh[6][kBeyTerms];       // -denom(v, m) / 2
   double lx[6][kBeyTerms];       // log(1 - exp(dh * st_window))
@@ -501,7 +484,7 @@ __global__ __launch_bounds__(kCdfBlock) void dmat_cdf_kernel(const double* xs, i
                                                              double p_outlier, double w_outlier,
                                                              double* out, int* defer,
                                                              int* n_defer) {
-  static_assert(kLaneTerms % G == 0 && 64 % G == 0, "group size");
+  static_assert(G == 4 && kLaneTerms % G == 0, "group size (group_bcast: quads)");
   __shared__ CdfTable L;
   {
     const double* src = (const double*)tab;
@@ -510,7 +493,7 @@ __global__ __launch_bounds__(kCdfBlock) void dmat_cdf_kernel(const double* xs, i
       dst[k] = src[k];
   }
   __syncthreads();
-  const int lane = threadIdx.x & 63, j = lane % G, base = lane - j;
+  const int lane = threadIdx.x & 63, j = lane % G;
   const int64_t per_block = kCdfBlock / G;
   for (int64_t b = blockIdx.x; b * per_block < n; b += gridDim.x) {
     const int64_t i = b * per_block + threadIdx.x / G;
@@ -532,7 +515,7 @@ __global__ __launch_bounds__(kCdfBlock) void dmat_cdf_kernel(const double* xs, i
       }
 #pragma unroll
       for (int k = 0; k < G; ++k) {
-        const double tk = G == 1 ? term : group_bcast<G>(term, base, k);
+        const double tk = group_bcast(term, k);
         if (pend) {
           h0 = h1;
           h1 = h2;
@@ -590,11 +573,6 @@ __global__ __launch_bounds__(64) void cdf_wave_kernel(const double* xs, CdfPar P
     const double xi = xs[idx];
     const CdfTrial T = cdf_prepare(fabs(xi), xi > 0, P, S);
     double F;
-#ifdef WFPT_CDF_DEBUG
-    const long long dbg_t0 = __builtin_amdgcn_s_memrealtime();
-    long long dbg_t1 = dbg_t0;
-    int dbg_rounds = 0;
-#endif
     if (T.branch == 1) {
       // h1, h2: the last two partial sums (the reference's sequential
       // additions, cdfdif.c:128-147). Per round the 64 additions run without
@@ -616,7 +594,7 @@ __global__ __launch_bounds__(64) void cdf_wave_kernel(const double* xs, CdfPar P
       for (int v0 = 0; v0 < kVMax && !conv; v0 += 64) {
         const int v = v0 + lane;
         double term = 0.0;
-        if (WFPT_CDF_BEY && v0 < kBeyTerms) {  // wave-uniform: kBeyTerms is a multiple of 64
+        if (v0 < kBeyTerms) {  // wave-uniform: kBeyTerms is a multiple of 64
           double cf[6], cd[6], cx[6];
 #pragma unroll
           for (int mm = 0; mm < 6; ++mm) {
@@ -656,9 +634,6 @@ __global__ __launch_bounds__(64) void cdf_wave_kernel(const double* xs, CdfPar P
         h1 = __shfl(hk, last > 0 ? last - 1 : 0, 64);
         if (last == 0) h1 = h2;
         h2 = __shfl(hk, last, 64);
-#ifdef WFPT_CDF_DEBUG
-        ++dbg_rounds;
-#endif
       }
       F = beyond_F(h2, T, P);
     } else {
@@ -674,9 +649,6 @@ __global__ __launch_bounds__(64) void cdf_wave_kernel(const double* xs, CdfPar P
       } else if (lane < 42) {
         if (!(fabs(S.gk[lane - 36]) > kEps)) val = window_m0(T, P);
       }
-#ifdef WFPT_CDF_DEBUG
-      dbg_t1 = __builtin_amdgcn_s_memrealtime();
-#endif
       double sum_nu = 0;
 #pragma unroll
       for (int m = 0; m < 6; ++m) {
@@ -692,13 +664,6 @@ __global__ __launch_bounds__(64) void cdf_wave_kernel(const double* xs, CdfPar P
       F = ((T.p0 * (1 - T.x)) + (T.p1 * T.x)) - sum_nu;  // cdfdif.c:210
     }
     if (lane == 0) out[idx] = cdf_output(F, xi, p_outlier, w_outlier, S);
-#ifdef WFPT_CDF_DEBUG
-    // diagnostic builds: -(rounds 1e12 + series ticks 1e6 + elapsed ticks) in
-    // place of the value (100 MHz ticks from the trial's start)
-    if (lane == 0)
-      out[idx] = -((double)dbg_rounds * 1e12 + (double)(dbg_t1 - dbg_t0) * 1e6 +
-                   (double)(__builtin_amdgcn_s_memrealtime() - dbg_t0));
-#endif
   }
 }
 
@@ -712,9 +677,7 @@ __global__ __launch_bounds__(64) void cdf_wave_kernel(const double* xs, CdfPar P
 #ifndef WFPT_CDF_WAVES
 #define WFPT_CDF_WAVES 4096
 #endif
-#ifndef WFPT_CDF_GROUP
-#define WFPT_CDF_GROUP 4
-#endif
+constexpr int kCdfGroup = 4;  // lanes per trial of dmat_cdf_kernel
 // the buffer: CdfTable, then CdfWinTable at kCdfTableBeyond doubles
 constexpr int kCdfTableBeyond = 1344;
 static_assert(sizeof(CdfTable) <= kCdfTableBeyond * sizeof(double), "kCdfTableBeyond");
@@ -739,7 +702,7 @@ void launch_dmat_cdf(const double* x, int64_t n, const double par[7], double p_o
   CdfWinTable* W = reinterpret_cast<CdfWinTable*>(tab + kCdfTableBeyond);
   CdfBeyTable* B = reinterpret_cast<CdfBeyTable*>(tab + kCdfTableWave);
   hipLaunchKernelGGL(cdf_table_kernel, dim3(kCdfTableBlocks), dim3(64), 0, s, P, T, W, B);
-  constexpr int G = WFPT_CDF_GROUP;
+  constexpr int G = kCdfGroup;
   const int64_t per_block = kCdfBlock / G;
   int64_t nb = (n + per_block - 1) / per_block;
   if (nb > 8192) nb = 8192;

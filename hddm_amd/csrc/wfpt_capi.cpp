@@ -421,7 +421,7 @@ int run_sum(wfpt_ctx* c, const double* dx, int64_t n, const wfpt::Params& P,
   if (c->count && (part & wfpt::kPassFast))
     HIP_TRY(hipMemsetAsync(c->evals, 0, sizeof(unsigned long long), c->stream));
   // profiling: ev0..ev1 bracket the level-0 fast kernel (the dominant kernel,
-  // the one rocprofv3 reports as fast_kernel<...>)
+  // lean_kernel, engine_kernel or direct_kernel in a rocprofv3 trace)
   const bool prof = c->profile && (part & wfpt::kPassFast);
   if (prof) HIP_TRY(hipEventRecord(c->ev0, c->stream));
   // heavy-chunk splitting belongs to full engine calls (not the lean / redo

@@ -85,26 +85,17 @@ constexpr double kTieBand = 1e-11;
 // instead of being recomputed on the exact path. Without the mixture
 // (full_pdf, p_outlier = 0) such a density still takes the exact path.
 constexpr double kMixAbsorb = 1e-250;
-#ifndef WFPT_TINY_MIX
-#define WFPT_TINY_MIX 1
-#endif
 __host__ __device__ inline bool tiny_absorbed(double p, double p_outlier, double w_outlier) {
-  return WFPT_TINY_MIX && p > 0.0 && p <= kExactBelow && w_outlier * p_outlier >= kMixAbsorb;
+  return p > 0.0 && p <= kExactBelow && w_outlier * p_outlier >= kMixAbsorb;
 }
 
 // UNROLL: the t-node loop fully unrolled (node positions, q hints and
 // accumulators without per-node selects or loop-carried copies; 5x the code).
-// The lean pass unrolls its boundary-uniform call site (WFPT_LEAN_UNROLL):
-// 127 VGPRs = 4 waves/SIMD instead of 168 = 3, and C3's level 0 -13%.
-#ifndef WFPT_LEAN_UNROLL
-#define WFPT_LEAN_UNROLL 1
-#endif
-// WFPT_FAST_L0_UNROLL: the same for the per-node and per-trial-parameter
-// level-0 passes (fast_level0: no scratch, node kernel -18%); the engine's
-// level 0 keeps the loop (measured: the unrolled copy slows its stress set 4%)
-#ifndef WFPT_FAST_L0_UNROLL
-#define WFPT_FAST_L0_UNROLL 1
-#endif
+// The lean pass unrolls its boundary-uniform call site: 127 VGPRs = 4
+// waves/SIMD instead of 168 = 3, and C3's level 0 -13%. So do the per-node and
+// per-trial-parameter level-0 passes (fast_level0: no scratch, node kernel
+// -18%); the engine's level 0 keeps the loop (measured: the unrolled copy
+// slows its stress set 4%).
 enum Flag : int {
   kFlagDepth = 1,     // refinement deeper than the stack (WFPT_MAX_DEPTH)
   kFlagBudget = 2,    // more than kEvalBudget pdf_sv evaluations in one trial
@@ -140,7 +131,7 @@ constexpr double kDblMin = 2.2250738585072014e-308;
 // step there), on the host fma() (the host builds the sine tables from the same
 // correctly rounded operations, so both produce the same bits).
 __host__ __device__ inline double horner_hd(double p, double r, double c) {
-#if defined(__HIP_DEVICE_COMPILE__) && (!defined(WFPT_HORNER_ASM) || WFPT_HORNER_ASM)
+#if defined(__HIP_DEVICE_COMPILE__)
   double d;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(p), "v"(r), "s"(c));
   return d;
@@ -353,33 +344,19 @@ __device__ inline TNode tnode_setup(double xx, double v, double sv, double a, do
 // choice, K and the Simpson stop tests use the reference's operations, and a
 // stop test within kTieBand = 1e-11 of its threshold is re-decided on the exact
 // path), so one fused rounding instead of two is within the few-ulp value
-// error the recurrences already carry. WFPT_SERIES_FMA=0 restores mul + add.
-#ifndef WFPT_SERIES_FMA
-#define WFPT_SERIES_FMA 1
-#endif
+// error the recurrences already carry.
 __host__ __device__ inline double madd(double a, double b, double c) {
-#if WFPT_SERIES_FMA
   return fma(a, b, c);
-#else
-  return c + a * b;
-#endif
 }
 // a b - c (the Chebyshev step 2cos(pi w) sin(k pi w) - sin((k-1) pi w))
 __host__ __device__ inline double msub(double a, double b, double c) {
-#if WFPT_SERIES_FMA
   return fma(a, b, -c);
-#else
-  return a * b - c;
-#endif
 }
 
 // Exponentials of the single-node path (tnode_ftt / tnode_pdf_sv; defined
 // after exp_val): values only, the fitted exp with its argument clamped to
 // [-1100, 1100] (exp_val would make NaN of +-inf; the clamp keeps 0 / inf and
-// NaN). WFPT_NODE_FAST_EXP=0: OCML's exp.
-#ifndef WFPT_NODE_FAST_EXP
-#define WFPT_NODE_FAST_EXP 1
-#endif
+// NaN).
 __device__ inline double exp_node(double x);
 
 // f(t|0,1,w) from a prepared t node (pdf.pxi:49-65).
@@ -930,111 +907,26 @@ __device__ inline ZGrid zgrid_setup(double lb, double ub, double v, double sv, d
 // then ldexp, which also saturates to inf / 0 / subnormals for |x| > 709. No
 // special-case selects (OCML's exp carries them for inf / NaN arguments,
 // which the hot call sites never pass: their arguments are bounded by the
-// -600 / 600 guards around them; the rare sites use exp_sat). WFPT_FAST_EXP=0
-// restores OCML's exp.
-#ifndef WFPT_FAST_EXP
-#define WFPT_FAST_EXP 1
-#endif
+// -600 / 600 guards around them; the rare sites use exp_sat).
 // One Horner step p r + c as a single three-operand v_fma_f64. Written with
 // fma(), the compiler selects the two-address v_fmac_f64 and, because the
 // coefficient c stays live for the next call site, copies it into the
 // accumulator first (a v_mov_b64 per step: 9 extra VALU instructions per
-// exponential). WFPT_HORNER_ASM=0 restores fma().
-#ifndef WFPT_HORNER_ASM
-#define WFPT_HORNER_ASM 1
-#endif
+// exponential).
 __device__ inline double horner(double p, double r, double c) {
-#if WFPT_HORNER_ASM
   double d;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(p), "v"(r), "s"(c));
   return d;
-#else
-  return fma(p, r, c);
-#endif
 }
 
-// WFPT_EXP_ESTRIN: the degree-11 polynomial by Estrin's scheme (dependency
-// depth 4 instead of Horner's 11, three more operations): the exponentials
-// sit on the level-0 pass's longest dependency chains. Values only (the
-// rounding differs from Horner's by an ulp; decisions keep their tie band).
-#ifndef WFPT_EXP_ESTRIN
-#define WFPT_EXP_ESTRIN 0
-#endif
-// WFPT_EXP_TABLE: exp_val as 2^(k/64) from a 64-entry table times a degree-5
-// polynomial: x = (64 e + j) ln2/64 + r, |r| <= ln2/128, exp(x) = 2^e T[j]
-// (1 + r + ... + r^5/120) (truncation < 4e-17 relative, ~1.5 ulp with the
-// table's and Horner's roundings): 10 fp64 operations and a table load per
-// exponential instead of 15 (and a 7-deep chain instead of 13). Values only,
-// like exp_val.
-#ifndef WFPT_EXP_TABLE
-#define WFPT_EXP_TABLE 0
-#endif
-__device__ const double kExp2J64[64] = {
-    0x1.0000000000000p+0, 0x1.02c9a3e778061p+0, 0x1.059b0d3158574p+0, 0x1.0874518759bc8p+0,
-    0x1.0b5586cf9890fp+0, 0x1.0e3ec32d3d1a2p+0, 0x1.11301d0125b51p+0, 0x1.1429aaea92de0p+0,
-    0x1.172b83c7d517bp+0, 0x1.1a35beb6fcb75p+0, 0x1.1d4873168b9aap+0, 0x1.2063b88628cd6p+0,
-    0x1.2387a6e756238p+0, 0x1.26b4565e27cddp+0, 0x1.29e9df51fdee1p+0, 0x1.2d285a6e4030bp+0,
-    0x1.306fe0a31b715p+0, 0x1.33c08b26416ffp+0, 0x1.371a7373aa9cbp+0, 0x1.3a7db34e59ff7p+0,
-    0x1.3dea64c123422p+0, 0x1.4160a21f72e2ap+0, 0x1.44e086061892dp+0, 0x1.486a2b5c13cd0p+0,
-    0x1.4bfdad5362a27p+0, 0x1.4f9b2769d2ca7p+0, 0x1.5342b569d4f82p+0, 0x1.56f4736b527dap+0,
-    0x1.5ab07dd485429p+0, 0x1.5e76f15ad2148p+0, 0x1.6247eb03a5585p+0, 0x1.6623882552225p+0,
-    0x1.6a09e667f3bcdp+0, 0x1.6dfb23c651a2fp+0, 0x1.71f75e8ec5f74p+0, 0x1.75feb564267c9p+0,
-    0x1.7a11473eb0187p+0, 0x1.7e2f336cf4e62p+0, 0x1.82589994cce13p+0, 0x1.868d99b4492edp+0,
-    0x1.8ace5422aa0dbp+0, 0x1.8f1ae99157736p+0, 0x1.93737b0cdc5e5p+0, 0x1.97d829fde4e50p+0,
-    0x1.9c49182a3f090p+0, 0x1.a0c667b5de565p+0, 0x1.a5503b23e255dp+0, 0x1.a9e6b5579fdbfp+0,
-    0x1.ae89f995ad3adp+0, 0x1.b33a2b84f15fbp+0, 0x1.b7f76f2fb5e47p+0, 0x1.bcc1e904bc1d2p+0,
-    0x1.c199bdd85529cp+0, 0x1.c67f12e57d14bp+0, 0x1.cb720dcef9069p+0, 0x1.d072d4a07897cp+0,
-    0x1.d5818dcfba487p+0, 0x1.da9e603db3285p+0, 0x1.dfc97337b9b5fp+0, 0x1.e502ee78b3ff6p+0,
-    0x1.ea4afa2a490dap+0, 0x1.efa1bee615a27p+0, 0x1.f50765b6e4540p+0, 0x1.fa7c1819e90d8p+0};
-// WFPT_EXP_TABLE=2: the table read from LDS (each kernel copies it at entry:
-// exp_table_init), =1: from global memory
-#if WFPT_EXP_TABLE == 2
-__shared__ double sExp2J64[64];
-#define WFPT_EXP_TAB sExp2J64
-#else
-#define WFPT_EXP_TAB kExp2J64
-#endif
-__device__ inline void exp_table_init() {
-#if WFPT_EXP_TABLE == 2
-  for (int k = threadIdx.x; k < 64; k += blockDim.x) sExp2J64[k] = kExp2J64[k];
-  __syncthreads();
-#endif
-}
-__device__ inline double exp_val_tab(double x) {
-  const double kd = rint(x * 92.33248261689366);  // 64 / ln2
-  double r = fma(-kd, 0x1.62e42fefa39efp-7, x);  // ln2 / 64, two parts
-  r = fma(-kd, 0x1.abc9e3b39803fp-62, r);
-  const int k = (int)kd;
-  const double t = WFPT_EXP_TAB[k & 63];
-  double p = horner(0x1.1111111111111p-7, r, 0x1.5555555555555p-5);
-  p = horner(p, r, 0x1.5555555555555p-3);
-  p = horner(p, r, 0.5);
-  p = fma(p, r, 1.0);
-  p = fma(p, r, 1.0);
-  return ldexp(t * p, k >> 6);
-}
+// Tried and not kept, values only like this one: the degree-11 polynomial by
+// Estrin's scheme (dependency depth 4 instead of Horner's 11, three more
+// operations), and 2^(k/64) from a 64-entry table (global memory or LDS) times
+// a degree-5 polynomial (10 fp64 operations and a table load instead of 15, a
+// 7-deep chain instead of 13). Estrin was 2.6% slower on the lean pass; the
+// table was 2.6% faster there but 7.8% slower on the engine's stress set
+// (its loads), and within noise from LDS.
 __device__ inline double exp_val(double x) {
-#if WFPT_FAST_EXP && WFPT_EXP_TABLE
-  return exp_val_tab(x);
-#elif WFPT_FAST_EXP && WFPT_EXP_ESTRIN
-  const double k = rint(x * 1.4426950408889634);
-  double r = fma(-k, 6.9314718055994529e-01, x);
-  r = fma(-k, 2.3190468138462996e-17, r);
-  const double r2 = r * r;
-  const double r4 = r2 * r2;
-  const double r8 = r4 * r4;
-  const double q0 = r + 1.0;
-  const double q1 = fma(1.666666666666668e-01, r, 5.000000000000019e-01);
-  const double q2 = fma(8.333333333319601e-03, r, 4.16666666664881e-02);
-  const double q3 = fma(1.9841269890047113e-04, r, 1.3888888952314775e-03);
-  const double q4 = fma(2.755724091857897e-06, r, 2.4801485482328494e-05);
-  const double q5 = fma(2.5110037605963777e-08, r, 2.763263963904103e-07);
-  const double s0 = fma(q1, r2, q0);
-  const double s1 = fma(q3, r2, q2);
-  const double s2 = fma(q5, r2, q4);
-  const double p = fma(s2, r8, fma(s1, r4, s0));
-  return ldexp(p, (int)k);
-#elif WFPT_FAST_EXP
   const double k = rint(x * 1.4426950408889634);
   double r = fma(-k, 6.9314718055994529e-01, x);
   r = fma(-k, 2.3190468138462996e-17, r);
@@ -1051,9 +943,6 @@ __device__ inline double exp_val(double x) {
   p = fma(p, r, 1.0);
   p = fma(p, r, 1.0);
   return ldexp(p, (int)k);
-#else
-  return exp(x);
-#endif
 }
 
 // Large-time sines of a grid (pdf.pxi:61-62: sin(k pi w) at the grid's 5
@@ -1063,10 +952,6 @@ __device__ inline double exp_val(double x) {
 // the host per call (RootGrids) so the lean pass reads them instead of
 // recomputing them per lane; bit-identical to the per-lane recurrence.
 constexpr int kSinK = 8;
-// WFPT_SIN_PREFETCH=0: each row of the table is loaded where it is used
-#ifndef WFPT_SIN_PREFETCH
-#define WFPT_SIN_PREFETCH 0
-#endif
 __host__ __device__ inline void sin_rot(const ZGrid& G, double (&sj)[5], double (&cj)[5]) {
   sj[0] = G.s0;
   cj[0] = G.c0;
@@ -1125,12 +1010,8 @@ __device__ inline double exp_sat(double x) { return exp(x); }
 // R(s^2))) with fdlibm's degree-7 R, plus k ln2 in two parts. <= 0.81 ulp
 // (2e7 random arguments incl. subnormals against long double, unbiased), 38
 // VALU operations against OCML's double-double log (~98). Zero, negative,
-// infinite and NaN arguments take OCML's log. WFPT_FAST_LOG=0: OCML's log.
-#ifndef WFPT_FAST_LOG
-#define WFPT_FAST_LOG 1
-#endif
+// infinite and NaN arguments take OCML's log.
 __device__ inline double log_val(double x) {
-#if WFPT_FAST_LOG
   if (!(x > 0.0 && x < __builtin_inf())) return log(x);
   int e;
   double m = frexp(x, &e);
@@ -1156,22 +1037,15 @@ __device__ inline double log_val(double x) {
   const double k = (double)e;
   return k * 6.93147180369123816490e-01 -
          ((hfsq - fma(sq, hfsq + R, k * 1.90821492927058770002e-10)) - f);
-#else
-  return log(x);
-#endif
 }
 
 __device__ inline double exp_node(double x) {
-#if WFPT_FAST_EXP && WFPT_NODE_FAST_EXP
   x = x < -1100.0 ? -1100.0 : (x > 1100.0 ? 1100.0 : x);
   return exp_val(x);
-#else
-  return exp(x);
-#endif
 }
 
-// Small-time series and drift factor of a grid in one 2-D recurrence
-// (WFPT_SMALL_2D). Every term of pdf.pxi:55-57 times the drift factor of
+// Small-time series and drift factor of a grid in one 2-D recurrence.
+// Every term of pdf.pxi:55-57 times the drift factor of
 // pdf.pxi:95-101 is exp(phi(j, k)) with
 //   phi(j, k) = m (g_j + 2k)^2 + c_j,   j = 0..4 (z node), k = lower..upper,
 // a quadratic in (j, k) on the equally spaced grid: its second differences
@@ -1183,9 +1057,6 @@ __device__ inline double exp_node(double x) {
 // way, when a term or an intermediate ratio could leave the normal range
 // (every exponent is affine or quadratic over the table: its corners bound
 // it) or a node's series is not positive (the fix-up path's semantics).
-#ifndef WFPT_SMALL_2D
-#define WFPT_SMALL_2D 1
-#endif
 __device__ inline bool small_grid2d(const TNode& T, const ZGrid& G, double sv, double (&out)[5]) {
   const int K = T.K;
   if (K > 8) return false;
@@ -1283,60 +1154,20 @@ __device__ inline bool tnode_pdf_sv_grid5(const TNode& T, const ZGrid& G, double
     return true;
   }
   const int K = T.K;
-#if defined(WFPT_KO_SMALL) || defined(WFPT_KO_LARGE)
-  // timing experiments only (tools/ab_variants.py): wrong values
-#ifdef WFPT_KO_SMALL
-  if (T.small) {
-#else
-  if (!T.small) {
-#endif
-#pragma unroll
-    for (int i = 0; i < 5; ++i) out[i] = T.sc * 0.25;
-    return true;
-  }
-#endif
-#if WFPT_SMALL_2D
   if (T.small && small_grid2d(T, G, sv, out)) return true;
-#endif
   if (T.small) {
     const int lower = (int)(-floor((K - 1) / 2.));
     const int upper = (int)ceil((K - 1) / 2.);
-    double qq = 0.0;
-    bool have_q = false;
     for (int k = lower; k <= upper; ++k) {
       const double k2 = (double)(2 * k);
-      // ek_j = (g_j + 2k)^2 m <= 0 is convex in j: the ends are the minima.
-      // Operands are formed where they are used (the grid is wave-uniform in
-      // the lean pass), not held as arrays across the branch.
-      const double w0 = G.g[0] + k2, w4 = G.g[4] + k2;
-      const double e0 = (w0 * w0) * T.m, e4 = (w4 * w4) * T.m;
-      // with WFPT_SMALL_2D the 2-D table above takes every grid it can, so
-      // this branch only sees the rare ones: node by node below
-      if (!WFPT_SMALL_2D && e0 > -600.0 && e4 > -600.0) {
-        const double w1 = G.g[1] + k2, w2 = G.g[2] + k2;
-        const double e1 = (w1 * w1) * T.m, e2 = (w2 * w2) * T.m;
-        const double d1 = e1 - e0;
-        if (!have_q) {
-          qq = exp_val((e2 - e1) - d1);
-          have_q = true;
-        }
-        double E = exp_val(e0);
-        double R = exp_val(d1);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-          p[i] = madd(G.g[i] + k2, E, p[i]);
-          E = E * R;
-          R = R * qq;
-        }
-      } else {
-        // rare (an end exponent in subnormal territory): one node per trip,
-        // so the hot path's register allocation does not carry five
-        // interleaved exponentials
+      // the 2-D table above takes every grid it can, so this branch only sees
+      // the rare ones (an end exponent in subnormal territory): one node per
+      // trip, so the hot path's register allocation does not carry five
+      // interleaved exponentials
 #pragma unroll 1
-        for (int i = 0; i < 5; ++i) {
-          const double wi = pick5(G.g, i) + k2;
-          put5(p, i, madd(wi, exp_sat((wi * wi) * T.m), pick5(p, i)));
-        }
+      for (int i = 0; i < 5; ++i) {
+        const double wi = pick5(G.g, i) + k2;
+        put5(p, i, madd(wi, exp_sat((wi * wi) * T.m), pick5(p, i)));
       }
     }
 #pragma unroll
@@ -1346,33 +1177,6 @@ __device__ inline bool tnode_pdf_sv_grid5(const TNode& T, const ZGrid& G, double
     // values the recurrence below produces (sin_table), read with scalar
     // loads instead of carried in 15 vector registers per lane
     double e = T.m, r = T.m * T.q2;
-#if WFPT_SIN_PREFETCH
-    if (K <= kSinK) {
-      // each row's scalar loads are issued one row ahead of their use, so
-      // the wait overlaps the previous row's products
-      double row[5];
-#pragma unroll
-      for (int i = 0; i < 5; ++i) row[i] = stab[5 + i];
-      for (int k = 1; k <= K; ++k) {
-        const int kq = k + 1 <= kSinK ? k + 1 : kSinK;
-        double nxt[5];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) nxt[i] = stab[5 * kq + i];
-        if (k == 1) {
-#pragma unroll
-          for (int i = 0; i < 5; ++i) p[i] = T.m * row[i];
-        } else {
-          e = e * r;
-          r = r * T.q2;
-          const double ke = (double)k * e;
-#pragma unroll
-          for (int i = 0; i < 5; ++i) p[i] = madd(ke, row[i], p[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < 5; ++i) row[i] = nxt[i];
-      }
-    } else {
-#else
     if (K >= 1) {
 #pragma unroll
       for (int i = 0; i < 5; ++i) p[i] = T.m * stab[5 + i];
@@ -1386,7 +1190,6 @@ __device__ inline bool tnode_pdf_sv_grid5(const TNode& T, const ZGrid& G, double
         for (int i = 0; i < 5; ++i) p[i] = madd(ke, stab[5 * k + i], p[i]);
       }
     } else {
-#endif
       // beyond the table (err far below 1e-10): the recurrence one node at
       // a time (few live registers)
 #pragma unroll 1
@@ -1453,13 +1256,6 @@ __device__ inline bool tnode_pdf_sv_grid5(const TNode& T, const ZGrid& G, double
 #pragma unroll
     for (int i = 0; i < 5; ++i) p[i] = p[i] * kPi;
   }
-#ifdef WFPT_KO_LDRIFT
-  if (!T.small) {  // timing experiment only: no drift factor
-#pragma unroll
-    for (int i = 0; i < 5; ++i) out[i] = p[i] * T.sc;
-    return true;
-  }
-#endif
   // exponent of the drift factor at each node (quadratic in g), formed where
   // it is used: A_i - vvx / 2 for sv = 0, (A_i - vvx) cden otherwise, as one
   // expression (the multiplier 1 is exact: no per-node select)
@@ -1632,15 +1428,11 @@ __device__ inline void tree_root(const Trial& tr, const Params& P, double& lb, d
 //           node's z integral needs refinement (bit k of `pend`: tree point
 //           k * kTreeW / 4); f[] = the root interval's values at lb, d, c, e, ub;
 //   kExact: the value hinges on last-bit rounding (recomputed exactly).
-template <int MODE, bool UNROLL = false, bool KEEP_F = true>
+template <int MODE, bool UNROLL = false>
 __device__ inline int eng_level0(double x0, const Params& P, const Knobs& K, const ZGrid& G,
                                  double& p, double (&f)[5], long long& ne, unsigned& pend);
 
-// KEEP_F = false: f[] is not written (a caller that only needs p and the
-// outcome: the per-node level 0, whose deferred chunks redo their level 0);
-// the root Simpson sums are accumulated as the t nodes complete (the lean
-// pass's form: the same values, fewer live registers)
-template <int MODE, bool KEEP_F = true>
+template <int MODE>
 __device__ inline int fast_level0(double x0, const Params& P, const Knobs& K, double& p,
                                   double (&f)[5], long long& ne, int& flags, unsigned& pend) {
   const Trial tr = trial_setup(x0, P);
@@ -1665,7 +1457,7 @@ __device__ inline int fast_level0(double x0, const Params& P, const Knobs& K, do
     G = zgrid_setup(z - tr.sz / 2., z + tr.sz / 2., v, sv, a);
   (void)t;
   (void)x;
-  return eng_level0<MODE, WFPT_FAST_L0_UNROLL != 0, KEEP_F>(x0, P, K, G, p, f, ne, pend);
+  return eng_level0<MODE, true>(x0, P, K, G, p, f, ne, pend);
 }
 
 // The engine's level 0 (kAdaptT / kAdaptTZ): the same operations as
@@ -1734,12 +1526,6 @@ __device__ inline double l0_node(const Trial& tr, const Params& P, const Knobs& 
     flags |= kFlagExact;
     return 0.0;
   }
-#ifdef WFPT_KO_NODE
-  if (MODE == kAdaptTZ) {  // timing experiment only: no grid evaluation
-    ne += 5;
-    return T.sc * iw;
-  }
-#endif
   if (MODE == kAdaptTZ) {
     const double iZz = 1.0 / ((z + tr.sz / 2.) - (z - tr.sz / 2.));
     return inner_root(T, G, iZz, v, sv, a, K, flags, ne, pend, stab) * iw;
@@ -1857,10 +1643,10 @@ __device__ inline int eng_level0_t(const Trial& tr, const Params& P, const Knobs
   p = 0.0;
   return kFinal;
 }
-template <int MODE, bool UNROLL, bool KEEP_F>
+template <int MODE, bool UNROLL>
 __device__ inline int eng_level0(double x0, const Params& P, const Knobs& K, const ZGrid& G,
                                  double& p, double (&f)[5], long long& ne, unsigned& pend) {
-  return eng_level0_t<MODE, KEEP_F, UNROLL>(trial_setup(x0, P), P, K, G, p, f, ne, pend);
+  return eng_level0_t<MODE, true, UNROLL>(trial_setup(x0, P), P, K, G, p, f, ne, pend);
 }
 
 // z grids of the engine, relative to the dyadic points P of [lb_z, ub_z]:

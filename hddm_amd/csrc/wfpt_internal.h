@@ -44,7 +44,7 @@ constexpr int kPhaseWaves = 16384;
 #define WFPT_SPLIT 8  // units per heavy chunk (kSplitTrials trials each)
 #endif
 constexpr int kSplit = WFPT_SPLIT, kSplitTrials = 64 / kSplit;
-// Two classes (WFPT_HEAVY_TOTAL): 1 = more than kHeavyZ z walks after level
+// Two classes: 1 = more than kHeavyZ z walks after level
 // 0 (always split), 2 = more than kHeavyZ over all levels only (split while
 // the dataset has few heavy chunks: the host sets n2 = 0 otherwise). The
 // lists hold class 1 in [0, cap / 2) and class 2 in [cap / 2, cap).

@@ -11,7 +11,7 @@
 //                         recorded by the previous call run as 8 split units
 //   small_kernel<MODE>    <= 256 trials (one HDDM node): level 0 and the
 //                         finalize in one launch
-//   fast_kernel<kDirect>  the simple DDM (one pdf_sv per trial)
+//   direct_kernel         the simple DDM (one pdf_sv per trial)
 //   fold_kernel<MODE>     one wave per chunk: its deferred trials (exact path,
 //                         trees deeper than kTreeDepth) settled in lane
 //                         order and added to the chunk's partial
@@ -38,10 +38,7 @@ namespace wfpt {
 constexpr int kBlock = 256;
 // Threads per block of the level-0 fast kernel (barrier-free, one chunk of 64
 // trials per wave): the block is only the hardware's dispatch unit.
-#ifndef WFPT_FAST_BLOCK
-#define WFPT_FAST_BLOCK 256
-#endif
-constexpr int kFastBlock = WFPT_FAST_BLOCK;
+constexpr int kFastBlock = 256;
 static inline int64_t fast_blocks(int64_t n) { return (n + kFastBlock - 1) / kFastBlock; }
 
 // Minimum waves per SIMD requested for the level-0 fast kernels (0 = let the
@@ -62,9 +59,7 @@ struct FastWaves {
 #define WFPT_SLOW_WAVES 2
 #endif
 // Blocks of the deferred-trial kernel (fold).
-#ifndef WFPT_FOLD_GRID
-#define WFPT_FOLD_GRID 16384
-#endif
+constexpr int kFoldGrid = 16384;
 
 // OUT_BOTH (the per-trial check of the summing kernels, wfpt_wiener_like_trials):
 // exactly OUT_SUM's chunk partials and zero words, plus each trial's log term
@@ -159,52 +154,16 @@ __device__ inline bool defer_slots(const Work& W, int64_t c, int lane, bool defe
 }
 
 // Direct family (sz = st = 0): one pdf_sv per trial, one chunk of 64 trials
-// per wave.
-template <int MODE, bool COUNT, int OUT>
-__global__ __launch_bounds__(kFastBlock, FastWaves<MODE>::value > 0 ? FastWaves<MODE>::value : 1)
-void fast_kernel(TrialArgs A, Work W) {
-  exp_table_init();
-  const int64_t i = (int64_t)blockIdx.x * kFastBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  const int64_t c = i >> 6;
-  double p = 0.0, f[5];
-  long long ne = 0;
-  int flags = 0, oc = kFinal;
-  unsigned pend = 0u;
-  if (i < A.n) oc = fast_level0<MODE>(A.x[i], A.P, A.K, p, f, ne, flags, pend);
-  double lp = 0.0;
-  int zero = 0;
-  if (i < A.n && oc == kFinal) emit<OUT>(A, i, p, lp, zero);
-  if (c * 64 >= A.n) return;  // a wave past the last chunk (wave-uniform)
-  const bool anyd = defer_slots(W, c, lane, oc != kFinal, kFlagExact);
-  if (sum_out(OUT)) {
-    lp = wave_sum(lp);
-    const int zs = __popcll(__ballot(zero != 0));
-    if (lane == 0) {
-      A.out[c] = lp;
-      A.zeros[c] = zs | (anyd ? kZeroDefer : 0);
-    }
-  }
-  if (COUNT) {
-    const long long nf = wave_sum_ll(oc == kFinal ? ne : 0);
-    if (lane == 0) atomicAdd(A.evals, (unsigned long long)nf);
-  }
-}
-
-// The direct family's level-0 pass with the call's per-boundary constants
+// per wave. The level-0 pass takes the call's per-boundary constants
 // (DirectArgs: v, w, sin / 2cos(pi w), (-v) a w, 1 / a^2 computed once on the
 // host) instead of per-lane flips, sincospi and a division: the same outputs
-// as fast_kernel<kDirect> bit for bit (direct_level0). As in the lean pass, a
+// as fast_level0<kDirect> bit for bit (direct_level0). As in the lean pass, a
 // wave's trials are taken by boundary (datasets are ordered by boundary, then
 // |rt|), so the constants are wave-uniform; only the wave at the boundary
 // switch takes the second call site.
-#ifndef WFPT_DIRECT_ARGS
-#define WFPT_DIRECT_ARGS 1
-#endif
 template <bool COUNT, int OUT>
 __global__ __launch_bounds__(kFastBlock, FastWaves<kDirect>::value > 0 ? FastWaves<kDirect>::value : 1)
 void direct_kernel(TrialArgs A, Work W, DirectArgs D) {
-  exp_table_init();
   const int64_t i = (int64_t)blockIdx.x * kFastBlock + threadIdx.x;
   const int lane = threadIdx.x & 63;
   const int64_t c = i >> 6;
@@ -271,44 +230,28 @@ void direct_kernel(TrialArgs A, Work W, DirectArgs D) {
 // it was split (likelihoods stay bitwise reproducible across call histories).
 // Trials whose value hinges on last-bit rounding (kFlagExact) or whose tree is
 // deeper (kFlagFallback) become deferred slots for fold_kernel.
-#ifndef WFPT_ENG_BLOCK
-#define WFPT_ENG_BLOCK 256
-#endif
 // waves per SIMD the engine kernel is built for (its LDS, 4 x 13.4 KB per
 // block, allows 3; its registers fit 2 without spilling)
 #ifndef WFPT_ENG_WAVES
 #define WFPT_ENG_WAVES 2
 #endif
-#ifndef WFPT_HEAVY_Z
-#define WFPT_HEAVY_Z 96
-#endif
-// WFPT_HEAVY_TOTAL=1: a chunk with more than kHeavyZ z walks over all its
-// levels (not after level 0 alone) is heavy too: class 2, split while the
-// dataset has few heavy chunks (Split::n2)
-#ifndef WFPT_HEAVY_TOTAL
-#define WFPT_HEAVY_TOTAL 1
-#endif
-constexpr int kEngBlock = WFPT_ENG_BLOCK;
+// A chunk with more than kHeavyZ z walks over all its levels (not after level
+// 0 alone) is heavy too: class 2, split while the dataset has few heavy
+// chunks (Split::n2)
+constexpr int kEngBlock = 256;
 constexpr int kEngWaves = kEngBlock / 64;
-constexpr int kHeavyZ = WFPT_HEAVY_Z;
+constexpr int kHeavyZ = 96;
 constexpr int kQCap = 2 * (1 << kTreeDepth) * 64;  // tasks (or z walks) of one level
 constexpr int kFlagIdle = 16;                       // lane without a trial to integrate
 constexpr int kFlagStop = kFlagExact | kFlagFallback | kFlagIdle;
 
-// WFPT_ZWALK_LDS=1: a z walk's 17 values are staged in LDS (ZV) for the lane
-// that runs its tree17; 0 (default): gathered by wave shuffles (no LDS, no
-// barrier; 3-4% faster on the stress sets in the r04 interleaved A/B despite
-// 28 B of engine scratch)
-#ifndef WFPT_ZWALK_LDS
-#define WFPT_ZWALK_LDS 0
-#endif
-// LDS of one chunk under refinement by a team of TW waves.
+// LDS of one chunk under refinement by a team of TW waves. A z walk's 17
+// values are not staged here: the lane that runs its tree17 gathers them by
+// wave shuffles (no LDS, no barrier; 3-4% faster on the stress sets in the r04
+// interleaved A/B than staging them, despite 28 B of engine scratch).
 template <int TW>
 struct ChunkLds {
   double F[kTreePoints * 64];              // tree values: point * 64 + owner lane
-#if WFPT_ZWALK_LDS
-  double ZV[16 * TW * kTreePoints];        // the current round's z walks
-#endif
   double X[64];                            // the owners' x
   EngTables tab;                           // the call's tables
   int fl[64];                              // the owners' flags
@@ -318,17 +261,10 @@ struct ChunkLds {
   uint16_t ZQ[kQCap];                      // z walks of the level: owner | point << 6
 };
 
-// WFPT_SYNC_FENCE: wave_sync is also a scheduling barrier (experiment)
-#ifndef WFPT_SYNC_FENCE
-#define WFPT_SYNC_FENCE 0
-#endif
 __device__ inline void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#if WFPT_SYNC_FENCE
-  __builtin_amdgcn_sched_barrier(0);
-#endif
 }
 template <int TW>
 __device__ inline void team_sync() {
@@ -377,10 +313,7 @@ __device__ inline void load_tree(const ChunkLds<TW>& cl, int o, double (&f)[kTre
 // chunk, else 64 trials per wave through their chunks (node_chunk_kernel),
 // which re-runs every trial of a chunk. Both produce each trial's term with
 // the same operations; the choice depends only on the call's inputs.
-#ifndef WFPT_NODE_REC_PER_CHUNK
-#define WFPT_NODE_REC_PER_CHUNK 8
-#endif
-constexpr int kNodeRecPerChunk = WFPT_NODE_REC_PER_CHUNK;
+constexpr int kNodeRecPerChunk = 8;
 __device__ inline bool node_records_sparse(int n_records, int n_chunks) {
   return (long long)n_records <= (long long)kNodeRecPerChunk * n_chunks;
 }
@@ -577,20 +510,6 @@ __device__ inline void refine_rounds(const TrialArgs& A, ChunkLds<TW>& cl, int t
       ++pc.nt;
     } else if (MODE == kAdaptTZ) {
       double zv[kTreePoints];
-#if WFPT_ZWALK_LDS
-      if (on) {
-        const double izf = cl.tab.iz[flip];
-        double* zw = cl.ZV + zslot * kTreePoints;
-#pragma unroll
-        for (int j = 0; j < 5; ++j)
-          if (grid_owns(gs, j)) zw[grid_point(gs, j)] = y[j] * izf;
-      }
-      team_sync<TW>();
-      if (tid < 16 * TW) {
-#pragma unroll
-        for (int k = 0; k < kTreePoints; ++k) zv[k] = cl.ZV[tid * kTreePoints + k];
-      }
-#else
       static_assert(TW == 1, "z walks gather their values by wave shuffles");
       // lane t < 16 runs walk t: its 17 values come from lanes 4t .. 4t + 3
       // (grid gs = source lane & 3; grid_point / grid_owns), by shuffles
@@ -607,7 +526,6 @@ __device__ inline void refine_rounds(const TrialArgs& A, ChunkLds<TW>& cl, int t
         zv[1 + 2 * j] = __shfl(yz[j], b4 + kGridL2L, 64);
         zv[9 + 2 * j] = __shfl(yz[j + 1], b4 + kGridL2R, 64);
       }
-#endif
       const int e = r * 16 * TW + tid;
       if (tid < 16 * TW && e < nz) {
         const int code = cl.ZQ[e];
@@ -708,9 +626,9 @@ __device__ inline void record_heavy(const Split& S, int64_t c, int cls) {
   S.next_pred[c] = flag;
 }
 // Heavy class of a chunk from its z walks after level 0 (z0) and over all
-// levels (zt): 1, 2 (WFPT_HEAVY_TOTAL) or 0.
+// levels (zt): 1, 2 or 0.
 __device__ inline int heavy_class(int z0, int zt) {
-  return z0 > kHeavyZ ? 1 : ((WFPT_HEAVY_TOTAL && zt > kHeavyZ) ? 2 : 0);
+  return z0 > kHeavyZ ? 1 : (zt > kHeavyZ ? 2 : 0);
 }
 
 // Chunk outputs of a split unit's trials: per-trial outputs now, the chunk
@@ -771,7 +689,6 @@ __device__ inline void split_out(const TrialArgs& A, const Work& W, const Split&
 template <int MODE, bool COUNT, int OUT>
 __global__ __launch_bounds__(kEngBlock, WFPT_ENG_WAVES) void engine_kernel(TrialArgs A, Work W, EngTables tab,
                                                               Split S) {
-  exp_table_init();
   __shared__ ChunkLds<1> lds[kEngWaves];
   const int lane = threadIdx.x & 63;
   ChunkLds<1>& cl = lds[threadIdx.x >> 6];
@@ -908,44 +825,12 @@ __global__ __launch_bounds__(kEngBlock, WFPT_ENG_WAVES) void engine_kernel(Trial
 // engine would (chunk_out). A chunk with a refining trial writes nothing but
 // its redo flag and a nonzero deferred count; the engine's redo pass
 // (kPassRedo) then processes it from scratch, as a full engine call would.
-// Root z grid of boundary b (0: lower, 1: upper) with b wave-uniform: every
-// field is a select between two kernel arguments on a uniform condition, so
-// the grid stays in scalar registers.
-// WFPT_ZGRID_REF: the grid is read through a reference into the kernel
-// argument block (scalar loads at a uniform offset, on demand) instead of
-// select-copied into registers.
-#ifndef WFPT_ZGRID_REF
-#define WFPT_ZGRID_REF 1
-#endif
-#if WFPT_ZGRID_REF
+// Root z grid of boundary b (0: lower, 1: upper) with b wave-uniform: the
+// grid is read through a reference into the kernel argument block (scalar
+// loads at a uniform offset, on demand) instead of select-copied into
+// registers, so it stays in scalar registers. The large-time sines come from
+// the call's table (R.S) instead of the per-lane recurrence (same values).
 __device__ inline const ZGrid& zgrid_uniform(const RootGrids& R, int b) { return R.G[b]; }
-#else
-__device__ inline ZGrid zgrid_uniform(const RootGrids& R, int b) {
-  const ZGrid& g0 = R.G[0];
-  const ZGrid& g1 = R.G[1];
-  ZGrid G;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    G.g[k] = b ? g1.g[k] : g0.g[k];
-    G.A[k] = b ? g1.A[k] : g0.A[k];
-  }
-  G.h6 = b ? g1.h6 : g0.h6;
-  G.h12 = b ? g1.h12 : g0.h12;
-  G.s0 = b ? g1.s0 : g0.s0;
-  G.c0 = b ? g1.c0 : g0.c0;
-  G.s4 = b ? g1.s4 : g0.s4;
-  G.c4 = b ? g1.c4 : g0.c4;
-  G.sd = b ? g1.sd : g0.sd;
-  G.cd = b ? g1.cd : g0.cd;
-  return G;
-}
-#endif
-
-// WFPT_SIN_TABLE=0: the lean pass evaluates the large-time sines per lane
-// (the recurrence) instead of reading the call's table (same values).
-#ifndef WFPT_SIN_TABLE
-#define WFPT_SIN_TABLE 1
-#endif
 
 // Block size of the lean pass (WFPT_LEAN_BLOCK; its waves are independent:
 // one chunk each, no block-level exchange). The launch bound's second
@@ -959,16 +844,10 @@ static_assert(kLeanBlock % 64 == 0 && kLeanBlock <= kFastBlock, "kLeanBlock");
 template <int MODE, bool COUNT, int OUT>
 __global__ __launch_bounds__(kLeanBlock, FastWaves<MODE>::value > 0 ? FastWaves<MODE>::value : 1)
 void lean_kernel(TrialArgs A, Work W, RootGrids R) {
-  exp_table_init();
 #ifdef WFPT_PHASE_TIMING
   const long long rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-#if WFPT_LEAN_REVERSE
-  // blocks dispatched last take the first chunks (timing experiment)
-  const int64_t i = (int64_t)(gridDim.x - 1 - blockIdx.x) * kLeanBlock + threadIdx.x;
-#else
   const int64_t i = (int64_t)blockIdx.x * kLeanBlock + threadIdx.x;
-#endif
   const int lane = threadIdx.x & 63;
   const int64_t c = i >> 6;
   if (c * 64 >= A.n) return;  // a wave past the last chunk (wave-uniform)
@@ -988,13 +867,12 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R) {
   const unsigned long long bo = __ballot(own), bp = __ballot(own && pos);
   const int b = (bp == bo) ? 1 : 0;  // every trial upper: 1; otherwise lower first
   if (own && pos == (b != 0))
-    oc = eng_level0_t<MODE, false, WFPT_LEAN_UNROLL != 0>(trial_setup_b(x0, A.P, b != 0), A.P, A.K,
-                                   zgrid_uniform(R, b), p, f0, ne0, pend0,
-                                   WFPT_SIN_TABLE ? &R.S[b][0][0] : nullptr);
+    oc = eng_level0_t<MODE, false, true>(trial_setup_b(x0, A.P, b != 0), A.P, A.K,
+                                         zgrid_uniform(R, b), p, f0, ne0, pend0, &R.S[b][0][0]);
   if (bp != 0ull && bp != bo) {  // mixed wave: its upper-boundary lanes
     if (own && pos)
-      oc = eng_level0_t<MODE, false, WFPT_LEAN_UNROLL != 0>(trial_setup_b(x0, A.P, true), A.P, A.K, R.G[1], p, f0,
-                                     ne0, pend0, WFPT_SIN_TABLE ? &R.S[1][0][0] : nullptr);
+      oc = eng_level0_t<MODE, false, true>(trial_setup_b(x0, A.P, true), A.P, A.K, R.G[1], p, f0,
+                                           ne0, pend0, &R.S[1][0][0]);
   }
   if (__ballot(oc == kTree) != 0ull) {
     if (lane == 0) {
@@ -1158,7 +1036,6 @@ template <int MODE, bool COUNT, bool MULTI>
 __global__ __launch_bounds__(kEngBlock, 2) void node_engine_kernel(
     const double* x, Knobs K, double* lp, const int64_t* d_idx, const Params* d_par,
     const int* n_defer, unsigned long long* evals, int* status) {
-  exp_table_init();
   __shared__ ChunkLds<1> lds[kEngWaves];
   const int lane = threadIdx.x & 63;
   node_records<MODE, COUNT, MULTI>(
@@ -1174,7 +1051,6 @@ __global__ __launch_bounds__(kEngBlock, 2) void node_engine_kernel(
 // wave sum added to the chunk's partial (a fixed order).
 template <int MODE, bool COUNT, int OUT>
 __global__ __launch_bounds__(256, WFPT_SLOW_WAVES) void fold_kernel(TrialArgs A, Work W, int64_t nw) {
-  exp_table_init();
   const int lane = threadIdx.x & 63;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
   long long ne = 0;
@@ -1216,7 +1092,6 @@ __global__ __launch_bounds__(256, WFPT_SLOW_WAVES) void fold_kernel(TrialArgs A,
 // settle, per-block {sum, zeros} (OUT_SUM) or per-trial outputs.
 template <int MODE, bool COUNT, int OUT>
 __global__ __launch_bounds__(kBlock, WFPT_SLOW_WAVES) void trial_kernel(TrialArgs A) {
-  exp_table_init();
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   long long ne = 0;
   double lp = 0.0;
@@ -1305,10 +1180,7 @@ __device__ inline void fin_write(double t, long long zz, int dd, int* status, do
 // order for a given (nb, G); G = 1 is the single-block order.
 constexpr int kFinLoads = 16;
 constexpr int kFinMaxBlocks = 64;
-#ifndef WFPT_FIN_PER_BLOCK
-#define WFPT_FIN_PER_BLOCK 8192
-#endif
-constexpr int64_t kFinPerBlock = WFPT_FIN_PER_BLOCK;  // partials per block when split
+constexpr int64_t kFinPerBlock = 8192;  // partials per block when split
 __global__ __launch_bounds__(1024) void finalize_kernel(const double* part, const int* zeros,
                                                         int64_t nb, int defer_bits,
                                                         int* status, double* out,
@@ -1397,7 +1269,7 @@ __global__ __launch_bounds__(1024) void finalize_kernel(const double* part, cons
 }
 
 // One-block calls (n <= kFastBlock trials: an HDDM node's 250, the drop-in's
-// per-node call): the level-0 pass of the direct family (fast_kernel's
+// per-node call): the level-0 pass of the direct family (fast_level0's
 // operations) or of the adaptive families (lean_kernel's), then the finalize
 // of the block's <= 4 chunk partials in the same launch, with finalize_kernel's
 // exact operations on them (thread k holds partial k, one wave sum, then the
@@ -1416,7 +1288,6 @@ struct FinArgs {
 template <int MODE, int OUT>
 __global__ __launch_bounds__(kFastBlock) void small_kernel(TrialArgs A, Work W, RootGrids R,
                                                            FinArgs F) {
-  exp_table_init();
   __shared__ double fp[kFastBlock / 64];
   __shared__ int fz[kFastBlock / 64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1446,14 +1317,14 @@ __global__ __launch_bounds__(kFastBlock) void small_kernel(TrialArgs A, Work W, 
       const unsigned long long bo = __ballot(own), bp = __ballot(own && pos);
       const int b = (bp == bo) ? 1 : 0;
       if (own && pos == (b != 0))
-        oc = eng_level0_t<MODE, false, WFPT_LEAN_UNROLL != 0>(
+        oc = eng_level0_t<MODE, false, true>(
             trial_setup_b(x0, A.P, b != 0), A.P, A.K, zgrid_uniform(R, b), p, f0, ne0, pend0,
-            WFPT_SIN_TABLE ? &R.S[b][0][0] : nullptr);
+            &R.S[b][0][0]);
       if (bp != 0ull && bp != bo) {
         if (own && pos)
-          oc = eng_level0_t<MODE, false, WFPT_LEAN_UNROLL != 0>(
+          oc = eng_level0_t<MODE, false, true>(
               trial_setup_b(x0, A.P, true), A.P, A.K, R.G[1], p, f0, ne0, pend0,
-              WFPT_SIN_TABLE ? &R.S[1][0][0] : nullptr);
+              &R.S[1][0][0]);
       }
       if (__ballot(oc == kTree) != 0ull) {
         if (lane == 0) W.redo[c] = 1;  // the host runs the redo pass (lean_kernel)
@@ -1517,14 +1388,7 @@ __global__ __launch_bounds__(kFastBlock) void small_kernel(TrialArgs A, Work W, 
 // test and the value from the five values as eng_level0_t does, and continue
 // exactly as small_kernel (chunk partials, zero words, deferred slots, the
 // finalize), so every output is small_kernel's, bit for bit.
-// WFPT_SMALL_SPLIT=0: small_kernel.
-#ifndef WFPT_SMALL_SPLIT
-#define WFPT_SMALL_SPLIT 1
-#endif
-#ifndef WFPT_SPLIT_LANES
-#define WFPT_SPLIT_LANES 3
-#endif
-constexpr int kSplitLanes = WFPT_SPLIT_LANES;
+constexpr int kSplitLanes = 3;
 constexpr int kSplitBlock = kSplitLanes * kFastBlock;
 
 // eng_level0_t's tail (KEEP_F) for one trial, from its five t-node values.
@@ -1553,7 +1417,6 @@ __device__ inline int l0_finish(const Trial& tr, const Params& P, const Knobs& K
 template <int MODE, int OUT>
 __global__ __launch_bounds__(kSplitBlock) void small_split_kernel(TrialArgs A, Work W,
                                                                  RootGrids R, FinArgs F) {
-  exp_table_init();
   static_assert(MODE == kAdaptTZ, "t-node split of the full DDM");
   __shared__ double sf[5][kFastBlock];  // t-node values, node-major
   __shared__ int sfl[kSplitLanes][kFastBlock];
@@ -1586,7 +1449,7 @@ __global__ __launch_bounds__(kSplitBlock) void small_split_kernel(TrialArgs A, W
     for (int j = sub; j < 5; j += kSplitLanes) {
       bool pj = false;
       sf[j][k] = l0_node<MODE>(tr, A.P, A.K, lb, ub, H, j, zgrid_uniform(R, bb), flags, pj, ne,
-                               WFPT_SIN_TABLE ? &R.S[bb][0][0] : nullptr);
+                               &R.S[bb][0][0]);
       if (pj) pend |= 1u << (j * (kTreeW / 4));
     }
   }
@@ -1846,21 +1709,11 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const double* lp, cons
 // r05 let each wave store its sum straight into the mapped slot, ordered
 // before the completion word by nothing: one GPU-suite run read a node sum
 // of the previous call (profiles/r06/stale_diag/ shows the test catching that
-// order deterministically in the WFPT_PUB_DIAG build). The last block also
-// resets the call's counters (the node path's n_defer words and the ticket:
-// 0 at rest, stream order).
-//
-// WFPT_PUB_DIAG=1 (diagnostic builds only, never the shipped library): every
-// block but the last takes its ticket *first* and writes its nodes' sums into
-// the mapped slot ~70 us later, i.e. the completion word deterministically
-// overtakes the sums -- the failure the regression test must be able to see.
-#ifndef WFPT_PUB_DIAG
-#define WFPT_PUB_DIAG 0
-#endif
-#ifndef WFPT_PUB_BLOCKS
-#define WFPT_PUB_BLOCKS 128
-#endif
-constexpr int32_t kPubBlocks = WFPT_PUB_BLOCKS;
+// order deterministically in the WFPT_PUB_DIAG build,
+// segment_publish_diag_kernel below). The last block also resets the call's
+// counters (the node path's n_defer words and the ticket: 0 at rest, stream
+// order).
+constexpr int32_t kPubBlocks = 128;
 // nodes a publishing wave sums at once (node_sums; 1: one node at a time)
 #ifndef WFPT_PUB_NODES
 #define WFPT_PUB_NODES 4
@@ -1885,11 +1738,6 @@ __global__ __launch_bounds__(256) void segment_publish_kernel(const double* lp, 
   const int j0 = blockIdx.x * 4 + (threadIdx.x >> 6);
   // (written by the call's earlier kernels: stream order)
   const bool pending = check_rare && counters[1] > 0;
-  double sum = 0.0;  // (the diagnostic build's: one node per wave)
-#if WFPT_PUB_DIAG
-  for (int j = pending ? n_nodes : j0; j < n_nodes; j += nwv)
-    sum = node_sum(lp, off, j, m_tab, n_tab, lane);
-#else
   // wave w sums nodes w, w + nwv, ..., kPubNodes of them at a time
   for (int j = pending ? n_nodes : j0; j < n_nodes; j += kPubNodes * nwv) {
     int32_t vj[kPubNodes];
@@ -1907,12 +1755,11 @@ __global__ __launch_bounds__(256) void segment_publish_kernel(const double* lp, 
         if (on[b]) __hip_atomic_store(&res[vj[b]], sums[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-#endif
   // the storing wave waits for its agent-scope stores (and status atomics) to
   // be performed: LLVM's workgroup barrier does not wait for other waves'
   // vector memory operations (non-tgsplit gfx950 emits only lgkmcnt(0) before
   // s_barrier), and thread 0's release below waits only for its own wave's
-  if (!WFPT_PUB_DIAG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();  // (2)
   if (threadIdx.x == 0)  // (3)
     last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
@@ -1929,14 +1776,6 @@ __global__ __launch_bounds__(256) void segment_publish_kernel(const double* lp, 
       publish_word(reinterpret_cast<unsigned long long*>(out + n_nodes + 1), seq);
     return;
   }
-#if WFPT_PUB_DIAG
-  if (!last) {
-    for (int r = 0; r < 20; ++r) __builtin_amdgcn_s_sleep(127);
-    if (j0 < n_nodes && lane == 0) out[j0] = sum;  // after the word: stale reads follow
-    return;
-  }
-  if (j0 < n_nodes && lane == 0) out[j0] = sum;
-#else
   if (!last) return;
   // plain loads: every block's stores happen-before them (the acquire above
   // invalidates this XCD's caches at agent scope); sixteen in flight per
@@ -1950,7 +1789,6 @@ __global__ __launch_bounds__(256) void segment_publish_kernel(const double* lp, 
     for (int u = 0; u < 16; ++u)
       if (k0 + 256 * u < n_nodes) out[k0 + 256 * u] = v[u];
   }
-#endif
   if (threadIdx.x == 0) {
     *ticket = 0;
     counters[0] = 0;
@@ -1963,6 +1801,64 @@ __global__ __launch_bounds__(256) void segment_publish_kernel(const double* lp, 
   if (threadIdx.x == 0)
     publish_word(reinterpret_cast<unsigned long long*>(out + n_nodes + 1), seq);
 }
+
+// Diagnostic builds only (WFPT_PUB_DIAG=1, never the shipped library):
+// segment_publish_kernel with the publication order broken on purpose. One
+// node per wave; every block takes its ticket *first*, and every block but the
+// last writes its nodes' sums into the mapped slot ~70 us later, i.e. the
+// completion word deterministically overtakes the sums -- the failure the
+// regression test must be able to see.
+#ifndef WFPT_PUB_DIAG
+#define WFPT_PUB_DIAG 0
+#endif
+#if WFPT_PUB_DIAG
+__global__ __launch_bounds__(256) void segment_publish_diag_kernel(
+    const double* lp, const int64_t* off, int32_t n_nodes, int* status, double* res, double* out,
+    unsigned long long seq, int* ticket, int* counters, int32_t m_tab, int64_t n_tab,
+    int check_rare) {
+  __shared__ int last;
+  const int lane = threadIdx.x & 63;
+  const int nwv = (int)gridDim.x * 4;
+  const int j0 = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const bool pending = check_rare && counters[1] > 0;
+  double sum = 0.0;
+  for (int j = pending ? n_nodes : j0; j < n_nodes; j += nwv)
+    sum = node_sum(lp, off, j, m_tab, n_tab, lane);
+  __syncthreads();
+  if (threadIdx.x == 0)
+    last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
+           (int)gridDim.x - 1;
+  __syncthreads();
+  if (pending) {  // as segment_publish_kernel
+    if (!last) return;
+    if (threadIdx.x == 0) {
+      *ticket = 0;
+      out[n_nodes] = kRarePending;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+      publish_word(reinterpret_cast<unsigned long long*>(out + n_nodes + 1), seq);
+    return;
+  }
+  if (!last) {
+    for (int r = 0; r < 20; ++r) __builtin_amdgcn_s_sleep(127);
+    if (j0 < n_nodes && lane == 0) out[j0] = sum;  // after the word: stale reads follow
+    return;
+  }
+  if (j0 < n_nodes && lane == 0) out[j0] = sum;
+  if (threadIdx.x == 0) {
+    *ticket = 0;
+    counters[0] = 0;
+    counters[1] = 0;
+    counters[2] = 0;
+    const int st = atomicExch(status, 0);
+    out[n_nodes] = (double)(st & kFlagDepth) + ((st & kFlagBudget) ? kBudgetUnit : 0.0);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    publish_word(reinterpret_cast<unsigned long long*>(out + n_nodes + 1), seq);
+}
+#endif
 
 // Node all-reduce (wfpt_wiener_like_nodes_allreduce): the encoded error
 // count of this rank's node pass appended to its per-node sums (res[n]),
@@ -1998,12 +1894,6 @@ __global__ __launch_bounds__(256) void publish_vec_kernel(const double* res, int
 // reads its row there. Blocks spanning more than kStageRows ids (empty nodes
 // between) read the table directly.
 constexpr int kStageRows = 256;
-// node_fast_kernel: root grids staged per block for up to this many nodes
-// (WFPT_NODE_L0T; a block of 256 stored trials spans 2 HDDM nodes of 250)
-#ifndef WFPT_NODE_L0T
-#define WFPT_NODE_L0T 0
-#endif
-constexpr int kNodeGridRows = 4;
 
 template <int STK>
 struct StackOf {
@@ -2017,7 +1907,6 @@ template <int STK, bool COUNT>
 __global__ __launch_bounds__(kBlock, WFPT_SLOW_WAVES) void node_kernel(
     const double* x, const int32_t* node, int64_t n, const Params* P, Knobs K, double* lp,
     unsigned long long* evals, int* status) {
-  exp_table_init();
   using Stack = typename StackOf<STK>::type;
   __shared__ Params rows[kStageRows];
   const int64_t i0 = (int64_t)blockIdx.x * kBlock;
@@ -2058,21 +1947,12 @@ __global__ __launch_bounds__(kBlock, WFPT_SLOW_WAVES) void node_kernel(
 // wave), which node_chunk_kernel completes 64 trials per wave. Direct family:
 // the rare exact-path trials are appended as (index, parameter row) records
 // for node_slow_kernel.
-// node_fast_kernel's level 0 without f[] (WFPT_NODE_KEEP_F=0; the deferred
-// chunks' level 0 is redone by node_chunk_kernel)
-#ifndef WFPT_NODE_KEEP_F
-#define WFPT_NODE_KEEP_F 1
-#endif
 template <int MODE, bool COUNT>
 __global__ __launch_bounds__(kBlock, FastWaves<MODE>::value > 0 ? FastWaves<MODE>::value : 1)
 void node_fast_kernel(const double* x, const int32_t* node, int64_t n, const Params* P, Knobs K,
                       double* lp, int64_t* d_idx, Params* d_par, int* n_defer, int* clist,
                       int* n_chunks, unsigned long long* evals, int* status, int* prof,
                       int32_t n_nodes, int64_t nw_tab, NodeRare R) {
-#ifdef WFPT_NODE_DEBUG_FAST
-  const long long dbg_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  exp_table_init();
   // parameter table blockIdx.y (multi-table calls: T tables x the same
   // trials): its rows, its terms lp[t n + i], its records' virtual indices
   // t n + i and its chunks' ids t nw_tab + c
@@ -2082,7 +1962,6 @@ void node_fast_kernel(const double* x, const int32_t* node, int64_t n, const Par
   lp += tab * n;
   const int64_t vbase = tab * n, cbase = tab * nw_tab;
   __shared__ Params rows[kStageRows];
-  __shared__ RootGrids grids[kNodeGridRows];
   const int64_t i0 = (int64_t)blockIdx.x * kBlock;
   const int64_t i = i0 + threadIdx.x;
   const int lane = threadIdx.x & 63;
@@ -2096,15 +1975,6 @@ void node_fast_kernel(const double* x, const int32_t* node, int64_t n, const Par
     for (int k = threadIdx.x; k < span * 8; k += kBlock) dst[k] = src[k];
   }
   __syncthreads();
-  // the full DDM with few nodes per block: each staged node's root z grids and
-  // sine tables once per block (root_grids: the engine's zgrid_of operations),
-  // and the lean pass's level 0 over them (eng_level0_t, the same bits as the
-  // engine's level 0) instead of a grid set up per lane
-  const bool gridded = WFPT_NODE_L0T && MODE == kAdaptTZ && staged && span <= kNodeGridRows;
-  if (gridded) {
-    if ((int)threadIdx.x < span) root_grids(rows[threadIdx.x], grids[threadIdx.x]);
-    __syncthreads();
-  }
   long long ne = 0;
   bool defer = false;
   Params Q;
@@ -2115,16 +1985,7 @@ void node_fast_kernel(const double* x, const int32_t* node, int64_t n, const Par
     double p, f[5];
     int flags = 0;
     unsigned pend;
-    int oc;
-    if (gridded) {
-      const double xi = x[i];
-      const bool flip = xi > 0;
-      const RootGrids& R = grids[nj - first];
-      oc = eng_level0_t<MODE, false, true>(trial_setup_b(xi, Q, flip), Q, K, R.G[flip], p, f, ne,
-                                           pend, WFPT_SIN_TABLE ? &R.S[flip][0][0] : nullptr);
-    } else {
-      oc = fast_level0<MODE, WFPT_NODE_KEEP_F != 0>(x[i], Q, K, p, f, ne, flags, pend);
-    }
+    const int oc = fast_level0<MODE>(x[i], Q, K, p, f, ne, flags, pend);
     if (oc == kFinal) lp[i] = node_logp(p, Q, K);
     else defer = true;
   }
@@ -2154,12 +2015,6 @@ void node_fast_kernel(const double* x, const int32_t* node, int64_t n, const Par
       }
     }
   }
-#ifdef WFPT_NODE_DEBUG_FAST
-  // diagnostic builds: lane 0's term of every wave is replaced by
-  // -(1e6 + the wave's elapsed 100 MHz ticks) (tools/node_fast_debug.py)
-  if (lane == 0 && i < n)
-    lp[i] = -(1e6 + (double)(__builtin_amdgcn_s_memrealtime() - dbg_t0));
-#endif
   if (COUNT) {
     ne = wave_sum_ll((defer && MODE != kDirect) ? 0 : ne);
     if (lane == 0) {
@@ -2187,7 +2042,6 @@ template <int MODE>
 __global__ __launch_bounds__(kNodeSplit * 64) void node_split_kernel(
     const double* x, const int32_t* node, int64_t n, const Params* P, Knobs K, double* lp,
     int64_t* d_idx, Params* d_par, int* clist, int* n_chunks) {
-  exp_table_init();
   static_assert(MODE == kAdaptT || MODE == kAdaptTZ, "t-node split");
   __shared__ double sf[kNodeSplit][64];
   __shared__ int sfl[kNodeSplit][64];
@@ -2302,14 +2156,7 @@ __device__ inline void eng_tables_team(const Params& P, EngTables& T, int wave, 
 // them the compiler's schedule over the record's divergent phases makes the
 // call's records 1.5x slower (node_chunk_kernel 24.0 -> 15.6 us at config 4's
 // generating parameters, same code otherwise).
-#ifndef WFPT_REC_FENCES
-#define WFPT_REC_FENCES 1
-#endif
-#if WFPT_REC_FENCES
 #define WFPT_REC_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define WFPT_REC_FENCE() ((void)0)
-#endif
 template <int NW>
 __device__ inline void record_sync() {
   if (NW == 1) wave_sync();
@@ -2325,8 +2172,7 @@ template <int MODE, int NW>
 __device__ inline void node_record_spec(double* buf, double* tv, int* pf, EngTables& T, int wave,
                                         int lane, const double* x, const Knobs& K, double* lp,
                                         int64_t i, const Params& Q, const NodeRare& R,
-                                        double* lp_base, int64_t v, int32_t vj,
-                                        long long dbg_entry = 0) {
+                                        double* lp_base, int64_t v, int32_t vj) {
   constexpr int NP = kTreePoints;
   constexpr int NG = MODE == kAdaptTZ ? 4 : 1;  // grids per t point
   constexpr int NE = NP * NG + (MODE == kAdaptTZ ? 5 : 0);
@@ -2343,15 +2189,9 @@ __device__ inline void node_record_spec(double* buf, double* tv, int* pf, EngTab
     if (wave == 0 && lane == 0) lp[i] = node_logp(0.0, Q, K);
     return;
   }
-#ifdef WFPT_NODE_DEBUG
-  const long long dbg0 = __builtin_amdgcn_s_memrealtime();
-#endif
   WFPT_REC_FENCE();
   eng_tables_team<NW>(Q, T, wave, lane);  // the record's tables in LDS
   record_sync<NW>();
-#ifdef WFPT_NODE_DEBUG
-  const long long dbg1 = __builtin_amdgcn_s_memrealtime();
-#endif
   WFPT_REC_FENCE();
   const int flip = x0 > 0 ? 1 : 0;
   const double a = Q.a, sv = Q.sv;
@@ -2403,9 +2243,6 @@ __device__ inline void node_record_spec(double* buf, double* tv, int* pf, EngTab
     }
   }
   record_sync<NW>();
-#ifdef WFPT_NODE_DEBUG
-  const long long dbg2 = __builtin_amdgcn_s_memrealtime();
-#endif
   WFPT_REC_FENCE();
   if (MODE == kAdaptTZ && wave == 0 && lane < NP) {
     // t point k's task completion (refine_rounds stage 0): the root test on
@@ -2443,9 +2280,6 @@ __device__ inline void node_record_spec(double* buf, double* tv, int* pf, EngTab
     fp[k] = flags;
   }
   if (wave == 0) wave_sync();
-#ifdef WFPT_NODE_DEBUG
-  const long long dbg3 = __builtin_amdgcn_s_memrealtime();
-#endif
   WFPT_REC_FENCE();
   if (wave == 0 && lane == 0) {
     const double(&tk)[kTreePoints] = *reinterpret_cast<const double(*)[kTreePoints]>(tv);
@@ -2470,17 +2304,6 @@ __device__ inline void node_record_spec(double* buf, double* tv, int* pf, EngTab
       rare_push(R, v, vj, (fl & kFlagExact) || fl == 0 ? kRareExact : kRareWalk, lp_base);
     else
       lp[i] = node_logp(p, Q, K);
-#if defined(WFPT_NODE_DEBUG) && !defined(WFPT_NODE_DEBUG_NOOUT)
-    // diagnostic builds: the record's phase times (100 MHz ticks: tables,
-    // evaluations, z settlement, t tree + settlement) in place of its term
-    const long long dbg4 = __builtin_amdgcn_s_memrealtime();
-    lp[i] = -((double)(dbg1 - dbg0) * 1e12 + (double)(dbg2 - dbg1) * 1e8 +
-              (double)(dbg3 - dbg2) * 1e4 + (double)(dbg4 - dbg3));
-#ifdef WFPT_NODE_DEBUG_ENTRY
-    // the kernel's entry -> record start and the record's total instead
-    lp[i] = -((double)(dbg0 - dbg_entry) * 1e8 + (double)(dbg4 - dbg0));
-#endif
-#endif
   }
   record_sync<NW>();  // the next record reuses the LDS
 }
@@ -2502,18 +2325,12 @@ __device__ inline void node_record_spec(double* buf, double* tv, int* pf, EngTab
 // fast pass's records one wave each instead (node_records), which skips the
 // level 0 of the chunks' settled trials. Trials the rounds hand on (the exact
 // path, trees deeper than kTreeDepth) are settled on their own lane (rare).
-// WFPT_NODE_REC_TEAM: a speculative record is one block's work (its waves
-// evaluate side by side), else one wave's.
-#ifndef WFPT_NODE_REC_TEAM
-#define WFPT_NODE_REC_TEAM 1
-#endif
-// Team records (one block each, ~12 us) while the call's records fit in one
+// A speculative record is one block's work (its waves evaluate side by side)
+// or one wave's: team records (one block each, ~12 us) while the call's records fit in one
 // round of resident blocks (2 per CU: the kernel's 68 KB of LDS); beyond, one
 // wave per record (~21 us, but 4x as many side by side): multi-table calls of
 // several chains defer thousands of trials
-#ifndef WFPT_REC_TEAM_MAX
-#define WFPT_REC_TEAM_MAX 512
-#endif
+constexpr int kRecTeamMax = 512;
 // waves per SIMD the node chunk engine is compiled for (register budget)
 #ifndef WFPT_NODE_CHUNK_WAVES
 #define WFPT_NODE_CHUNK_WAVES 2
@@ -2524,12 +2341,6 @@ __global__ __launch_bounds__(kEngBlock, WFPT_NODE_CHUNK_WAVES) void node_chunk_k
     const int* clist, const int* n_chunks, const int64_t* r_idx, const Params* r_par,
     unsigned long long* evals, int* status, int* prof, int spec, int32_t n_nodes,
     int64_t nw_tab, NodeRare R) {
-#ifdef WFPT_NODE_DEBUG
-  const long long dbg_entry = __builtin_amdgcn_s_memrealtime();
-#else
-  const long long dbg_entry = 0;
-#endif
-  exp_table_init();
   __shared__ ChunkLds<1> lds[kEngWaves];
   const int lane = threadIdx.x & 63;
   ChunkLds<1>& cl = lds[threadIdx.x >> 6];
@@ -2540,7 +2351,7 @@ __global__ __launch_bounds__(kEngBlock, WFPT_NODE_CHUNK_WAVES) void node_chunk_k
   if (node_records_sparse(nrec, nc)) {  // a few deferred trials: one wave each
     if constexpr (!COUNT && (MODE == kAdaptT || MODE == kAdaptTZ)) {
       if (spec) {  // every tree point in two rounds (node_record_spec)
-        if (WFPT_NODE_REC_TEAM && nrec <= WFPT_REC_TEAM_MAX) {
+        if (nrec <= kRecTeamMax) {
           // one block per record, its waves side by side (wave 0's LDS)
           ChunkLds<1>& c0 = lds[0];
           const int wv = threadIdx.x >> 6;
@@ -2549,15 +2360,15 @@ __global__ __launch_bounds__(kEngBlock, WFPT_NODE_CHUNK_WAVES) void node_chunk_k
             const int64_t t = v / n, ix = v - t * n;
             node_record_spec<MODE, kEngWaves>(c0.F, c0.X, c0.fl, c0.tab, wv, lane, x + ix, K,
                                               lp + v, 0, r_par[k], R, lp, v,
-                                              (int32_t)(t * n_nodes + node[ix]), dbg_entry);
+                                              (int32_t)(t * n_nodes + node[ix]));
           }
         } else {
           for (int k = w0; k < nrec; k += nwaves) {
             const int64_t v = r_idx[k];
             const int64_t t = v / n, ix = v - t * n;
+            // F: 1088 doubles, fl: 64 ints
             node_record_spec<MODE, 1>(cl.F, cl.X, cl.fl, cl.tab, 0, lane, x + ix, K, lp + v, 0,
-                                      r_par[k], R, lp, v, (int32_t)(t * n_nodes + node[ix]),
-                                      dbg_entry);  // F: 1088 doubles, fl: 64 ints
+                                      r_par[k], R, lp, v, (int32_t)(t * n_nodes + node[ix]));
           }
         }
         return;
@@ -2677,7 +2488,6 @@ template <int MODE, int STK, bool COUNT, bool MULTI = false>
 __global__ __launch_bounds__(64, WFPT_SLOW_WAVES) void node_slow_kernel(
     const double* x, Knobs K, double* lp, const int64_t* d_idx, const Params* d_par,
     const int* n_defer, unsigned long long* evals, int* status) {
-  exp_table_init();
   using Stack = typename StackOf<STK>::type;
   const int nd = *n_defer;
   long long ne = 0;
@@ -2706,7 +2516,6 @@ template <int STK>
 __global__ __launch_bounds__(kBlock, WFPT_SLOW_WAVES) void multi_kernel(
     const double* x, int64_t n, const double* const* arr, const double* scal, Knobs K,
     double p_outlier, double* out, int* zeros, int* status, double* lpo) {
-  exp_table_init();
   using Stack = typename StackOf<STK>::type;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double lp = 0.0;
@@ -2769,7 +2578,6 @@ __global__ __launch_bounds__(kBlock, FastWaves<MODE>::value > 0 ? FastWaves<MODE
 void multi_fast_kernel(const double* x, int64_t n, const double* const* arr, const double* scal,
                        Knobs K, double p_outlier, double* lp, int64_t* d_idx, Params* d_par,
                        int* n_defer, unsigned long long* evals) {
-  exp_table_init();
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int lane = threadIdx.x & 63;
   long long ne = 0;
@@ -2853,15 +2661,10 @@ template <int MODE, bool COUNT, int OUT>
 static void run_fast(const TrialArgs& A, const Work& W, const EngTables& T, const Split& S,
                      bool lean, hipStream_t s, hipEvent_t fast_done) {
   if constexpr (MODE == kDirect) {
-    if (WFPT_DIRECT_ARGS) {
-      DirectArgs D;
-      direct_args(A.P, D);
-      hipLaunchKernelGGL((direct_kernel<COUNT, OUT>), dim3(fast_blocks(A.n)), dim3(kFastBlock), 0,
-                         s, A, W, D);
-    } else {
-      hipLaunchKernelGGL((fast_kernel<MODE, COUNT, OUT>), dim3(fast_blocks(A.n)),
-                         dim3(kFastBlock), 0, s, A, W);
-    }
+    DirectArgs D;
+    direct_args(A.P, D);
+    hipLaunchKernelGGL((direct_kernel<COUNT, OUT>), dim3(fast_blocks(A.n)), dim3(kFastBlock), 0, s,
+                       A, W, D);
   } else if (lean) {
     RootGrids R;
     root_grids(A.P, R);
@@ -2885,8 +2688,8 @@ static void run_deferred(const TrialArgs& A, const Work& W, const EngTables& T, 
       hipLaunchKernelGGL((engine_kernel<MODE, COUNT, OUT>), dim3((nw + kEngWaves - 1) / kEngWaves),
                          dim3(kEngBlock), 0, s, A, W, T, Split{});
   }
-  // the fold: one wave per chunk, up to WFPT_FOLD_GRID blocks of 4
-  const int64_t gf = std::min<int64_t>(WFPT_FOLD_GRID, (nw + 3) / 4);
+  // the fold: one wave per chunk, up to kFoldGrid blocks of 4
+  const int64_t gf = std::min<int64_t>(kFoldGrid, (nw + 3) / 4);
   hipLaunchKernelGGL((fold_kernel<MODE, COUNT, OUT>), dim3(gf), dim3(256), 0, s, A, W, nw);
 }
 
@@ -2992,12 +2795,8 @@ int launch_small(const double* x, int64_t n, const Params& P, const Knobs& K, do
                          Fa);                                                                \
       break;                                                                                 \
     default:                                                                                 \
-      if (WFPT_SMALL_SPLIT)                                                                  \
-        hipLaunchKernelGGL((small_split_kernel<kAdaptTZ, O_>), dim3(1), dim3(kSplitBlock), 0, s, \
-                           A, F, R, Fa);                                                     \
-      else                                                                                   \
-        hipLaunchKernelGGL((small_kernel<kAdaptTZ, O_>), dim3(1), dim3(kFastBlock), 0, s, A, F, \
-                           R, Fa);                                                           \
+      hipLaunchKernelGGL((small_split_kernel<kAdaptTZ, O_>), dim3(1), dim3(kSplitBlock), 0, s, \
+                         A, F, R, Fa);                                                       \
       break;                                                                                 \
   }
   if (trial) {
@@ -3006,7 +2805,7 @@ int launch_small(const double* x, int64_t n, const Params& P, const Knobs& K, do
     SMALL_MODES(OUT_SUM)
   }
 #undef SMALL_MODES
-  return (mode == kAdaptTZ && WFPT_SMALL_SPLIT) ? kSmallSplit : kSmallOne;
+  return mode == kAdaptTZ ? kSmallSplit : kSmallOne;
 }
 
 void launch_finalize(const double* part, const int* zeros, int64_t nb, int defer_bits,
@@ -3149,12 +2948,16 @@ void launch_segment_sum(const double* lp, const int64_t* off, int32_t n_nodes, d
                         int check_rare) {
   if (n_nodes <= 0) return;
   const int32_t nv = n_nodes * std::max(n_tables, 1);  // virtual nodes t m + j
+#if WFPT_PUB_DIAG
+  hipLaunchKernelGGL(segment_publish_diag_kernel, dim3((nv + 3) / 4), dim3(256), 0, s, lp, off, nv,
+                     status, res, out, seq, ticket, counters, n_nodes, n, check_rare);
+#else
   // one node per wave up to kPubBlocks blocks, then several per wave: the
-  // blocks' ticket releases serialise on one word (the diagnostic build keeps
-  // one node per wave)
-  const int32_t nb = WFPT_PUB_DIAG ? (nv + 3) / 4 : std::min<int32_t>((nv + 3) / 4, kPubBlocks);
+  // blocks' ticket releases serialise on one word
+  const int32_t nb = std::min<int32_t>((nv + 3) / 4, kPubBlocks);
   hipLaunchKernelGGL(segment_publish_kernel, dim3(nb), dim3(256), 0, s, lp, off, nv, status, res,
                      out, seq, ticket, counters, n_nodes, n, check_rare);
+#endif
 }
 
 template <int MODE, bool COUNT>

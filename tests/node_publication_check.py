@@ -12,8 +12,8 @@ each by a call whose result was read after a full stream synchronisation).
 
 prints one JSON line {calls, stale_calls, stale_nodes, first}. The GPU test
 runs it in-process on the shipped library (stale_calls must be 0) and in a
-child process on the WFPT_PUB_DIAG build (hddm_amd/lib/libwfpt_amd_pubdiag.so,
-whose non-last blocks store their sums only after the completion word): there
+child process on the WFPT_PUB_DIAG build (hddm_amd/lib/libwfpt_amd_pubdiag.so:
+segment_publish_diag_kernel, whose non-last blocks store their sums only after the completion word): there
 it must report stale calls, i.e. the check can see the failure it guards
 against.
 """

@@ -148,3 +148,35 @@ def test_raw_prototypes_bind_the_declared_entry_points():
     rc = _lib.raw_wiener_like(None, None, ctypes.addressof(p), ctypes.addressof(k),
                               ctypes.addressof(out))
     assert rc == 2
+
+
+# The compile-time switches of hddm_amd/csrc: the occupancy / geometry
+# constants that a kept tool builds or the next rounds tune, and the two
+# diagnostic builds. A rejected experiment's arm is deleted, not left here.
+BUILD_SWITCHES = {
+    "WFPT_FAST_WAVES", "WFPT_FAST_WAVES_TZ", "WFPT_SLOW_WAVES", "WFPT_ENG_WAVES",
+    "WFPT_NODE_CHUNK_WAVES", "WFPT_LEAN_BLOCK", "WFPT_SPLIT", "WFPT_PUB_NODES",
+    "WFPT_CDF_CHUNK", "WFPT_CDF_WAVES", "WFPT_PHASE_TIMING", "WFPT_PUB_DIAG"}
+
+
+def test_build_switch_inventory():
+    """Every WFPT_* name a preprocessor conditional under hddm_amd/csrc tests
+    is on the allow-list, and every define the variant tables build exists."""
+    import importlib.util
+    from hddm_amd import build as hb
+    found = set()
+    for f in os.listdir(hb.CSRC):
+        for line in open(os.path.join(hb.CSRC, f)):
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                found |= set(re.findall(r"\bWFPT_[A-Z0-9_]+", line))
+    assert found == BUILD_SWITCHES, sorted(found ^ BUILD_SWITCHES)
+    tables = [hb.VARIANTS]
+    for tool in ("ab_variants", "ab_cdf"):
+        spec = importlib.util.spec_from_file_location(
+            tool, os.path.join(ROOT, "tools", tool + ".py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        tables.append(mod.VARIANTS)
+    named = {d.split("=")[0] for t in tables for v in t.values() for d in v
+             if not d.startswith("-")}
+    assert named <= found, sorted(named - found)

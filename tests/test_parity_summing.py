@@ -130,7 +130,7 @@ def test_lean_kernel_per_trial_on_bench_dataset(gpu, oracle_lib):
 @pytest.mark.gpu
 def test_c2_direct_kernel_per_trial_10m(gpu, oracle_lib):
     """C2's timed kernel at dataset scale: the 10M simple-DDM resident dataset
-    (tests/test_parity_strict.py's C2 data) through fast_kernel<kDirect>'s
+    (tests/test_parity_strict.py's C2 data) through direct_kernel's
     OUT_BOTH build. Its chunk partials and total are bitwise the plain call's,
     each term is within 1e-6 of the reference's addend (src/wfpt.pyx:66-74),
     and every one of the plain call's 156,250 chunk partials is within 1e-12

@@ -17,21 +17,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 VARIANTS = {
-    "base": ["WFPT_CDF_CHUNK=1", "WFPT_CDF_BEY=0", "WFPT_CDF_READLANE=0"],
-    "chunk8": ["WFPT_CDF_BEY=0"],
-    "bey": ["WFPT_CDF_CHUNK=1", "WFPT_CDF_READLANE=0"],
-    "new": [],
-    "new_w16k": ["WFPT_CDF_WAVES=16384"],
-    "new_c4": ["WFPT_CDF_CHUNK=4"],
-    "debug": ["WFPT_CDF_DEBUG", "WFPT_CDF_CHUNK=1", "WFPT_CDF_READLANE=0"],
-    "debug_rl": ["WFPT_CDF_DEBUG"],
-    "rl": [],
-    "stage": [],
-    "debug_stage": ["WFPT_CDF_DEBUG"],
-    "nodpp": ["WFPT_CDF_DPP=0"],
-    "dpp": [],
-    "dpp_c1": ["WFPT_CDF_CHUNK=1"],
-    "dpp_c4": ["WFPT_CDF_CHUNK=4"],
+    "default": [],
+    "w16k": ["WFPT_CDF_WAVES=16384"],
+    "c1": ["WFPT_CDF_CHUNK=1"],
+    "c4": ["WFPT_CDF_CHUNK=4"],
 }
 LIBDIR = os.path.join(ROOT, "hddm_amd", "lib", "variants")
 

@@ -17,27 +17,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 VARIANTS = {
     "default": [],
-    "exptab": ["WFPT_EXP_TABLE=1"],
-    "exptab_lds": ["WFPT_EXP_TABLE=2"],
-    "nodedbg": ["WFPT_NODE_DEBUG"],
-    "nodedbg_solo": ["WFPT_NODE_DEBUG", "WFPT_NODE_REC_TEAM=0"],
-    "nodedbg_entry": ["WFPT_NODE_DEBUG", "WFPT_NODE_DEBUG_ENTRY"],
-    "stamps_noout": ["WFPT_NODE_DEBUG", "WFPT_NODE_DEBUG_NOOUT"],
-    "recfence": ["WFPT_REC_FENCES=1"],
-    "syncfence": ["WFPT_SYNC_FENCE=1"],
     "pub_diag": ["WFPT_PUB_DIAG=1"],
-    "fastdbg": ["WFPT_NODE_DEBUG_FAST"],
     "ilp": ["-mllvm -amdgpu-sched-strategy=max-ilp"],
     "occbias": ["-mllvm -amdgpu-schedule-metric-bias=100"],
     "memclause": ["-mllvm -amdgpu-sched-strategy=max-memory-clause"],
     "wavepri": ["-mllvm -amdgpu-set-wave-priority"],
     "latbias": ["-mllvm -amdgpu-schedule-metric-bias=0"],
-    "rec_solo": ["WFPT_NODE_REC_TEAM=0"],
-    "direct_off": ["WFPT_DIRECT_ARGS=0"],
     "lb64": ["WFPT_LEAN_BLOCK=64"],
     "lb128": ["WFPT_LEAN_BLOCK=128"],
     "phase": ["WFPT_PHASE_TIMING"],
-    "htot0": ["WFPT_HEAVY_TOTAL=0"],
     "split16": ["WFPT_SPLIT=16"],
     "split4": ["WFPT_SPLIT=4"],
     "pubnodes1": ["WFPT_PUB_NODES=1"],

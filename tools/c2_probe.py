@@ -1,7 +1,7 @@
 """Config 2 probe: simple DDM (v, a, t) Navarro-Fuss pdf over 10M resident
 trials on one GPU (BASELINE.json configs[1]), HDDM knobs, p_outlier .05;
 K timed wiener_like calls plus HIP-event kernel time of the level-0 pass
-(fast_kernel<kDirect>). For rocprofv3 passes (tools/gpu_profile_cmd.sh).
+(direct_kernel). For rocprofv3 passes (tools/gpu_profile_cmd.sh).
 
     python tools/c2_probe.py [--reps 20] [--trials 10000000]
 """
