@@ -141,6 +141,28 @@ PATH_LEAN, PATH_ENGINE, PATH_SMALL, PATH_REDO = 1, 2, 4, 8
 PATH_FOLD, PATH_DIRECT, PATH_FIXED, PATH_SPLIT = 16, 32, 64, 128
 PATH_SMALL_SPLIT, PATH_NODE_SPLIT, PATH_NODE_RARE = 256, 512, 1024
 wfpt_decode_result = _sig("wfpt_decode_result", _I, [_PD, _PD])
+# reinforcement-learning family (include/wfpt_amd.h)
+_PI64 = ctypes.POINTER(_I64)
+wfpt_rl_dataset_create = _sig("wfpt_rl_dataset_create", _I,
+                              [_VP, _PD, _PI64, _PD, _PI64, _I64, ctypes.POINTER(_I32), _I32,
+                               ctypes.POINTER(_VP)])
+wfpt_rl_dataset_destroy = _sig("wfpt_rl_dataset_destroy", None, [_VP])
+wfpt_wiener_like_rlddm = _sig("wfpt_wiener_like_rlddm", _I, [_VP, _VP, _D, _D, _D, _PP, _PK, _PD])
+wfpt_wiener_like_rlddm_ex = _sig("wfpt_wiener_like_rlddm_ex", _I,
+                                 [_VP, _VP, _D, _D, _D, _PP, _PK, _PD, _PD, _PD])
+wfpt_wiener_like_rl = _sig("wfpt_wiener_like_rl", _I, [_VP, _VP, _D, _D, _D, _D, _D, _D, _D, _PD])
+wfpt_wiener_like_rl_ex = _sig("wfpt_wiener_like_rl_ex", _I,
+                              [_VP, _VP, _D, _D, _D, _D, _D, _D, _D, _PD, _PD, _PD])
+wfpt_wiener_like_multi_rlddm = _sig("wfpt_wiener_like_multi_rlddm", _I,
+                                    [_VP, _PD, _PI64, _PD, _PI64, _I64, _D, ctypes.POINTER(_PD),
+                                     _PD, _PK, _D, _PD])
+wfpt_wiener_like_multi_rlddm_ex = _sig("wfpt_wiener_like_multi_rlddm_ex", _I,
+                                       [_VP, _PD, _PI64, _PD, _PI64, _I64, _D,
+                                        ctypes.POINTER(_PD), _PD, _PK, _D, _PD, _PD, _PD])
+wfpt_wiener_like_rlddm_nodes = _sig("wfpt_wiener_like_rlddm_nodes", _I,
+                                    [_VP, _VP, _PD, _PP, _PK, _PD])
+wfpt_wiener_like_rlddm_nodes_ex = _sig("wfpt_wiener_like_rlddm_nodes_ex", _I,
+                                       [_VP, _VP, _PD, _PP, _PK, _PD, _PD, _PD])
 
 EXPORTED = [
     "wfpt_device_count", "wfpt_open", "wfpt_close", "wfpt_last_error", "wfpt_dataset_create",
@@ -155,6 +177,10 @@ EXPORTED = [
     "wfpt_wiener_like_trials", "wfpt_dataset_order", "wfpt_debug_partials", "wfpt_last_path",
     "wfpt_wiener_like_local", "wfpt_wiener_like_nodes_local", "wfpt_wiener_like_nodes_allreduce",
     "wfpt_wiener_like_nodes_multi", "wfpt_wiener_like_nodes_multi_ex",
+    "wfpt_rl_dataset_create", "wfpt_rl_dataset_destroy", "wfpt_wiener_like_rlddm",
+    "wfpt_wiener_like_rlddm_ex", "wfpt_wiener_like_rl", "wfpt_wiener_like_rl_ex",
+    "wfpt_wiener_like_multi_rlddm", "wfpt_wiener_like_multi_rlddm_ex",
+    "wfpt_wiener_like_rlddm_nodes", "wfpt_wiener_like_rlddm_nodes_ex",
 ]
 
 # error encoding of a result triple (include/wfpt_amd.h: wfpt_decode_result)

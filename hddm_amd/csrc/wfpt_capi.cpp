@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/wfpt_amd.h"
+#include "rl_internal.h"
 #include "wfpt_device.hpp"
 #include "wfpt_internal.h"
 
@@ -118,6 +119,8 @@ struct MappedBuf {
   }
 };
 
+struct wfpt_rl_ds;
+
 struct wfpt_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -203,6 +206,14 @@ struct wfpt_ctx {
   // the context's live datasets: wfpt_close releases their device memory and
   // detaches them (a dataset destroyed after its context only frees itself)
   std::vector<wfpt_ds*> dsets;
+  // RL family (rl_kernels.hip): per-call workspaces and the live RL datasets
+  DevBuf<double> rl_drift;     // the scan's drifts, compact (scored trials)
+  DevBuf<double> rl_drift_in;  // ... of every trial in the caller's order (_ex calls)
+  DevBuf<double> rl_arr;       // node batch: per-trial parameter arrays (rl_fill_kernel)
+  DevBuf<double> rl_npart;     // node batch: block partials of the per-node sums
+  DevBuf<wfpt::RlRow> rl_rows; // node batch: the nodes' Q-learning rows
+  DevBuf<wfpt::Params> rl_par; // node batch: the nodes' DDM rows
+  std::vector<wfpt_rl_ds*> rl_dsets;
 };
 
 constexpr int64_t kSplitCap = 16384;  // heavy chunks a dataset records per call (both classes)
@@ -268,6 +279,7 @@ struct DeviceGuard {
 };
 
 void ds_free_device(wfpt_ds* d);  // defined with wfpt_dataset_destroy
+void rl_detach(wfpt_rl_ds* d);    // defined with wfpt_rl_dataset_destroy
 
 wfpt::Params to_params(const wfpt_params* p) {
   wfpt::Params q;
@@ -777,6 +789,14 @@ void wfpt_close(wfpt_ctx* c) {
     d->ctx = nullptr;
   }
   c->dsets.clear();
+  for (wfpt_rl_ds* d : c->rl_dsets) rl_detach(d);
+  c->rl_dsets.clear();
+  c->rl_drift.release();
+  c->rl_drift_in.release();
+  c->rl_arr.release();
+  c->rl_npart.release();
+  c->rl_rows.release();
+  c->rl_par.release();
   if (c->comm) (void)ncclCommDestroy(c->comm);
   c->x.release();
   c->part.release();
@@ -1887,6 +1907,573 @@ int wfpt_synchronize(wfpt_ctx* c) {
   DeviceGuard g(c->device);
   HIP_TRY(hipStreamSynchronize(c->stream));
   return WFPT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Reinforcement-learning family (wfpt.pyx:79-241, 277-320; rl_kernels.hip).
+
+// The fixed per-trial inputs of the RL likelihoods, resident: laid out once on
+// the host (rl_internal.h: RlLayout), uploaded once.
+struct wfpt_rl_ds {
+  wfpt_ctx* ctx = nullptr;
+  int64_t n = 0;        // trials
+  int64_t m = 0;        // scored trials (all but each segment's first; all when by_runs)
+  int32_t n_seg = 0;
+  int32_t n_nodes = 0;  // 0: created without node ids
+  bool has_rt = false;
+  bool by_runs = false;  // wiener_like_multi_rlddm's segments (runs of equal split_by)
+  double* x_c = nullptr;  // [m] RTs of the scored trials, compact
+  int64_t* lane_start = nullptr;
+  int64_t* lane_out = nullptr;
+  int64_t* lane_len = nullptr;
+  int32_t* lane_node = nullptr;
+  int64_t* step_off = nullptr;
+  unsigned char* resp_t = nullptr;
+  double* fb_t = nullptr;
+  int64_t* caller = nullptr;
+  unsigned char* resp_c = nullptr;  // [m] responses of the scored trials
+  int32_t* node_c = nullptr;        // [m] their nodes
+  int64_t* node_off = nullptr;      // [n_nodes + 1] compact range of each node
+  std::vector<int64_t> c2caller;    // host [m]: the caller's index of a compact trial
+  std::vector<int64_t> node_off_host;  // host copy of node_off
+  int64_t node_max = 0;             // most scored trials in one node
+};
+
+namespace {
+
+constexpr double kRlBase = 2.718281828459;  // the reference's literal (wfpt.pyx:123)
+
+// (2.718281828459**alpha) / (1 + 2.718281828459**alpha), libm pow (wfpt.pyx:123-125)
+double rl_rate(double alpha) {
+  const double e = std::pow(kRlBase, alpha);
+  return e / (1 + e);
+}
+
+template <class T>
+hipError_t rl_up(T** dst, const std::vector<T>& v) {
+  hipError_t e = hipMalloc((void**)dst, std::max<size_t>(v.size(), 1) * sizeof(T));
+  if (e == hipSuccess && !v.empty())
+    e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+  return e;
+}
+
+void rl_free_device(wfpt_rl_ds* d) {
+  void** ptrs[] = {(void**)&d->x_c,      (void**)&d->lane_start, (void**)&d->lane_out,
+                   (void**)&d->lane_len, (void**)&d->lane_node,  (void**)&d->step_off,
+                   (void**)&d->resp_t,   (void**)&d->fb_t,       (void**)&d->caller,
+                   (void**)&d->resp_c,   (void**)&d->node_c,     (void**)&d->node_off};
+  for (void** p : ptrs) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+}
+
+void rl_detach(wfpt_rl_ds* d) {
+  rl_free_device(d);
+  d->ctx = nullptr;
+}
+
+// Lays the trials out and uploads them (context locked by the caller).
+// by_runs: segments are the runs of equal adjacent split_by values, every
+// trial scored (wfpt.pyx:300-318); else the (node, condition) groups,
+// conditions in rising order as np.unique gives them, the caller's order kept
+// inside a group (the boolean masks of wfpt.pyx:114-116), the first trial of
+// each unscored.
+int rl_build(wfpt_ctx* c, const double* rt, const int64_t* response, const double* feedback,
+             const int64_t* split_by, int64_t n, const int32_t* node_id, int32_t n_nodes,
+             bool by_runs, wfpt_rl_ds** out) {
+  for (int64_t i = 0; i < n; ++i) {
+    if (response[i] != 0 && response[i] != 1)
+      return fail(WFPT_ERR_ARG, "response must be 0 or 1 (trial " + std::to_string(i) + ")");
+    if (rt && std::fabs(rt[i]) == 999.)
+      return fail(WFPT_ERR_ARG, "|rt| == 999 at trial " + std::to_string(i) +
+                                    ": the RL likelihoods have no missing-response code");
+    if (node_id && (node_id[i] < 0 || node_id[i] >= n_nodes))
+      return fail(WFPT_ERR_ARG, "node id out of range at trial " + std::to_string(i));
+  }
+  std::vector<int64_t> idx(n);
+  for (int64_t i = 0; i < n; ++i) idx[i] = i;
+  if (!by_runs)
+    std::stable_sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b) {
+      if (node_id && node_id[a] != node_id[b]) return node_id[a] < node_id[b];
+      return split_by[a] < split_by[b];
+    });
+  std::vector<int64_t> seg_start;
+  for (int64_t j = 0; j < n; ++j) {
+    const int64_t a = idx[j], b = j ? idx[j - 1] : 0;
+    if (j == 0 || split_by[a] != split_by[b] || (node_id && node_id[a] != node_id[b]))
+      seg_start.push_back(j);
+  }
+  if (seg_start.size() > (size_t)INT32_MAX) return fail(WFPT_ERR_ARG, "too many segments");
+  const int32_t ns = (int32_t)seg_start.size();
+  seg_start.push_back(n);
+  auto seg_len = [&](int32_t s) { return seg_start[s + 1] - seg_start[s]; };
+  const int64_t m = by_runs ? n : n - ns;
+  // lanes: the segments by falling length
+  std::vector<int32_t> lane(ns);
+  for (int32_t s = 0; s < ns; ++s) lane[s] = s;
+  std::stable_sort(lane.begin(), lane.end(),
+                   [&](int32_t a, int32_t b) { return seg_len(a) > seg_len(b); });
+  const int64_t lmax = ns ? seg_len(lane[0]) : 0;
+  std::vector<int64_t> step_off(lmax + 1, 0);
+  for (int32_t s = 0; s < ns; ++s) step_off[seg_len(s)]++;  // histogram of the lengths
+  {
+    int64_t longer = 0, acc = 0;  // longer: segments with more than k trials
+    for (int64_t k = lmax; k >= 0; --k) {
+      const int64_t here = step_off[k];
+      step_off[k] = longer;
+      longer += here;
+    }
+    for (int64_t k = 0; k <= lmax; ++k) {  // counts -> offsets
+      const int64_t cnt = step_off[k];
+      step_off[k] = acc;
+      acc += cnt;
+    }
+  }
+  std::vector<int64_t> lane_start(ns), lane_out(ns), lane_len(ns);
+  std::vector<int32_t> lane_node(node_id ? ns : 0);
+  std::vector<unsigned char> resp_t(n);
+  std::vector<double> fb_t(n);
+  for (int32_t r = 0; r < ns; ++r) {
+    const int32_t s = lane[r];
+    lane_start[r] = seg_start[s];
+    lane_out[r] = by_runs ? seg_start[s] : seg_start[s] - s;
+    lane_len[r] = seg_len(s);
+    if (node_id) lane_node[r] = node_id[idx[seg_start[s]]];
+    for (int64_t k = 0; k < lane_len[r]; ++k) {
+      const int64_t src = idx[seg_start[s] + k];
+      resp_t[step_off[k] + r] = (unsigned char)response[src];
+      fb_t[step_off[k] + r] = feedback[src];
+    }
+  }
+  auto* d = new wfpt_rl_ds();
+  std::vector<double> x_c(rt ? m : 0);
+  std::vector<unsigned char> resp_c(m);
+  std::vector<int32_t> node_c(node_id ? m : 0);
+  std::vector<int64_t> node_off(node_id ? n_nodes + 1 : 0, 0);
+  d->c2caller.resize(m);
+  {
+    int64_t k = 0;
+    for (int32_t s = 0; s < ns; ++s)
+      for (int64_t j = seg_start[s] + (by_runs ? 0 : 1); j < seg_start[s + 1]; ++j, ++k) {
+        const int64_t src = idx[j];
+        if (rt) x_c[k] = rt[src];
+        resp_c[k] = (unsigned char)response[src];
+        d->c2caller[k] = src;
+        if (node_id) {
+          node_c[k] = node_id[src];
+          node_off[node_id[src] + 1]++;
+        }
+      }
+  }
+  for (int32_t j = 0; node_id && j < n_nodes; ++j) {
+    d->node_max = std::max(d->node_max, node_off[j + 1]);
+    node_off[j + 1] += node_off[j];
+  }
+  d->node_off_host = node_off;
+  d->ctx = c;
+  d->n = n;
+  d->m = m;
+  d->n_seg = ns;
+  d->n_nodes = node_id ? n_nodes : 0;
+  d->has_rt = rt != nullptr;
+  d->by_runs = by_runs;
+  hipError_t e = rl_up(&d->x_c, x_c);
+  if (e == hipSuccess) e = rl_up(&d->lane_start, lane_start);
+  if (e == hipSuccess) e = rl_up(&d->lane_out, lane_out);
+  if (e == hipSuccess) e = rl_up(&d->lane_len, lane_len);
+  if (e == hipSuccess && node_id) e = rl_up(&d->lane_node, lane_node);
+  if (e == hipSuccess) e = rl_up(&d->step_off, step_off);
+  if (e == hipSuccess) e = rl_up(&d->resp_t, resp_t);
+  if (e == hipSuccess) e = rl_up(&d->fb_t, fb_t);
+  if (e == hipSuccess && !by_runs) e = rl_up(&d->caller, idx);
+  if (e == hipSuccess) e = rl_up(&d->resp_c, resp_c);
+  if (e == hipSuccess && node_id) e = rl_up(&d->node_c, node_c);
+  if (e == hipSuccess && node_id) e = rl_up(&d->node_off, node_off);
+  if (e != hipSuccess) {
+    rl_free_device(d);
+    delete d;
+    return fail(WFPT_ERR_HIP, std::string("RL dataset upload: ") + hipGetErrorString(e));
+  }
+  *out = d;
+  return WFPT_OK;
+}
+
+wfpt::RlLayout rl_layout(const wfpt_rl_ds* d) {
+  wfpt::RlLayout L;
+  L.n_seg = d->n_seg;
+  L.lane_start = d->lane_start;
+  L.lane_out = d->lane_out;
+  L.lane_len = d->lane_len;
+  L.lane_node = d->lane_node;
+  L.step_off = d->step_off;
+  L.resp_t = d->resp_t;
+  L.fb_t = d->fb_t;
+  L.caller = d->caller;
+  L.score_first = d->by_runs ? 1 : 0;
+  return L;
+}
+
+// The scan of one call: drifts into c->rl_drift (compact) and, for an _ex
+// call, c->rl_drift_in (every trial, the caller's order). Opens the call's
+// profile bracket.
+int rl_scan(wfpt_ctx* c, const wfpt_rl_ds* d, const wfpt::RlRow& one, const wfpt::RlRow* rows,
+            const double* vmul, const double* rate, bool want_drift) {
+  HIP_TRY(c->rl_drift.reserve(std::max<int64_t>(d->m, 1)));
+  const bool separate = want_drift && !d->by_runs;  // by_runs: compact == the caller's order
+  if (separate) HIP_TRY(c->rl_drift_in.reserve(std::max<int64_t>(d->n, 1)));
+  if (c->count) HIP_TRY(hipMemsetAsync(c->evals, 0, sizeof(unsigned long long), c->stream));
+  if (c->profile) HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  wfpt::launch_rl_scan(rl_layout(d), one, rows, vmul, rate, c->rl_drift.p,
+                       separate ? c->rl_drift_in.p : nullptr, c->stream);
+  HIP_TRY(hipGetLastError());
+  return WFPT_OK;
+}
+
+// run_multi's scoring over arrays that are already on the device: dptr[j] (j =
+// v, sv, a, z, sz, t, st) a device array of m values or null for scal[j]. A
+// uniform adaptive / direct family takes the level-0 pass + deferred records,
+// anything else the generic per-trial kernel, exactly as run_multi chooses.
+// Leaves each trial's term in c->lp and the block sums in c->part / c->zero.
+// The workspaces are sized for `total` trials (>= m) and the pointer /
+// scalar tables of slots [0, nslots) go up in one copy each (dptr / scal hold
+// 7 entries per slot and stay alive until the call has finished).
+int rl_score_reserve(wfpt_ctx* c, int64_t total, int nslots, double* const* dptr,
+                     const double* scal) {
+  HIP_TRY(c->mptr.reserve(7 * (size_t)nslots));
+  HIP_TRY(c->mscal.reserve(7 * (size_t)nslots));
+  HIP_TRY(hipMemcpyAsync(c->mptr.p, dptr, 7 * nslots * sizeof(double*), hipMemcpyHostToDevice,
+                         c->stream));
+  HIP_TRY(hipMemcpyAsync(c->mscal.p, scal, 7 * nslots * sizeof(double), hipMemcpyHostToDevice,
+                         c->stream));
+  const int64_t nb = wfpt::blocks_for(total);
+  HIP_TRY(c->part.reserve(std::max<int64_t>(nb, 1)));
+  HIP_TRY(c->zero.reserve(std::max<int64_t>(nb, 1)));
+  HIP_TRY(c->lp.reserve(std::max<int64_t>(total, 1)));
+  HIP_TRY(c->nd_idx.reserve(std::max<int64_t>(total, 1)));
+  HIP_TRY(c->nd_par.reserve(std::max<int64_t>(total, 1)));
+  return WFPT_OK;
+}
+
+// The scoring launches over m trials with the tables of `slot`: terms into lp,
+// block sums into c->part / c->zero.
+int rl_score_launch(wfpt_ctx* c, const double* dx, int64_t m, int slot, double* const dptr[7],
+                    const double scal[7], const wfpt::Knobs& K, double p_outlier, double* lp) {
+  const int mode =
+      (dptr[4] || dptr[6]) ? -1 : wfpt::select_mode(scal[4], scal[6], K.use_adaptive);
+  if (mode >= 0 && mode <= wfpt::kAdaptTZ && m > 0) {
+    HIP_TRY(hipMemsetAsync(c->n_defer, 0, sizeof(int), c->stream));
+    wfpt::launch_multi_fast(mode, dx, m, c->mptr.p + 7 * slot, c->mscal.p + 7 * slot, K,
+                            p_outlier, lp, c->nd_idx.p, c->nd_par.p, c->n_defer, c->part.p,
+                            c->zero.p, c->count ? c->evals : nullptr, c->status, c->stream);
+  } else {
+    wfpt::launch_multi(dx, m, c->mptr.p + 7 * slot, c->mscal.p + 7 * slot, K, p_outlier,
+                       c->part.p, c->zero.p, c->status, c->stream, lp);
+  }
+  HIP_TRY(hipGetLastError());
+  return WFPT_OK;
+}
+
+int rl_score(wfpt_ctx* c, const double* dx, int64_t m, double* const dptr[7],
+             const double scal[7], const wfpt::Knobs& K, double p_outlier) {
+  if (int rc = rl_score_reserve(c, m, 1, dptr, scal)) return rc;
+  return rl_score_launch(c, dx, m, 0, dptr, scal, K, p_outlier, c->lp.p);
+}
+
+// Closes the profile bracket, adds the m trials' block sums in finalize's fixed
+// order and waits for the call: *out = the sum (a zero mixture density's
+// log, -inf, is a term of it).
+int rl_finish(wfpt_ctx* c, int64_t m, double* out) {
+  if (c->profile) HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  wfpt::launch_finalize(c->part.p, c->zero.p, wfpt::blocks_for(m), 0, c->status, c->mres_dev,
+                        ++c->seq, c->stream, nullptr, nullptr, nullptr, nullptr, c->fin,
+                        c->fin_ticket);
+  HIP_TRY(hipGetLastError());
+  if (int rc = wait_result(c, c->mres)) return rc;
+  if (int rc = check_status_value(c->mres[2])) return rc;
+  if (int rc = finish_profile(c)) return rc;
+  *out = c->mres[0];
+  return WFPT_OK;
+}
+
+// The _ex outputs of a finished call, in the caller's order: out_trial (each
+// scored trial's term from c->lp, 0.0 for an unscored first trial), out_drift.
+int rl_outputs(wfpt_ctx* c, const wfpt_rl_ds* d, double* out_trial, double* out_drift) {
+  if (out_trial && d->n > 0) {
+    std::vector<double> h(std::max<int64_t>(d->m, 1));
+    if (d->m > 0)
+      HIP_TRY(hipMemcpy(h.data(), c->lp.p, d->m * sizeof(double), hipMemcpyDeviceToHost));
+    std::fill(out_trial, out_trial + d->n, 0.0);
+    for (int64_t i = 0; i < d->m; ++i) out_trial[d->c2caller[i]] = h[i];
+  }
+  if (out_drift && d->n > 0)
+    HIP_TRY(hipMemcpy(out_drift, d->by_runs ? c->rl_drift.p : c->rl_drift_in.p,
+                      d->n * sizeof(double), hipMemcpyDeviceToHost));
+  return WFPT_OK;
+}
+
+int rl_check_ds(wfpt_ctx* c, const wfpt_rl_ds* d, bool need_rt) {
+  if (!wfpt::rl_kernels_linked())
+    return fail(WFPT_ERR_UNSUPPORTED, "this build does not contain the RL kernels");
+  if (d->ctx != c) return fail(WFPT_ERR_ARG, "RL dataset belongs to another context");
+  if (d->by_runs) return fail(WFPT_ERR_ARG, "RL dataset laid out for wiener_like_multi_rlddm");
+  if (need_rt && !d->has_rt)
+    return fail(WFPT_ERR_ARG, "RL dataset was created without RTs (choice-only model)");
+  return WFPT_OK;
+}
+
+wfpt::RlRow rl_row(double q, double alpha, double pos_alpha, double v) {
+  wfpt::RlRow R;
+  R.q = q;
+  R.alfa = rl_rate(alpha);
+  R.pos_alfa = pos_alpha == 100.00 ? R.alfa : rl_rate(pos_alpha);  // wfpt.pyx:105-108
+  R.v = v;
+  return R;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wfpt_rl_dataset_create(wfpt_ctx* c, const double* rt, const int64_t* response,
+                           const double* feedback, const int64_t* split_by, int64_t n,
+                           const int32_t* node_id, int32_t n_nodes, wfpt_rl_ds** out) {
+  if (!c || !out) return fail(WFPT_ERR_ARG, "null pointer");
+  if (n < 0) return fail(WFPT_ERR_ARG, "n < 0");
+  if (n > 0 && (!response || !feedback || !split_by))
+    return fail(WFPT_ERR_ARG, "null response / feedback / split_by array");
+  if (node_id && n_nodes <= 0) return fail(WFPT_ERR_ARG, "node ids need n_nodes > 0");
+  WFPT_RANGE("wfpt_rl_dataset_create");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  wfpt_rl_ds* d = nullptr;
+  if (int rc = rl_build(c, rt, response, feedback, split_by, n, node_id, n_nodes, false, &d))
+    return rc;
+  c->rl_dsets.push_back(d);
+  *out = d;
+  return WFPT_OK;
+}
+
+void wfpt_rl_dataset_destroy(wfpt_rl_ds* d) {
+  if (!d) return;
+  if (wfpt_ctx* c = d->ctx) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    c->rl_dsets.erase(std::remove(c->rl_dsets.begin(), c->rl_dsets.end(), d), c->rl_dsets.end());
+    rl_free_device(d);
+  }
+  delete d;
+}
+
+int wfpt_wiener_like_rlddm_ex(wfpt_ctx* c, const wfpt_rl_ds* d, double q, double alpha,
+                              double pos_alpha, const wfpt_params* p, const wfpt_knobs* k,
+                              double* out, double* out_trial, double* out_drift) {
+  if (!c || !d || !p || !k || !out) return fail(WFPT_ERR_ARG, "null pointer");
+  if (int rc = rl_check_ds(c, d, true)) return rc;
+  if (!p_outlier_in_range(p->p_outlier)) {  // wfpt.pyx:102-103
+    *out = -INFINITY;
+    return WFPT_OK;
+  }
+  const wfpt::Knobs K = to_knobs(k);
+  WFPT_RANGE("wfpt_wiener_like_rlddm");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  if (int rc = rl_scan(c, d, rl_row(q, alpha, pos_alpha, p->v), nullptr, nullptr, nullptr,
+                       out_drift != nullptr))
+    return rc;
+  double* dptr[7] = {c->rl_drift.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const double scal[7] = {0.0, p->sv, p->a, p->z, p->sz, p->t, p->st};
+  if (int rc = rl_score(c, d->x_c, d->m, dptr, scal, K, p->p_outlier)) return rc;
+  if (int rc = rl_finish(c, d->m, out)) return rc;
+  return rl_outputs(c, d, out_trial, out_drift);
+}
+
+int wfpt_wiener_like_rlddm(wfpt_ctx* c, const wfpt_rl_ds* d, double q, double alpha,
+                           double pos_alpha, const wfpt_params* p, const wfpt_knobs* k,
+                           double* out) {
+  return wfpt_wiener_like_rlddm_ex(c, d, q, alpha, pos_alpha, p, k, out, nullptr, nullptr);
+}
+
+int wfpt_wiener_like_rl_ex(wfpt_ctx* c, const wfpt_rl_ds* d, double q, double alpha,
+                           double pos_alpha, double v, double z, double p_outlier,
+                           double w_outlier, double* out, double* out_trial,
+                           double* out_drift) {
+  if (!c || !d || !out) return fail(WFPT_ERR_ARG, "null pointer");
+  if (int rc = rl_check_ds(c, d, false)) return rc;
+  if (!p_outlier_in_range(p_outlier)) {  // wfpt.pyx:178-179
+    *out = -INFINITY;
+    return WFPT_OK;
+  }
+  WFPT_RANGE("wfpt_wiener_like_rl");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  if (int rc = rl_scan(c, d, rl_row(q, alpha, pos_alpha, v), nullptr, nullptr, nullptr,
+                       out_drift != nullptr))
+    return rc;
+  const int64_t nb = wfpt::blocks_for(d->m);
+  HIP_TRY(c->part.reserve(std::max<int64_t>(nb, 1)));
+  HIP_TRY(c->zero.reserve(std::max<int64_t>(nb, 1)));
+  HIP_TRY(c->lp.reserve(std::max<int64_t>(d->m, 1)));
+  wfpt::launch_rl_choice(c->rl_drift.p, d->resp_c, d->m, z, p_outlier, w_outlier * p_outlier,
+                         c->lp.p, c->part.p, c->zero.p, c->stream);
+  HIP_TRY(hipGetLastError());
+  if (int rc = rl_finish(c, d->m, out)) return rc;
+  return rl_outputs(c, d, out_trial, out_drift);
+}
+
+int wfpt_wiener_like_rl(wfpt_ctx* c, const wfpt_rl_ds* d, double q, double alpha,
+                        double pos_alpha, double v, double z, double p_outlier, double w_outlier,
+                        double* out) {
+  return wfpt_wiener_like_rl_ex(c, d, q, alpha, pos_alpha, v, z, p_outlier, w_outlier, out,
+                                nullptr, nullptr);
+}
+
+int wfpt_wiener_like_multi_rlddm_ex(wfpt_ctx* c, const double* x, const int64_t* response,
+                                    const double* feedback, const int64_t* split_by, int64_t n,
+                                    double q, const double* const arrays[8],
+                                    const double scalars[8], const wfpt_knobs* k,
+                                    double p_outlier, double* out, double* out_trial,
+                                    double* out_drift) {
+  if (!c || !arrays || !scalars || !k || !out) return fail(WFPT_ERR_ARG, "null pointer");
+  if (n < 0) return fail(WFPT_ERR_ARG, "n < 0");
+  if (n > 0 && (!x || !response || !feedback || !split_by))
+    return fail(WFPT_ERR_ARG, "null x / response / feedback / split_by array");
+  if (!wfpt::rl_kernels_linked())
+    return fail(WFPT_ERR_UNSUPPORTED, "this build does not contain the RL kernels");
+  const wfpt::Knobs K = to_knobs(k);
+  WFPT_RANGE("wfpt_wiener_like_multi_rlddm");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  wfpt_rl_ds* d = nullptr;
+  if (int rc = rl_build(c, x, response, feedback, split_by, n, nullptr, 0, true, &d)) return rc;
+  // per-trial alpha -> per-trial learning rates (wfpt.pyx:317), on the host
+  std::vector<double> rate(arrays[7] ? n : 0);
+  for (int64_t i = 0; i < (int64_t)rate.size(); ++i) rate[i] = rl_rate(arrays[7][i]);
+  auto run = [&]() -> int {
+    int na = 0;
+    for (int j = 0; j < 8; ++j) na += arrays[j] != nullptr;
+    HIP_TRY(c->marr.reserve(std::max<int64_t>((int64_t)na * n, 1)));
+    double* dev[8];
+    int slot = 0;
+    for (int j = 0; j < 8; ++j) {
+      dev[j] = nullptr;
+      if (!arrays[j]) continue;
+      dev[j] = c->marr.p + (int64_t)slot++ * n;
+      if (n > 0)
+        HIP_TRY(hipMemcpyAsync(dev[j], j == 7 ? rate.data() : arrays[j], n * sizeof(double),
+                               hipMemcpyHostToDevice, c->stream));
+    }
+    wfpt::RlRow one;
+    one.q = q;
+    one.alfa = one.pos_alfa = arrays[7] ? 0.0 : rl_rate(scalars[7]);
+    one.v = scalars[0];
+    if (int rc = rl_scan(c, d, one, nullptr, dev[0], dev[7], out_drift != nullptr)) return rc;
+    double* dptr[7] = {c->rl_drift.p, dev[1], dev[2], dev[3], dev[4], dev[5], dev[6]};
+    if (int rc = rl_score(c, d->x_c, n, dptr, scalars, K, p_outlier)) return rc;
+    if (int rc = rl_finish(c, n, out)) return rc;
+    return rl_outputs(c, d, out_trial, out_drift);
+  };
+  const int rc = run();
+  if (rc != WFPT_OK) (void)hipStreamSynchronize(c->stream);  // nothing may still read d
+  rl_free_device(d);
+  delete d;
+  return rc;
+}
+
+int wfpt_wiener_like_multi_rlddm(wfpt_ctx* c, const double* x, const int64_t* response,
+                                 const double* feedback, const int64_t* split_by, int64_t n,
+                                 double q, const double* const arrays[8], const double scalars[8],
+                                 const wfpt_knobs* k, double p_outlier, double* out) {
+  return wfpt_wiener_like_multi_rlddm_ex(c, x, response, feedback, split_by, n, q, arrays,
+                                         scalars, k, p_outlier, out, nullptr, nullptr);
+}
+
+int wfpt_wiener_like_rlddm_nodes_ex(wfpt_ctx* c, const wfpt_rl_ds* d, const double* rl_rows,
+                                    const wfpt_params* per_node, const wfpt_knobs* k,
+                                    double* out_logp, double* out_trial, double* out_drift) {
+  if (!c || !d || !rl_rows || !per_node || !k || !out_logp)
+    return fail(WFPT_ERR_ARG, "null pointer");
+  if (int rc = rl_check_ds(c, d, true)) return rc;
+  const int32_t nn = d->n_nodes;
+  if (nn <= 0) return fail(WFPT_ERR_ARG, "RL dataset was created without node ids");
+  if (d->node_max > wfpt::kRlNodeMax)
+    return fail(WFPT_ERR_UNSUPPORTED, "a node holds more scored trials than the per-node sum takes");
+  for (int32_t j = 1; j < nn; ++j)  // the per-trial-parameter pass takes one p_outlier
+    if (per_node[j].p_outlier != per_node[0].p_outlier)
+      return fail(WFPT_ERR_UNSUPPORTED, "the RL node batch needs one p_outlier for all nodes");
+  const double p_outlier = per_node[0].p_outlier;
+  if (!p_outlier_in_range(p_outlier)) {  // wfpt.pyx:102-103, every node
+    for (int32_t j = 0; j < nn; ++j) out_logp[j] = -INFINITY;
+    return WFPT_OK;
+  }
+  const wfpt::Knobs K = to_knobs(k);
+  WFPT_RANGE("wfpt_wiener_like_rlddm_nodes");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  std::vector<wfpt::RlRow> rows(nn);
+  std::vector<wfpt::Params> par(nn);
+  for (int32_t j = 0; j < nn; ++j) {
+    rows[j] = rl_row(rl_rows[3 * j], rl_rows[3 * j + 1], rl_rows[3 * j + 2], per_node[j].v);
+    par[j] = to_params(&per_node[j]);
+  }
+  HIP_TRY(c->rl_rows.reserve(nn));
+  HIP_TRY(c->rl_par.reserve(nn));
+  HIP_TRY(hipMemcpyAsync(c->rl_rows.p, rows.data(), nn * sizeof(wfpt::RlRow),
+                         hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->rl_par.p, par.data(), nn * sizeof(wfpt::Params),
+                         hipMemcpyHostToDevice, c->stream));
+  const int64_t m = d->m;
+  // sv, a, z and t per trial (rl_fill_kernel); sz and st stay scalars, so the
+  // scoring pass is the one the single-node call takes (the level-0 pass for
+  // the adaptive / direct families) and gives the same bits per trial: one
+  // launch when the nodes share sz and st (HDDM's default: group-only), else
+  // one per run of consecutive nodes that do
+  constexpr int mask = 0x2e;
+  HIP_TRY(c->rl_arr.reserve(std::max<int64_t>(4 * m, 1)));
+  if (int rc = rl_scan(c, d, wfpt::RlRow{}, c->rl_rows.p, nullptr, nullptr, out_drift != nullptr))
+    return rc;
+  wfpt::launch_rl_fill(d->node_c, m, c->rl_par.p, mask, c->rl_arr.p, c->stream);
+  HIP_TRY(hipGetLastError());
+  std::vector<int32_t> run_lo;  // first node of each run
+  for (int32_t j = 0; j < nn; ++j)
+    if (j == 0 || per_node[j].sz != per_node[j - 1].sz || per_node[j].st != per_node[j - 1].st)
+      run_lo.push_back(j);
+  const int nruns = (int)run_lo.size();
+  run_lo.push_back(nn);
+  std::vector<double*> tabs(7 * (size_t)nruns, nullptr);
+  std::vector<double> scals(7 * (size_t)nruns, 0.0);
+  for (int r = 0; r < nruns; ++r) {
+    const int64_t lo = d->node_off_host[run_lo[r]];
+    tabs[7 * r] = c->rl_drift.p + lo;
+    for (int f = 1, slot = 0; f < 7; ++f)
+      if (mask & (1 << f)) tabs[7 * r + f] = c->rl_arr.p + (int64_t)slot++ * m + lo;
+    scals[7 * r + 4] = per_node[run_lo[r]].sz;
+    scals[7 * r + 6] = per_node[run_lo[r]].st;
+  }
+  if (int rc = rl_score_reserve(c, m, nruns, tabs.data(), scals.data())) return rc;
+  for (int r = 0; r < nruns; ++r) {
+    const int64_t lo = d->node_off_host[run_lo[r]], hi = d->node_off_host[run_lo[r + 1]];
+    if (int rc = rl_score_launch(c, d->x_c + lo, hi - lo, r, &tabs[7 * r], &scals[7 * r], K,
+                                 p_outlier, c->lp.p + lo))
+      return rc;
+  }
+  HIP_TRY(c->rl_npart.reserve(wfpt::rl_node_partials(m, nn)));
+  HIP_TRY(c->res.reserve(nn));
+  wfpt::launch_rl_node_sum(c->lp.p, d->node_off, nn, c->rl_npart.p, c->res.p, c->stream);
+  HIP_TRY(hipGetLastError());
+  double total;  // a finalize over no partials: the status word and the call's completion
+  if (int rc = rl_finish(c, 0, &total)) return rc;
+  HIP_TRY(hipMemcpy(out_logp, c->res.p, nn * sizeof(double), hipMemcpyDeviceToHost));
+  return rl_outputs(c, d, out_trial, out_drift);
+}
+
+int wfpt_wiener_like_rlddm_nodes(wfpt_ctx* c, const wfpt_rl_ds* d, const double* rl_rows,
+                                 const wfpt_params* per_node, const wfpt_knobs* k,
+                                 double* out_logp) {
+  return wfpt_wiener_like_rlddm_nodes_ex(c, d, rl_rows, per_node, k, out_logp, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -7,14 +7,19 @@ hddm/likelihoods.py:54-60,86) and the CDF through `cdfdif_wrapper`
 (hddm/__init__.py:11,19; hddm/likelihoods.py:91). `install()` rebinds only the
 hot-path attributes of those module objects, so every holder of the module sees
 the MI355X functions while the names this engine does not provide
-(`wiener_like_rl*`, `wiener_like_contaminant`, `gen_cdf_using_pdf`, `split_cdf`,
-wfpt.pyx:79-421) keep the reference's implementations.
+(`wiener_like_contaminant`, `gen_cdf_using_pdf`, `split_cdf`, wfpt.pyx:357-421)
+keep the reference's implementations. The reinforcement-learning likelihoods
+(`wiener_like_rlddm`, `wiener_like_rl`, `wiener_like_multi_rlddm`,
+wfpt.pyx:79-241, 277-320) are rebound only on request, `install(rl=True)`:
+they reject |rt| == 999 and responses outside {0, 1}, which the reference's
+versions accept.
 """
 import importlib
 import sys
 
 HOT_PATH = ("pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "gen_rts_from_cdf")
 CDF_PATH = ("dmat_cdf_array",)
+RL_PATH = ("wiener_like_rlddm", "wiener_like_rl", "wiener_like_multi_rlddm")
 
 
 class Installation:
@@ -65,8 +70,12 @@ def _patch(inst, key, target, ours, names):
     return target
 
 
-def install(wfpt_module=None, cdfdif_module=None, likelihoods_module=None):
+def install(wfpt_module=None, cdfdif_module=None, likelihoods_module=None, rl=False):
     """Route HDDM's likelihood and CDF calls to libwfpt_amd.so.
+
+    `rl=True` also rebinds the reinforcement-learning likelihoods (RL_PATH)
+    that HDDMrl, Hrl and HDDMrlRegressor call (hddm/models/hddm_rl.py:61-73,
+    rl.py:145-158); by default they stay the reference's.
 
     `wfpt_module` / `cdfdif_module` default to the already-imported (or
     importable) reference extensions `wfpt` and `cdfdif_wrapper`; when one is
@@ -85,7 +94,8 @@ def install(wfpt_module=None, cdfdif_module=None, likelihoods_module=None):
     from . import likelihoods as amd_lk
     from . import wfpt as amd_wfpt
     inst = Installation()
-    _patch(inst, "wfpt", _find("wfpt", wfpt_module), amd_wfpt, HOT_PATH)
+    _patch(inst, "wfpt", _find("wfpt", wfpt_module), amd_wfpt,
+           HOT_PATH + RL_PATH if rl else HOT_PATH)
     _patch(inst, "cdfdif_wrapper", _find("cdfdif_wrapper", cdfdif_module), amd_cdf, CDF_PATH)
     lk = likelihoods_module if likelihoods_module is not None else sys.modules.get("hddm.likelihoods")
     if lk is not None:

@@ -7,6 +7,9 @@ module that `hddm/__init__.py:16` imports as `hddm.wfpt`:
     wiener_like src/wfpt.pyx:54-76    (defaults n_st=n_sz=10, simps_err=1e-8, w_outlier=0.1)
     full_pdf    src/pdf.pxi:104-146   (cpdef; defaults n_st=n_sz=2, simps_err=1e-3)
     wiener_like_multi  src/wfpt.pyx:244-274
+    wiener_like_rlddm        src/wfpt.pyx:79-154   (Q-learning drift; RLDataset: resident data)
+    wiener_like_rl           src/wfpt.pyx:157-241  (choice probability only)
+    wiener_like_multi_rlddm  src/wfpt.pyx:277-320  (per-trial parameters, adjacent-change reset)
     gen_rts_from_cdf   src/wfpt.pyx:323-354 (density grid on the GPU, sampling in NumPy)
 
 Every density is computed by the HIP kernels of libwfpt_amd.so; there is no
@@ -25,7 +28,9 @@ import numpy as np
 from . import _lib
 
 __all__ = ["pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "gen_rts_from_cdf",
-           "Dataset", "prob_ub"]
+           "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl", "wiener_like_multi_rlddm",
+           "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_terms",
+           "wiener_like_rl_terms", "wiener_like_multi_rlddm_terms"]
 
 
 def _check_x(x, name="x"):
@@ -409,3 +414,276 @@ class Dataset:
                                                ctypes.byref(K), _lib.dptr(out)))
         del keep
         return out
+
+
+# ---------------------------------------------------------------------------
+# Reinforcement-learning family (src/wfpt.pyx:79-241, 277-320)
+
+def _check_long(a, name):
+    """Cython `np.ndarray[long, ndim=1]` argument semantics."""
+    if not isinstance(a, np.ndarray):
+        raise TypeError(f"Argument '{name}' has incorrect type (expected numpy.ndarray, got "
+                        f"{type(a).__name__})")
+    if a.dtype != np.int64:
+        raise ValueError(f"Buffer dtype mismatch, expected 'long' but got {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"Buffer has wrong number of dimensions (expected 1, got {a.ndim})")
+    return np.ascontiguousarray(a)
+
+
+def _i64ptr(a):
+    return a.ctypes.data_as(_lib._PI64)
+
+
+def _same_length(n, **arrays):
+    for nm, arr in arrays.items():
+        if arr.shape[0] != n:
+            raise ValueError(f"{nm} must have one entry per trial ({n}), got {arr.shape[0]}")
+
+
+def _multi_rl_args(n, v, sv, a, z, sz, t, st, alpha, multi):
+    """_multi_args with the eighth parameter of wiener_like_multi_rlddm, alpha
+    (wfpt.pyx:296)."""
+    names = ("v", "sv", "a", "z", "sz", "t", "st", "alpha")
+    vals = (v, sv, a, z, sz, t, st, alpha)
+    multi = set(multi)
+    keep = []
+    ptrs = (_lib._PD * 8)()
+    scal = np.zeros(8)
+    for j, (nm, val) in enumerate(zip(names, vals)):
+        if nm in multi:
+            arr = np.ascontiguousarray(np.asarray(val, dtype=np.float64))
+            if arr.shape != (n,):
+                raise ValueError(f"parameter {nm} must have one value per trial")
+            keep.append(arr)
+            ptrs[j] = _lib.dptr(arr)
+        else:
+            ptrs[j] = _lib._PD()
+            scal[j] = float(val)
+    return ptrs, scal, keep
+
+
+class RLDataset:
+    """The fixed inputs of the RL likelihoods (RT, response, feedback,
+    condition) resident in HBM: per call only the scalars go to the device.
+    `rt` may be None for the choice-only model (wiener_like_rl). Optional
+    `node_id` groups trials into `n_nodes` likelihood nodes scored together by
+    `wiener_like_rlddm_nodes`. |rt| == 999 is rejected (ValueError): the RL
+    likelihoods have no missing-response code."""
+
+    def __init__(self, rt, response, feedback, split_by, node_id=None, n_nodes=None, device=None,
+                 ctx=None):
+        response = np.ascontiguousarray(np.asarray(response, dtype=np.int64).ravel())
+        n = response.shape[0]
+        feedback = np.ascontiguousarray(np.asarray(feedback, dtype=np.float64).ravel())
+        split_by = np.ascontiguousarray(np.asarray(split_by, dtype=np.int64).ravel())
+        _same_length(n, feedback=feedback, split_by=split_by)
+        if rt is not None:
+            rt = np.ascontiguousarray(np.asarray(rt, dtype=np.float64).ravel())
+            _same_length(n, rt=rt)
+        self.ctx = ctx if ctx is not None else _lib.context(device)
+        self.n = n
+        self._host = (rt, response, feedback, split_by)
+        node = nptr = None
+        self.n_nodes = 0
+        if node_id is not None:
+            node = np.ascontiguousarray(np.asarray(node_id, dtype=np.int32).ravel())
+            _same_length(n, node_id=node)
+            self.n_nodes = int(n_nodes if n_nodes is not None else (node.max() + 1 if node.size
+                                                                    else 0))
+            nptr = node.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        h = _lib._VP()
+        _lib.check(_lib.wfpt_rl_dataset_create(
+            self.ctx.handle, _lib.dptr(rt) if rt is not None else None, _i64ptr(response),
+            _lib.dptr(feedback), _i64ptr(split_by), n, nptr, self.n_nodes, ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.wfpt_rl_dataset_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.n
+
+    def _outputs(self, terms):
+        if not terms:
+            return None, None, None, None
+        tr = np.empty(self.n, dtype=np.float64)
+        dr = np.empty(self.n, dtype=np.float64)
+        return tr, dr, _lib.dptr(tr), _lib.dptr(dr)
+
+    def wiener_like_rlddm(self, q, alpha, pos_alpha, v, sv, a, z, sz, t, st, err, n_st=10,
+                          n_sz=10, use_adaptive=1, simps_err=1e-8, p_outlier=0, w_outlier=0,
+                          terms=False):
+        """wiener_like_rlddm (wfpt.pyx:79-154) over the resident trials.
+        terms=True: (sum, per-trial terms, per-trial drifts), caller order."""
+        P = _lib.make_params(v, sv, a, z, sz, t, st, p_outlier)
+        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        out = ctypes.c_double()
+        tr, dr, ptr, pdr = self._outputs(terms)
+        _lib.check(_lib.wfpt_wiener_like_rlddm_ex(
+            self.ctx.handle, self.handle, float(q), float(alpha), float(pos_alpha),
+            ctypes.byref(P), ctypes.byref(K), ctypes.byref(out), ptr, pdr))
+        return (out.value, tr, dr) if terms else out.value
+
+    def wiener_like_rl(self, q, alpha, pos_alpha, v, z, err=1e-4, n_st=10, n_sz=10,
+                       use_adaptive=1, simps_err=1e-8, p_outlier=0, w_outlier=0, terms=False):
+        """wiener_like_rl (wfpt.pyx:157-241): err, n_st, n_sz, use_adaptive and
+        simps_err are accepted and ignored, as in the reference."""
+        out = ctypes.c_double()
+        tr, dr, ptr, pdr = self._outputs(terms)
+        _lib.check(_lib.wfpt_wiener_like_rl_ex(
+            self.ctx.handle, self.handle, float(q), float(alpha), float(pos_alpha), float(v),
+            float(z), float(p_outlier), float(w_outlier), ctypes.byref(out), ptr, pdr))
+        return (out.value, tr, dr) if terms else out.value
+
+    def wiener_like_multi_rlddm(self, q, v, sv, a, z, sz, t, st, alpha, err, multi=None, n_st=10,
+                                n_sz=10, use_adaptive=1, simps_err=1e-3, p_outlier=0,
+                                w_outlier=0, terms=False):
+        """wiener_like_multi_rlddm (wfpt.pyx:277-320). Its segments (runs of
+        equal adjacent split_by) and per-trial arrays differ per model, so this
+        call works from the host copies, not the resident layout."""
+        rt, response, feedback, split_by = self._host
+        if rt is None:
+            raise ValueError("wiener_like_multi_rlddm needs RTs")
+        if multi is None:
+            return full_pdf(rt, v, sv, a, z, sz, t, st, err)  # wfpt.pyx:293-294
+        ptrs, scal, keep = _multi_rl_args(self.n, v, sv, a, z, sz, t, st, alpha, multi)
+        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        out = ctypes.c_double()
+        tr, dr, ptr, pdr = self._outputs(terms)
+        _lib.check(_lib.wfpt_wiener_like_multi_rlddm_ex(
+            self.ctx.handle, _lib.dptr(rt), _i64ptr(response), _lib.dptr(feedback),
+            _i64ptr(split_by), self.n, float(q), ptrs, _lib.dptr(scal), ctypes.byref(K),
+            float(p_outlier), ctypes.byref(out), ptr, pdr))
+        del keep
+        return (out.value, tr, dr) if terms else out.value
+
+    def wiener_like_rlddm_nodes(self, rl_rows, params, err=1e-4, n_st=2, n_sz=2, use_adaptive=1,
+                                simps_err=1e-3, w_outlier=0.1, terms=False):
+        """One wiener_like_rlddm per node in one scan + one scoring pass:
+        rl_rows (n_nodes, 3) of q, alpha, pos_alpha; params (n_nodes, 8) of v,
+        sv, a, z, sz, t, st, p_outlier (one p_outlier for all nodes). Returns
+        the per-node sums; terms=True: (sums, per-trial terms, drifts)."""
+        if self.n_nodes == 0:
+            raise ValueError("dataset was created without node ids")
+        rr = np.ascontiguousarray(rl_rows, dtype=np.float64)
+        pm = np.ascontiguousarray(params, dtype=np.float64)
+        if rr.shape != (self.n_nodes, 3):
+            raise ValueError(f"rl_rows must have shape ({self.n_nodes}, 3)")
+        if pm.shape != (self.n_nodes, 8):
+            raise ValueError(f"params must have shape ({self.n_nodes}, 8)")
+        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        out = np.empty(self.n_nodes, dtype=np.float64)
+        tr, dr, ptr, pdr = self._outputs(terms)
+        _lib.check(_lib.wfpt_wiener_like_rlddm_nodes_ex(
+            self.ctx.handle, self.handle, _lib.dptr(rr), pm.ctypes.data_as(_lib._PP),
+            ctypes.byref(K), _lib.dptr(out), ptr, pdr))
+        return (out, tr, dr) if terms else out
+
+
+def _rl_dataset(x, response, feedback, split_by):
+    """A transient RLDataset from arguments checked as Cython checks them, in
+    the reference's argument order."""
+    if x is not None:
+        x = _check_x(x)
+    response = _check_long(response, "response")
+    feedback = _check_x(feedback, "feedback")
+    split_by = _check_long(split_by, "split_by")
+    return RLDataset(x, response, feedback, split_by)
+
+
+def wiener_like_rlddm(x, response, feedback, split_by, q, alpha, pos_alpha, v, sv, a, z, sz, t,
+                      st, err, n_st=10, n_sz=10, use_adaptive=1, simps_err=1e-8, p_outlier=0,
+                      w_outlier=0):
+    ds = _rl_dataset(x, response, feedback, split_by)
+    try:
+        return ds.wiener_like_rlddm(q, alpha, pos_alpha, v, sv, a, z, sz, t, st, err, n_st, n_sz,
+                                    use_adaptive, simps_err, p_outlier, w_outlier)
+    finally:
+        ds.close()
+
+
+def wiener_like_rl(response, feedback, split_by, q, alpha, pos_alpha, v, z, err=1e-4, n_st=10,
+                   n_sz=10, use_adaptive=1, simps_err=1e-8, p_outlier=0, w_outlier=0):
+    ds = _rl_dataset(None, response, feedback, split_by)
+    try:
+        return ds.wiener_like_rl(q, alpha, pos_alpha, v, z, err, n_st, n_sz, use_adaptive,
+                                 simps_err, p_outlier, w_outlier)
+    finally:
+        ds.close()
+
+
+def wiener_like_multi_rlddm(x, response, feedback, split_by, q, v, sv, a, z, sz, t, st, alpha,
+                            err, multi=None, n_st=10, n_sz=10, use_adaptive=1, simps_err=1e-3,
+                            p_outlier=0, w_outlier=0):
+    return wiener_like_multi_rlddm_terms(x, response, feedback, split_by, q, v, sv, a, z, sz, t,
+                                         st, alpha, err, multi, n_st, n_sz, use_adaptive,
+                                         simps_err, p_outlier, w_outlier, _terms=False)
+
+
+def wiener_like_rlddm_terms(x, response, feedback, split_by, q, alpha, pos_alpha, v, sv, a, z,
+                            sz, t, st, err, n_st=10, n_sz=10, use_adaptive=1, simps_err=1e-8,
+                            p_outlier=0, w_outlier=0):
+    """wiener_like_rlddm returning (sum, terms, drift): terms[i] is trial i's
+    log term (0.0 for the unscored first trial of a condition), drift[i] the
+    drift the recurrence holds when it reaches trial i."""
+    ds = _rl_dataset(x, response, feedback, split_by)
+    try:
+        return ds.wiener_like_rlddm(q, alpha, pos_alpha, v, sv, a, z, sz, t, st, err, n_st, n_sz,
+                                    use_adaptive, simps_err, p_outlier, w_outlier, terms=True)
+    finally:
+        ds.close()
+
+
+def wiener_like_rl_terms(response, feedback, split_by, q, alpha, pos_alpha, v, z, err=1e-4,
+                         n_st=10, n_sz=10, use_adaptive=1, simps_err=1e-8, p_outlier=0,
+                         w_outlier=0):
+    """wiener_like_rl returning (sum, terms, drift), as wiener_like_rlddm_terms."""
+    ds = _rl_dataset(None, response, feedback, split_by)
+    try:
+        return ds.wiener_like_rl(q, alpha, pos_alpha, v, z, err, n_st, n_sz, use_adaptive,
+                                 simps_err, p_outlier, w_outlier, terms=True)
+    finally:
+        ds.close()
+
+
+def wiener_like_multi_rlddm_terms(x, response, feedback, split_by, q, v, sv, a, z, sz, t, st,
+                                  alpha, err, multi, n_st=10, n_sz=10, use_adaptive=1,
+                                  simps_err=1e-3, p_outlier=0, w_outlier=0, _terms=True):
+    """wiener_like_multi_rlddm returning (sum, terms, drift); every trial is
+    scored here, the first of a run at drift 0."""
+    x = _check_x(x)
+    response = _check_long(response, "response")
+    feedback = _check_x(feedback, "feedback")
+    split_by = _check_long(split_by, "split_by")
+    if multi is None:
+        return full_pdf(x, v, sv, a, z, sz, t, st, err)  # wfpt.pyx:293-294 (TypeError for arrays)
+    n = x.shape[0]
+    _same_length(n, response=response, feedback=feedback, split_by=split_by)
+    ptrs, scal, keep = _multi_rl_args(n, v, sv, a, z, sz, t, st, alpha, multi)
+    c = _lib.context()
+    K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+    out = ctypes.c_double()
+    tr = np.empty(n, dtype=np.float64) if _terms else None
+    dr = np.empty(n, dtype=np.float64) if _terms else None
+    _lib.check(_lib.wfpt_wiener_like_multi_rlddm_ex(
+        c.handle, _lib.dptr(x), _i64ptr(response), _lib.dptr(feedback), _i64ptr(split_by), n,
+        float(q), ptrs, _lib.dptr(scal), ctypes.byref(K), float(p_outlier), ctypes.byref(out),
+        _lib.dptr(tr) if _terms else None, _lib.dptr(dr) if _terms else None))
+    del keep
+    return (out.value, tr, dr) if _terms else out.value
+
+
+def wiener_like_rlddm_nodes(ds, rl_rows, params, err=1e-4, n_st=2, n_sz=2, use_adaptive=1,
+                            simps_err=1e-3, w_outlier=0.1, terms=False):
+    """RLDataset.wiener_like_rlddm_nodes as a module function."""
+    return ds.wiener_like_rlddm_nodes(rl_rows, params, err, n_st, n_sz, use_adaptive, simps_err,
+                                      w_outlier, terms)

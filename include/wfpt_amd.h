@@ -170,6 +170,95 @@ int wfpt_wiener_like_multi_resident_ex(wfpt_ctx *ctx, const wfpt_ds *ds,
                                        const wfpt_knobs *k, double p_outlier, double *out_logp,
                                        double *out_trial);
 
+/* ---- reinforcement-learning likelihoods (Q-learning drift) --------------- */
+/* The reference's RL family: a Q-value pair per condition, updated trial by
+ * trial from the feedback, sets each trial's drift (qs[1] - qs[0]) * v.
+ *   wfpt_wiener_like_rlddm*       <- wfpt.wiener_like_rlddm       src/wfpt.pyx:79-154
+ *   wfpt_wiener_like_rl*          <- wfpt.wiener_like_rl          src/wfpt.pyx:157-241
+ *   wfpt_wiener_like_multi_rlddm* <- wfpt.wiener_like_multi_rlddm src/wfpt.pyx:277-320
+ *   wfpt_wiener_like_rlddm_nodes* <- one wiener_like_rlddm per node, batched
+ * The recurrence runs on the device bit for bit as the reference computes it
+ * (learning rates pow(2.718281828459, alpha) / (1 + pow(2.718281828459,
+ * alpha)) from the host's libm; q + alfa * (f - q) in three roundings; strict
+ * feedback > q), so every drift equals the reference's exactly. The densities
+ * come from the per-trial-parameter pass of wfpt_wiener_like_multi with the
+ * drifts in its v slot.
+ * Divergence from the reference: |rt| == 999 is rejected (WFPT_ERR_ARG). The
+ * per-trial-parameter pass scores +-999 as a missing response by prob_ub
+ * (wfpt.pyx:267-270); the reference's RL functions pass it to full_pdf like
+ * any other RT. */
+typedef struct wfpt_rl_ds wfpt_rl_ds;
+/* Uploads the fixed inputs of the RL likelihoods once (wfpt.pyx:79-82: x,
+ * response, feedback, split_by). rt is nullable (choice-only model,
+ * wfpt_wiener_like_rl); response[n] must be 0 or 1 (the reference indexes qs
+ * with it unchecked); node_id (nullable) / n_nodes as in wfpt_dataset_create.
+ * Trials are grouped into one segment per (node, condition), conditions in
+ * rising split_by order (np.unique, wfpt.pyx:100), the caller's order kept
+ * inside a condition (the masks of wfpt.pyx:114-116). WFPT_ERR_ARG: a response
+ * outside {0, 1}, n < 0, a null array with n > 0, |rt| == 999, a node id out
+ * of range. The caller's arrays are not retained. */
+int wfpt_rl_dataset_create(wfpt_ctx *ctx, const double *rt, const int64_t *response,
+                           const double *feedback, const int64_t *split_by, int64_t n,
+                           const int32_t *node_id, int32_t n_nodes, wfpt_rl_ds **out);
+void wfpt_rl_dataset_destroy(wfpt_rl_ds *ds);
+/* wiener_like_rlddm (wfpt.pyx:79-154) over a resident RL dataset; p->v is the
+ * drift scaling. pos_alpha == 100.0 means "use alpha" (wfpt.pyx:105-108).
+ * -inf for a p_outlier outside [0, 1] (wfpt.pyx:102-103; the _ex outputs are
+ * then left untouched) or a scored trial of zero mixture density (:138-139).
+ * The first trial of every condition only updates q (:121-130). */
+int wfpt_wiener_like_rlddm(wfpt_ctx *ctx, const wfpt_rl_ds *ds, double q, double alpha,
+                           double pos_alpha, const wfpt_params *p, const wfpt_knobs *k,
+                           double *out_logp);
+/* The _ex siblings of the RL entries: out_trial (nullable, n values, the
+ * caller's order) receives each trial's log term, 0.0 for an unscored first
+ * trial; out_drift (nullable, n values) the drift the recurrence holds when it
+ * reaches the trial, for every trial. */
+int wfpt_wiener_like_rlddm_ex(wfpt_ctx *ctx, const wfpt_rl_ds *ds, double q, double alpha,
+                              double pos_alpha, const wfpt_params *p, const wfpt_knobs *k,
+                              double *out_logp, double *out_trial, double *out_drift);
+/* wiener_like_rl (wfpt.pyx:157-241): the choice probability alone. As the
+ * reference does, it applies p_outlier and w_outlier, no a, and ignores err,
+ * n_st, n_sz, use_adaptive and simps_err (not taken here). */
+int wfpt_wiener_like_rl(wfpt_ctx *ctx, const wfpt_rl_ds *ds, double q, double alpha,
+                        double pos_alpha, double v, double z, double p_outlier,
+                        double w_outlier, double *out_logp);
+int wfpt_wiener_like_rl_ex(wfpt_ctx *ctx, const wfpt_rl_ds *ds, double q, double alpha,
+                           double pos_alpha, double v, double z, double p_outlier,
+                           double w_outlier, double *out_logp, double *out_trial,
+                           double *out_drift);
+/* wiener_like_multi_rlddm (wfpt.pyx:277-320) on host arrays (uploaded for this
+ * call). arrays[j] (j = v, sv, a, z, sz, t, st, alpha) is a host array of n
+ * values or NULL to use scalars[j]. Its semantics differ from
+ * wiener_like_rlddm's, as in the reference: the Q pair resets where split_by[i]
+ * != split_by[i - 1] (an adjacent change, not a grouping), every trial is
+ * scored (the first at drift 0), there is one learning rate, no p_outlier
+ * range check and no early -inf (log(0) enters the sum). */
+int wfpt_wiener_like_multi_rlddm(wfpt_ctx *ctx, const double *x, const int64_t *response,
+                                 const double *feedback, const int64_t *split_by, int64_t n,
+                                 double q, const double *const arrays[8],
+                                 const double scalars[8], const wfpt_knobs *k, double p_outlier,
+                                 double *out_logp);
+int wfpt_wiener_like_multi_rlddm_ex(wfpt_ctx *ctx, const double *x, const int64_t *response,
+                                    const double *feedback, const int64_t *split_by, int64_t n,
+                                    double q, const double *const arrays[8],
+                                    const double scalars[8], const wfpt_knobs *k,
+                                    double p_outlier, double *out_logp, double *out_trial,
+                                    double *out_drift);
+/* One wiener_like_rlddm per node of a dataset created with node ids, in one
+ * scan launch and one scoring pass: rl_rows[3 j ..] = node j's (q, alpha,
+ * pos_alpha), per_node[j] its DDM row, out_logp[n_nodes]. Node j's sum is bit
+ * for bit wfpt_wiener_like_rlddm on that node's trials with that node's row.
+ * sz and st stay scalars of the scoring pass: one launch when all nodes share
+ * them (HDDM's default: group-only parameters), else one per run of
+ * consecutive nodes that do. The nodes must share p_outlier, and a node may
+ * hold at most 2^22 scored trials (WFPT_ERR_UNSUPPORTED otherwise). */
+int wfpt_wiener_like_rlddm_nodes(wfpt_ctx *ctx, const wfpt_rl_ds *ds, const double *rl_rows,
+                                 const wfpt_params *per_node, const wfpt_knobs *k,
+                                 double *out_logp);
+int wfpt_wiener_like_rlddm_nodes_ex(wfpt_ctx *ctx, const wfpt_rl_ds *ds, const double *rl_rows,
+                                    const wfpt_params *per_node, const wfpt_knobs *k,
+                                    double *out_logp, double *out_trial, double *out_drift);
+
 /* ---- DMAT / Tuerlinckx CDF ---------------------------------------------- */
 /* Per-trial CDF of signed RTs with the outlier mixture, exactly
  * cdfdif_wrapper.dmat_cdf_array(x, v, sv, a, z, sz, t, st, p_outlier, w_outlier)
