@@ -163,6 +163,14 @@ wfpt_wiener_like_rlddm_nodes = _sig("wfpt_wiener_like_rlddm_nodes", _I,
                                     [_VP, _VP, _PD, _PP, _PK, _PD])
 wfpt_wiener_like_rlddm_nodes_ex = _sig("wfpt_wiener_like_rlddm_nodes_ex", _I,
                                        [_VP, _VP, _PD, _PP, _PK, _PD, _PD, _PD])
+# RT sampler (include/wfpt_amd.h)
+_U64 = ctypes.c_uint64
+wfpt_gen_rts_nodes = _sig("wfpt_gen_rts_nodes", _I,
+                          [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD])
+wfpt_gen_rts_nodes_ex = _sig("wfpt_gen_rts_nodes_ex", _I,
+                             [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD, _PD,
+                              _PD, _PI64, _PD, _PD])
+wfpt_profile_stages = _sig("wfpt_profile_stages", _I, [_VP, _PD, _I])
 
 EXPORTED = [
     "wfpt_device_count", "wfpt_open", "wfpt_close", "wfpt_last_error", "wfpt_dataset_create",
@@ -181,6 +189,7 @@ EXPORTED = [
     "wfpt_wiener_like_rlddm_ex", "wfpt_wiener_like_rl", "wfpt_wiener_like_rl_ex",
     "wfpt_wiener_like_multi_rlddm", "wfpt_wiener_like_multi_rlddm_ex",
     "wfpt_wiener_like_rlddm_nodes", "wfpt_wiener_like_rlddm_nodes_ex",
+    "wfpt_gen_rts_nodes", "wfpt_gen_rts_nodes_ex", "wfpt_profile_stages",
 ]
 
 # error encoding of a result triple (include/wfpt_amd.h: wfpt_decode_result)
@@ -258,6 +267,13 @@ class Context:
         check(wfpt_profile_read(self.handle, ctypes.byref(ms), ctypes.byref(nl),
                                 ctypes.byref(ne), 1 if reset else 0))
         return ms.value, nl.value, ne.value
+
+    def profile_stages(self, reset=False):
+        """Device ms of the RT sampler's stages since the last reset
+        (wfpt_profile_stages): density, scan, normalise, draws."""
+        a = (_D * 4)()
+        check(wfpt_profile_stages(self.handle, a, 1 if reset else 0))
+        return dict(zip(("density", "scan", "normalise", "draws"), a))
 
     def profile_lists(self, reset=False):
         """Deferred-pass list sizes (include/wfpt_amd.h: wfpt_profile_lists)."""

@@ -1,0 +1,67 @@
+// sim_internal.h — launcher interface between the C ABI (wfpt_capi.cpp) and the
+// RT sampler kernels (sim_kernels.hip). Not part of the public ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace wfpt {
+struct Params;
+
+// Weak like the RL launchers (rl_internal.h): the host-only sanitizer build
+// links wfpt_capi.cpp without this unit; sim_kernels_linked() is false there
+// and the sampler entry points fail with WFPT_ERR_UNSUPPORTED.
+#define WFPT_SIM_WEAK __attribute__((weak))
+
+// One tile of the batched inverse-CDF sampler (wfpt.pyx:323-354; DESIGN.md
+// §15): rows [row0, row0 + nrows) of the call's parameter table over the
+// shared grid x[0 .. G). The workspace W holds one row of m = G - 1 doubles per
+// tile row, row-major: first the densities at x[1 .. G), then (in place) their
+// running sums, then the normalised CDF.
+struct SimTile {
+  const double* grid;  // [G] rising RT grid
+  int64_t m;           // G - 1 points per row
+  const Params* rows;  // [R] the call's rows (t and st enter only the delays)
+  int64_t row0;        // global index of the tile's first row
+  int32_t nrows;       // rows of the tile
+  double* W;           // [sim_ws_rows(nrows) * m]
+  double* tot;         // [R] each row's unnormalised total (global row index)
+};
+
+// W[r][i] = full_pdf(x[i + 1], v, sv, a, z, sz, 0, 0, 1e-4) with full_pdf's
+// defaults n_st = n_sz = 2, adaptive, simps_err = 1e-3 (wfpt.pyx:335): one grid
+// point per lane, one row per block. Depth / budget flags are OR-ed into status.
+WFPT_SIM_WEAK void launch_sim_pdf(const SimTile& T, int* status, hipStream_t s);
+
+// W[r][i] <- W[r][0] + ... + W[r][i], added in index order from 0.0 as the
+// reference's loop does (wfpt.pyx:333-336), one lane per row; tot[row0 + r] =
+// the row's last sum. The scan moves whole blocks of 64 rows: W must hold
+// sim_ws_rows(nrows) rows (the rows past nrows are scratch).
+inline int64_t sim_ws_rows(int64_t nrows) { return (nrows + 63) / 64 * 64; }
+WFPT_SIM_WEAK void launch_sim_scan(const SimTile& T, hipStream_t s);
+
+// W[r][i] <- W[r][i] / tot[row0 + r] (wfpt.pyx:338).
+WFPT_SIM_WEAK void launch_sim_norm(const SimTile& T, hipStream_t s);
+
+// The draws of the tile's rows: draw j of global row r is element off[r] + j
+// of out / u_choice / u_delay / idx_out (off: [R + 1] prefix sums of the
+// counts). u_choice == null: both uniforms are Philox4x32-10 draws keyed by
+// seed at counter (j lo, j hi, r, stream) (stream 0 choice, 1 delay), so the
+// tiling cannot change them. u_delay may be null when no row has st != 0.
+// uc_out / ud_out / idx_out (nullable): the uniforms used and the grid index.
+struct SimDraw {
+  const int64_t* off;
+  const double* u_choice;
+  const double* u_delay;
+  uint64_t seed;
+  double* out;
+  int64_t* idx_out;
+  double* uc_out;
+  double* ud_out;
+};
+WFPT_SIM_WEAK void launch_sim_draw(const SimTile& T, const SimDraw& D, int64_t first,
+                                   int64_t ndraws, hipStream_t s);
+
+inline bool sim_kernels_linked() {
+  return launch_sim_pdf && launch_sim_scan && launch_sim_norm && launch_sim_draw;
+}
+}  // namespace wfpt

@@ -1,0 +1,255 @@
+// sim_kernels.hip — the batched inverse-CDF RT sampler on gfx950
+// (gen_rts_from_cdf, src/wfpt.pyx:323-354, for many parameter rows at once;
+// DESIGN.md §15).
+//
+//   sim_pdf_kernel    the grid densities, one grid point per lane, one row
+//                     per block
+//   sim_scan_kernel   the reference's sequential running sum, one lane per row,
+//                     tiles staged through LDS
+//   sim_norm_kernel   division by the row's total
+//   sim_draw_kernel   one draw per lane: uniforms (supplied or Philox),
+//                     searchsorted(side='left') by bisection, the
+//                     non-decision-time shift
+#include <hip/hip_runtime.h>
+
+#include "sim_internal.h"
+#include "wfpt_device.hpp"
+
+#pragma clang fp contract(off)
+
+namespace wfpt {
+namespace {
+
+constexpr int kSimBlock = 256;   // grid points (pdf / norm) or draws per block
+constexpr int kSimRows = 64;     // rows per scan block: one wave, one lane per row
+constexpr int kSimCols = 32;     // grid points of a row staged per scan step
+constexpr int kSimPitch = kSimCols + 1;  // LDS row pitch (doubles): the lanes' rows on distinct banks
+
+// full_pdf's defaults, which wfpt.pyx:335 takes: n_st = n_sz = 2, adaptive,
+// simps_err = 1e-3; err = 1e-4.
+__device__ inline Knobs sim_knobs() {
+  Knobs K;
+  K.err = 1e-4;
+  K.n_st = 2;
+  K.n_sz = 2;
+  K.use_adaptive = 1;
+  K.simps_err = 1e-3;
+  K.w_outlier = 0.0;
+  return K;
+}
+
+// blockIdx.x = tile row * blocks per row + the block's position in the row:
+// the row's parameters are uniform over the block.
+__global__ __launch_bounds__(kSimBlock) void sim_pdf_kernel(SimTile T, int bpr, int* status) {
+  const int64_t r = blockIdx.x / bpr;
+  const int64_t i = (int64_t)(blockIdx.x % bpr) * kSimBlock + threadIdx.x;
+  if (i >= T.m) return;
+  Params Q = T.rows[T.row0 + r];
+  Q.t = 0.0;  // wfpt.pyx:335: t = st = 0, the delays are added to the draws
+  Q.st = 0.0;
+  Q.p_outlier = 0.0;
+  const Knobs K = sim_knobs();
+  const double x = T.grid[i + 1];
+  long long ne = 0;
+  int flags = 0;
+  double p = full_pdf<kRuntime, RegStack<2>>(x, Q, K, ne, flags);
+  p = settle(p, x, Q, K, !trial_setup(x, Q).valid, ne, flags);
+  if (flags & kFlagErrors) atomicOr(status, flags & kFlagErrors);
+  T.W[r * T.m + i] = p;
+}
+
+// LDS hand-over inside the scan's one-wave block: orders the wave's LDS
+// accesses without a barrier instruction. __syncthreads() would also wait for
+// every outstanding global load and store, i.e. expose a memory round trip per
+// piece.
+__device__ inline void sim_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One wave per block, lane l owns tile row blockIdx.x * 64 + l. Per step the
+// wave stages a 64 x 32 piece of the row-major workspace in LDS (each load
+// instruction reads two rows' 256 consecutive bytes), every lane adds its own
+// row's 32 values in index order, and the piece goes back the same way. Two
+// LDS pieces alternate: the stores of the piece before and the loads of the
+// piece after are both issued ahead of the adds, which depend on neither, so
+// the wait at the top of the next step (the compiler waits for all of them)
+// overlaps the adds instead of exposing a store round trip per step.
+static_assert(kSimRows == 64, "sim_scan_kernel's block is one wave (sim_wave_sync)");
+__global__ __launch_bounds__(kSimRows) void sim_scan_kernel(SimTile T) {
+  __shared__ double tile[2][kSimRows * kSimPitch];
+  const int l = threadIdx.x;
+  const int half = l >> 5, col = l & (kSimCols - 1);
+  const int64_t r0 = (int64_t)blockIdx.x * kSimRows;
+  const int rows_here = (T.nrows - r0 < kSimRows) ? (int)(T.nrows - r0) : kSimRows;
+  // lane (half, col) moves element col of rows half, half + 2, ... of a piece.
+  // The workspace holds whole blocks of 64 rows (sim_ws_rows), so rows past
+  // the tile's last are read and written like the others (their sums are
+  // never used) and only a row's last, partial piece needs a bounds test:
+  // the whole pieces' loads and stores carry no predicate and no branch.
+  double* lane0 = T.W + (r0 + half) * T.m + col;
+  const int64_t step = 2 * T.m;
+  double nxt[kSimCols];
+  auto fetch = [&](int64_t c0) {
+    const double* p = lane0 + c0;
+    if (c0 + kSimCols <= T.m) {
+#pragma unroll
+      for (int k = 0; k < kSimCols; ++k) nxt[k] = p[k * step];
+    } else {
+#pragma unroll
+      for (int k = 0; k < kSimCols; ++k) nxt[k] = (c0 + col < T.m) ? p[k * step] : 0.0;
+    }
+  };
+  auto put_back = [&](const double* t, int64_t c0) {
+    double* p = lane0 + c0;
+    if (c0 + kSimCols <= T.m) {
+#pragma unroll
+      for (int k = 0; k < kSimCols; ++k) p[k * step] = t[(2 * k + half) * kSimPitch + col];
+    } else {
+#pragma unroll
+      for (int k = 0; k < kSimCols; ++k)
+        if (c0 + col < T.m) p[k * step] = t[(2 * k + half) * kSimPitch + col];
+    }
+  };
+  fetch(0);
+  double acc = 0.0;  // l_cdf[0] = 0 (wfpt.pyx:332)
+  int cur = 0;
+  for (int64_t c0 = 0; c0 < T.m; c0 += kSimCols, cur ^= 1) {
+    double* t = tile[cur];
+#pragma unroll
+    for (int k = 0; k < kSimCols; ++k) t[(2 * k + half) * kSimPitch + col] = nxt[k];
+    sim_wave_sync();
+    if (c0 > 0) put_back(tile[cur ^ 1], c0 - kSimCols);
+    if (c0 + kSimCols < T.m) fetch(c0 + kSimCols);
+    const int nc = (T.m - c0 < kSimCols) ? (int)(T.m - c0) : kSimCols;
+#pragma unroll
+    for (int k = 0; k < kSimCols; ++k) {
+      if (k < nc) {
+        acc = acc + t[l * kSimPitch + k];  // l_cdf[i] = l_cdf[i - 1] + pdf
+        t[l * kSimPitch + k] = acc;
+      }
+    }
+    sim_wave_sync();
+  }
+  put_back(tile[cur ^ 1], (T.m - 1) / kSimCols * kSimCols);
+  if (l < rows_here) T.tot[T.row0 + r0 + l] = acc;
+}
+
+__global__ __launch_bounds__(kSimBlock) void sim_norm_kernel(SimTile T, int bpr) {
+  const int64_t r = blockIdx.x / bpr;
+  const int64_t i = (int64_t)(blockIdx.x % bpr) * kSimBlock + threadIdx.x;
+  if (i >= T.m) return;
+  const double tot = T.tot[T.row0 + r];
+  T.W[r * T.m + i] = T.W[r * T.m + i] / tot;  // wfpt.pyx:338
+}
+
+// Philox4x32-10 (Salmon et al. 2011), counter c, key k.
+struct Philox {
+  uint32_t w[4];
+};
+__device__ inline Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                       uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox{{c0, c1, c2, c3}};
+}
+
+// A uniform in [0, 1) with 53 random bits from the first two output words.
+__device__ inline double philox_uniform(uint64_t seed, uint64_t draw, uint32_t row,
+                                        uint32_t stream) {
+  const Philox o = philox4x32_10((uint32_t)draw, (uint32_t)(draw >> 32), row, stream,
+                                 (uint32_t)seed, (uint32_t)(seed >> 32));
+  return ((double)(o.w[0] >> 5) * 67108864.0 + (double)(o.w[1] >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+// One draw per lane. The draw's row is found by bisection in the prefix sums
+// (rows without draws are skipped by it); then np.searchsorted(l_cdf, f) of
+// wfpt.pyx:347 over l_cdf = [0, W[r][0 .. m)]: the number of entries strictly
+// below f, by NumPy's own bisection, clamped to the grid.
+__global__ __launch_bounds__(kSimBlock) void sim_draw_kernel(SimTile T, SimDraw D, int64_t first,
+                                                             int64_t ndraws) {
+  const int64_t q = (int64_t)blockIdx.x * kSimBlock + threadIdx.x;
+  if (q >= ndraws) return;
+  const int64_t e = first + q;
+  int64_t lo = T.row0, hi = T.row0 + T.nrows;  // the last row with off[row] <= e
+  while (hi - lo > 1) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (D.off[mid] <= e) lo = mid;
+    else hi = mid;
+  }
+  const int64_t r = lo, j = e - D.off[r];
+  const Params Q = T.rows[r];
+  double f, u = 0.0;
+  if (D.u_choice) {
+    f = D.u_choice[e];
+    if (Q.st != 0 && D.u_delay) u = D.u_delay[e];
+  } else {
+    f = philox_uniform(D.seed, (uint64_t)j, (uint32_t)r, 0u);
+    if (Q.st != 0) u = philox_uniform(D.seed, (uint64_t)j, (uint32_t)r, 1u);
+  }
+  const double* cdf = T.W + (r - T.row0) * T.m;
+  int64_t a = 0, b = T.m + 1;
+  while (a < b) {
+    const int64_t mid = a + ((b - a) >> 1);
+    const double cv = mid == 0 ? 0.0 : cdf[mid - 1];
+    if (cv < f) a = mid + 1;
+    else b = mid;
+  }
+  const int64_t idx = a < T.m ? a : T.m;
+  const double rt = T.grid[idx];
+  const double sgn = rt > 0 ? 1.0 : (rt < 0 ? -1.0 : 0.0);  // np.sign
+  double res;
+  if (Q.st == 0) {
+    res = rt + sgn * Q.t;  // wfpt.pyx:350
+  } else {
+    const double delay = u * Q.st + (Q.t - Q.st / 2.);  // wfpt.pyx:345
+    res = rt + sgn * delay;                             // wfpt.pyx:352
+  }
+  D.out[e] = res;
+  if (D.idx_out) D.idx_out[e] = idx;
+  if (D.uc_out) D.uc_out[e] = f;
+  if (D.ud_out) D.ud_out[e] = u;
+}
+
+int sim_blocks_per_row(int64_t m) { return (int)((m + kSimBlock - 1) / kSimBlock); }
+
+}  // namespace
+
+void launch_sim_pdf(const SimTile& T, int* status, hipStream_t s) {
+  if (T.nrows <= 0 || T.m <= 0) return;
+  const int bpr = sim_blocks_per_row(T.m);
+  hipLaunchKernelGGL(sim_pdf_kernel, dim3((unsigned)((int64_t)bpr * T.nrows)), dim3(kSimBlock), 0,
+                     s, T, bpr, status);
+}
+
+void launch_sim_scan(const SimTile& T, hipStream_t s) {
+  if (T.nrows <= 0 || T.m <= 0) return;
+  hipLaunchKernelGGL(sim_scan_kernel, dim3((T.nrows + kSimRows - 1) / kSimRows), dim3(kSimRows), 0,
+                     s, T);
+}
+
+void launch_sim_norm(const SimTile& T, hipStream_t s) {
+  if (T.nrows <= 0 || T.m <= 0) return;
+  const int bpr = sim_blocks_per_row(T.m);
+  hipLaunchKernelGGL(sim_norm_kernel, dim3((unsigned)((int64_t)bpr * T.nrows)), dim3(kSimBlock), 0,
+                     s, T, bpr);
+}
+
+void launch_sim_draw(const SimTile& T, const SimDraw& D, int64_t first, int64_t ndraws,
+                     hipStream_t s) {
+  if (ndraws <= 0) return;
+  hipLaunchKernelGGL(sim_draw_kernel, dim3((unsigned)((ndraws + kSimBlock - 1) / kSimBlock)),
+                     dim3(kSimBlock), 0, s, T, D, first, ndraws);
+}
+
+}  // namespace wfpt

@@ -24,6 +24,7 @@
 
 #include "../../include/wfpt_amd.h"
 #include "rl_internal.h"
+#include "sim_internal.h"
 #include "wfpt_device.hpp"
 #include "wfpt_internal.h"
 
@@ -214,6 +215,18 @@ struct wfpt_ctx {
   DevBuf<wfpt::RlRow> rl_rows; // node batch: the nodes' Q-learning rows
   DevBuf<wfpt::Params> rl_par; // node batch: the nodes' DDM rows
   std::vector<wfpt_rl_ds*> rl_dsets;
+  // RT sampler (sim_kernels.hip): the call's grid, rows, draw offsets, row
+  // totals, tile workspace, uniforms, draws and (debugging calls) grid indices
+  DevBuf<double> sim_grid;
+  DevBuf<wfpt::Params> sim_rows;
+  DevBuf<int64_t> sim_off;
+  DevBuf<double> sim_tot;
+  DevBuf<double> sim_ws;
+  DevBuf<double> sim_u;
+  DevBuf<double> sim_out;
+  DevBuf<int64_t> sim_idx;
+  hipEvent_t sim_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  double sim_ms[4] = {0, 0, 0, 0};  // profiled time by stage: density, scan, normalise, draws
 };
 
 constexpr int64_t kSplitCap = 16384;  // heavy chunks a dataset records per call (both classes)
@@ -797,6 +810,16 @@ void wfpt_close(wfpt_ctx* c) {
   c->rl_npart.release();
   c->rl_rows.release();
   c->rl_par.release();
+  c->sim_grid.release();
+  c->sim_rows.release();
+  c->sim_off.release();
+  c->sim_tot.release();
+  c->sim_ws.release();
+  c->sim_u.release();
+  c->sim_out.release();
+  c->sim_idx.release();
+  for (hipEvent_t& ev : c->sim_ev)
+    if (ev) (void)hipEventDestroy(ev);
   if (c->comm) (void)ncclCommDestroy(c->comm);
   c->x.release();
   c->part.release();
@@ -2474,6 +2497,177 @@ int wfpt_wiener_like_rlddm_nodes(wfpt_ctx* c, const wfpt_rl_ds* d, const double*
                                  const wfpt_params* per_node, const wfpt_knobs* k,
                                  double* out_logp) {
   return wfpt_wiener_like_rlddm_nodes_ex(c, d, rl_rows, per_node, k, out_logp, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// RT sampler (sim_kernels.hip; wfpt.pyx:323-354 for R parameter rows)
+
+int wfpt_gen_rts_nodes_ex(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_params* rows,
+                          int64_t R, const int64_t* counts, const double* u_choice,
+                          const double* u_delay, uint64_t seed, int64_t workspace_bytes,
+                          double* out, double* out_pdf, double* out_cdf, int64_t* out_idx,
+                          double* out_u_choice, double* out_u_delay) {
+  if (!grid || !rows || !counts) return fail(WFPT_ERR_ARG, "null pointer (grid / rows / counts)");
+  if (G < 2) return fail(WFPT_ERR_ARG, "gen_rts_nodes: G < 2 (the grid needs two points)");
+  if (R < 1) return fail(WFPT_ERR_ARG, "gen_rts_nodes: R < 1");
+  if (R >= (int64_t)1 << 31) return fail(WFPT_ERR_ARG, "gen_rts_nodes: R must be < 2^31");
+  if (workspace_bytes < 0) return fail(WFPT_ERR_ARG, "gen_rts_nodes: negative workspace_bytes");
+  std::vector<int64_t> off((size_t)R + 1, 0);
+  bool any_st = false;
+  for (int64_t r = 0; r < R; ++r) {
+    if (counts[r] < 0)
+      return fail(WFPT_ERR_ARG, "gen_rts_nodes: negative count in row " + std::to_string(r));
+    off[r + 1] = off[r] + counts[r];
+    any_st = any_st || rows[r].st != 0;
+  }
+  const int64_t total = off[R];
+  if ((u_delay && !u_choice) || (u_choice && !u_delay && any_st))
+    return fail(WFPT_ERR_ARG,
+                "gen_rts_nodes: u_choice and u_delay go together when a row has st != 0");
+  if (!out && total > 0) return fail(WFPT_ERR_ARG, "null pointer (out)");
+  if (!c) return fail(WFPT_ERR_ARG, "null pointer (context)");
+  if (!wfpt::sim_kernels_linked())
+    return fail(WFPT_ERR_UNSUPPORTED, "this build does not contain the RT sampler kernels");
+  const int64_t m = G - 1;
+  const int64_t ws = workspace_bytes > 0 ? workspace_bytes : (int64_t)1 << 30;
+  // rows per tile: the workspace's, at most R, and few enough for one launch
+  // of 256-point blocks (a grid's x dimension is below 2^31)
+  int64_t rpt = std::max<int64_t>(1, ws / 8 / m);
+  rpt = std::min(rpt, R);
+  rpt = std::min(rpt, std::max<int64_t>(1, (((int64_t)1 << 31) - 1) / ((m + 255) / 256)));
+  rpt = std::min<int64_t>(rpt, (int64_t)1 << 30);
+  WFPT_RANGE("wfpt_gen_rts_nodes");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  std::vector<wfpt::Params> par((size_t)R);
+  for (int64_t r = 0; r < R; ++r) par[r] = to_params(&rows[r]);
+  const bool want_u = out_u_choice || out_u_delay;
+  HIP_TRY(c->sim_grid.reserve(G));
+  HIP_TRY(c->sim_rows.reserve(R));
+  HIP_TRY(c->sim_off.reserve(R + 1));
+  HIP_TRY(c->sim_tot.reserve(R));
+  HIP_TRY(c->sim_ws.reserve((size_t)wfpt::sim_ws_rows(rpt) * m));
+  HIP_TRY(c->sim_out.reserve(std::max<int64_t>(total, 1)));
+  // [0, total) the choice uniforms, [total, 2 total) the delay uniforms:
+  // supplied ones going in, generated ones coming out of a debugging call
+  if (u_choice || want_u) HIP_TRY(c->sim_u.reserve(std::max<int64_t>(2 * total, 1)));
+  if (out_idx) HIP_TRY(c->sim_idx.reserve(std::max<int64_t>(total, 1)));
+  HIP_TRY(hipMemcpyAsync(c->sim_grid.p, grid, G * sizeof(double), hipMemcpyHostToDevice,
+                         c->stream));
+  HIP_TRY(hipMemcpyAsync(c->sim_rows.p, par.data(), R * sizeof(wfpt::Params),
+                         hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->sim_off.p, off.data(), (R + 1) * sizeof(int64_t),
+                         hipMemcpyHostToDevice, c->stream));
+  if (u_choice && total > 0) {
+    HIP_TRY(hipMemcpyAsync(c->sim_u.p, u_choice, total * sizeof(double), hipMemcpyHostToDevice,
+                           c->stream));
+    if (u_delay)
+      HIP_TRY(hipMemcpyAsync(c->sim_u.p + total, u_delay, total * sizeof(double),
+                             hipMemcpyHostToDevice, c->stream));
+  }
+  if (c->profile)
+    for (hipEvent_t& ev : c->sim_ev)
+      if (!ev) HIP_TRY(hipEventCreate(&ev));
+  if (int rc = begin_status(c)) return rc;
+  wfpt::SimDraw D;
+  D.off = c->sim_off.p;
+  D.u_choice = u_choice ? c->sim_u.p : nullptr;
+  D.u_delay = (u_choice && u_delay) ? c->sim_u.p + total : nullptr;
+  D.seed = seed;
+  D.out = c->sim_out.p;
+  D.idx_out = out_idx ? c->sim_idx.p : nullptr;
+  // the uniforms of a supplied-uniform call are the caller's own: returned
+  // from the host arrays below
+  D.uc_out = (want_u && !u_choice) ? c->sim_u.p : nullptr;
+  D.ud_out = (want_u && !u_choice) ? c->sim_u.p + total : nullptr;
+  for (int64_t r0 = 0; r0 < R; r0 += rpt) {
+    wfpt::SimTile T;
+    T.grid = c->sim_grid.p;
+    T.m = m;
+    T.rows = c->sim_rows.p;
+    T.row0 = r0;
+    T.nrows = (int32_t)std::min(rpt, R - r0);
+    T.W = c->sim_ws.p;
+    T.tot = c->sim_tot.p;
+    const size_t tile_bytes = (size_t)T.nrows * m * sizeof(double);
+    if (c->profile) HIP_TRY(hipEventRecord(c->sim_ev[0], c->stream));
+    wfpt::launch_sim_pdf(T, c->status, c->stream);
+    HIP_TRY(hipGetLastError());
+    if (out_pdf)
+      HIP_TRY(hipMemcpyAsync(out_pdf + r0 * m, T.W, tile_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (c->profile) HIP_TRY(hipEventRecord(c->sim_ev[1], c->stream));
+    wfpt::launch_sim_scan(T, c->stream);
+    HIP_TRY(hipGetLastError());
+    if (c->profile) HIP_TRY(hipEventRecord(c->sim_ev[2], c->stream));
+    wfpt::launch_sim_norm(T, c->stream);
+    HIP_TRY(hipGetLastError());
+    if (out_cdf)
+      HIP_TRY(hipMemcpyAsync(out_cdf + r0 * m, T.W, tile_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (c->profile) HIP_TRY(hipEventRecord(c->sim_ev[3], c->stream));
+    wfpt::launch_sim_draw(T, D, off[r0], off[r0 + T.nrows] - off[r0], c->stream);
+    HIP_TRY(hipGetLastError());
+    if (c->profile) {
+      HIP_TRY(hipEventRecord(c->sim_ev[4], c->stream));
+      HIP_TRY(hipEventSynchronize(c->sim_ev[4]));
+      for (int k = 0; k < 4; ++k) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->sim_ev[k], c->sim_ev[k + 1]));
+        c->sim_ms[k] += ms;
+        c->k_ms += ms;
+      }
+      c->launches += 4;
+    }
+  }
+  std::vector<double> tot((size_t)R);
+  HIP_TRY(hipMemcpyAsync(tot.data(), c->sim_tot.p, R * sizeof(double), hipMemcpyDeviceToHost,
+                         c->stream));
+  if (int rc = fetch_status(c)) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // a tile workspace grown past 256 MiB is not kept between calls
+  if (c->sim_ws.cap * sizeof(double) > ((size_t)256 << 20)) c->sim_ws.release();
+  if (int rc = check_status(c)) return rc;
+  // wfpt.pyx:338 divides by the row's total: a total that is not finite and
+  // positive (invalid parameters: all-zero densities; a == 0: NaN) has no CDF
+  for (int64_t r = 0; r < R; ++r)
+    if (!(tot[r] > 0) || !std::isfinite(tot[r]))
+      return fail(WFPT_ERR_UNSUPPORTED, "gen_rts_nodes: row " + std::to_string(r) +
+                                    " has no CDF (the sum of its grid densities is " +
+                                    std::to_string(tot[r]) + "); no draws are returned");
+  if (total > 0) {
+    HIP_TRY(hipMemcpy(out, c->sim_out.p, total * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_idx)
+      HIP_TRY(hipMemcpy(out_idx, c->sim_idx.p, total * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (out_u_choice) {
+      if (u_choice) std::memcpy(out_u_choice, u_choice, total * sizeof(double));
+      else HIP_TRY(hipMemcpy(out_u_choice, c->sim_u.p, total * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (out_u_delay) {
+      if (u_choice && u_delay) std::memcpy(out_u_delay, u_delay, total * sizeof(double));
+      else if (u_choice) std::memset(out_u_delay, 0, total * sizeof(double));
+      else
+        HIP_TRY(hipMemcpy(out_u_delay, c->sim_u.p + total, total * sizeof(double),
+                          hipMemcpyDeviceToHost));
+    }
+  }
+  return WFPT_OK;
+}
+
+int wfpt_gen_rts_nodes(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_params* rows,
+                       int64_t R, const int64_t* counts, const double* u_choice,
+                       const double* u_delay, uint64_t seed, int64_t workspace_bytes,
+                       double* out) {
+  return wfpt_gen_rts_nodes_ex(c, grid, G, rows, R, counts, u_choice, u_delay, seed,
+                               workspace_bytes, out, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int wfpt_profile_stages(wfpt_ctx* c, double stage_ms[4], int reset) {
+  if (!c || !stage_ms) return fail(WFPT_ERR_ARG, "null pointer");
+  std::lock_guard<std::mutex> lk(c->mu);
+  for (int k = 0; k < 4; ++k) {
+    stage_ms[k] = c->sim_ms[k];
+    if (reset) c->sim_ms[k] = 0.0;
+  }
+  return WFPT_OK;
 }
 
 }  // extern "C"

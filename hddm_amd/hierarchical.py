@@ -245,6 +245,7 @@ class HDDM:
             self.n_units[fam] = self.n_subj * n_lv
         self.dataset = _wfpt.Dataset(rt, node_id=node_codes, n_nodes=self.n_nodes, device=device)
         self.n_trials = rt.size
+        self.node_counts = np.bincount(node_codes, minlength=self.n_nodes).astype(np.int64)
         self.likelihood_calls = 0
         self.likelihood_seconds = 0.0
         self.call_stats = {}  # updated parameter -> [calls, seconds]
@@ -479,6 +480,56 @@ class HDDM:
                       "2.5q": float(np.quantile(v, .025)), "97.5q": float(np.quantile(v, .975))}
         return out
 
+    def post_pred_rows(self, samples=500):
+        """The kept sweeps a posterior predictive draws from and their node
+        parameters: (picked, table) with `picked` the indices of `samples`
+        evenly spaced kept sweeps (all of them when fewer were kept) and table
+        (len(picked), n_nodes, 8) in node_table's column order."""
+        if not hasattr(self, "trace") or not isinstance(getattr(self, "trace_subj", None), dict) \
+                or not isinstance(self.trace_subj.get("a"), np.ndarray):
+            raise RuntimeError("post_pred_gen needs the traces: run sample() first")
+        kept = self.trace_subj["a"].shape[0]
+        if kept < 1:
+            raise RuntimeError("post_pred_gen: sample() kept no sweep")
+        samples = int(samples)
+        if samples < 1:
+            raise ValueError("samples must be >= 1")
+        picked = np.unique(np.linspace(0, kept - 1, min(samples, kept)).round().astype(np.int64))
+        P = np.empty((picked.size, self.n_nodes, 8))
+        P[:, :, 0] = self.trace_subj["v"][picked][:, self.node_unit["v"]]
+        P[:, :, 2] = self.trace_subj["a"][picked][:, self.node_unit["a"]]
+        P[:, :, 3] = 0.5
+        P[:, :, 5] = self.trace_subj["t"][picked][:, self.node_unit["t"]]
+        for name in ("sv", "sz", "st"):
+            P[:, :, self._COL[name]] = (self.trace[name][picked][:, None] if name in self.include
+                                        else self.inter[name])
+        P[:, :, 7] = self.p_outlier
+        return picked, P
+
+    def post_pred_gen(self, samples=500, seed=None, cdf_range=(-5, 5), dt=1e-4):
+        """Posterior predictive data (kabuki.analyze.post_pred_gen over the
+        stochastic's random(), hddm/utils.py:384-387): for each of `samples`
+        evenly spaced kept sweeps and each observed node, as many RTs as the
+        node has trials, drawn at the sweep's parameters by ONE batched
+        sampler call (wfpt.gen_rts_from_cdf_nodes with a device seed). The
+        draws come from the DDM alone: p_outlier's mixture is not simulated.
+
+        Returns a DataFrame with columns sample (index of the kept sweep), node
+        (index into node_keys), rt (signed) and response (1 upper / 0 lower)."""
+        import pandas as pd
+        picked, P = self.post_pred_rows(samples)
+        counts = self.node_counts
+        S = picked.size
+        if seed is None:
+            seed = int(self.rng.integers(0, 2 ** 63))
+        rts, off = _wfpt.gen_rts_from_cdf_nodes(P.reshape(S * self.n_nodes, 8), np.tile(counts, S),
+                                                cdf_lb=cdf_range[0], cdf_ub=cdf_range[1], dt=dt,
+                                                seed=seed)
+        per = np.diff(off)
+        return pd.DataFrame({"sample": np.repeat(np.repeat(picked, self.n_nodes), per),
+                             "node": np.repeat(np.tile(np.arange(self.n_nodes), S), per),
+                             "rt": rts, "response": (rts > 0).astype(np.int64)})
+
 
 class HDDMChains(HDDM):
     """`chains` independent chains of HDDM(...) sampled in lockstep on one GPU.
@@ -587,6 +638,12 @@ class HDDMChains(HDDM):
 
     def node_table(self, over=None):
         raise NotImplementedError("HDDMChains: node_tables() holds one table per chain")
+
+    def post_pred_rows(self, samples=500):
+        raise NotImplementedError("HDDMChains: posterior predictive draws take one chain (HDDM)")
+
+    def post_pred_gen(self, samples=500, seed=None, cdf_range=(-5, 5), dt=1e-4):
+        raise NotImplementedError("HDDMChains: posterior predictive draws take one chain (HDDM)")
 
     def _unit_group_c(self, fam):
         """(C, units) group mean of each unit's level, per chain."""

@@ -19,7 +19,9 @@ CPU path. Argument checking mirrors Cython's buffer protocol: `x` must be a
 Additions for resident data (the reference re-reads host memory every call):
 `Dataset(rt)` uploads RTs once; `Dataset.wiener_like(...)` has wiener_like's
 signature minus `x`. `Dataset(rt, node_id=...)` + `wiener_like_nodes` scores
-many PyMC nodes in one launch.
+many PyMC nodes in one launch. `gen_rts_from_cdf_nodes` draws RTs for many
+parameter rows in one call, grid, CDF and search on the device (posterior
+predictive data sets: HDDM.post_pred_gen).
 """
 import ctypes
 
@@ -28,8 +30,8 @@ import numpy as np
 from . import _lib
 
 __all__ = ["pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "gen_rts_from_cdf",
-           "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl", "wiener_like_multi_rlddm",
-           "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_terms",
+           "gen_rts_from_cdf_nodes", "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl",
+           "wiener_like_multi_rlddm", "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_terms",
            "wiener_like_rl_terms", "wiener_like_multi_rlddm_terms"]
 
 
@@ -166,6 +168,102 @@ def gen_rts_from_cdf(v, sv, a, z, sz, t, st, samples=1000, cdf_lb=-6, cdf_ub=6, 
     if st == 0:
         return rt + np.sign(rt) * t
     return rt + np.sign(rt) * delay
+
+
+def gen_rts_from_cdf_nodes(params, samples, cdf_lb=-6, cdf_ub=6, dt=1e-2, u=None, u_delay=None,
+                           seed=None, max_workspace=None, return_debug=False):
+    """gen_rts_from_cdf (wfpt.pyx:323-354) for R parameter rows in one call:
+    grid densities, running sums, normalisation, search and delays all run on
+    the GPU (wfpt_gen_rts_nodes); only the draws come back.
+
+    params: (R, 7) or (R, 8) rows of v, sv, a, z, sz, t, st[, p_outlier]
+    (node_table's column order; p_outlier is ignored). samples: draws per row,
+    an int or R ints. Returns (rts, offsets): row r's draws are
+    rts[offsets[r]:offsets[r + 1]].
+
+    Uniforms, in this order of precedence: `u` (and `u_delay` when a row has
+    st != 0), sum(samples) values in [0, 1) each, row after row; `seed`, the
+    device's Philox4x32-10 streams (the draws depend on the seed, the row index
+    and the draw index only); else NumPy's global RNG in the reference's order,
+    rand(n_r) and, when the row's st != 0, rand(n_r), row after row: under one
+    np.random.seed the call reproduces a loop of gen_rts_from_cdf calls.
+
+    max_workspace: device bytes for the rows' grids (default 1 GiB); more rows
+    than fit are processed in tiles, with the same result. return_debug: also
+    a dict of the grid `x`, the densities `pdf` and normalised CDF `cdf`
+    (R, len(x) - 1), each draw's grid index `idx` and the uniforms `u`,
+    `u_delay` used.
+    """
+    pm = np.asarray(params, dtype=np.float64)
+    if pm.ndim != 2 or pm.shape[1] not in (7, 8) or pm.shape[0] < 1:
+        raise ValueError("params must have shape (R, 7) or (R, 8), R >= 1")
+    R = pm.shape[0]
+    table = np.zeros((R, 8))
+    table[:, :pm.shape[1]] = pm
+    cnt = np.asarray(samples)
+    if cnt.ndim == 0:
+        cnt = np.full(R, int(cnt))
+    if cnt.shape != (R,) or not np.issubdtype(cnt.dtype, np.integer):
+        raise ValueError(f"samples must be an int or {R} ints")
+    cnt = np.ascontiguousarray(cnt, dtype=np.int64)
+    if np.any(cnt < 0):
+        raise ValueError("samples must be non-negative")
+    offsets = np.zeros(R + 1, dtype=np.int64)
+    np.cumsum(cnt, out=offsets[1:])
+    total = int(offsets[R])
+    has_st = table[:, 6] != 0
+    if u is None and u_delay is not None:
+        raise ValueError("u_delay needs u")
+    if u is not None:
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.shape != (total,):
+            raise ValueError(f"u must hold sum(samples) = {total} uniforms")
+        if has_st.any():
+            if u_delay is None:
+                raise ValueError("u_delay is needed: a row has st != 0")
+        if u_delay is not None:
+            u_delay = np.ascontiguousarray(u_delay, dtype=np.float64)
+            if u_delay.shape != (total,):
+                raise ValueError(f"u_delay must hold sum(samples) = {total} uniforms")
+        for nm, arr in (("u", u), ("u_delay", u_delay)):
+            if arr is not None and arr.size and not (arr.min() >= 0 and arr.max() < 1):
+                raise ValueError(f"{nm} must lie in [0, 1)")
+    elif seed is None:
+        # the reference's order of draws from the global RNG (wfpt.pyx:340-345)
+        u = np.empty(total)
+        u_delay = np.zeros(total) if has_st.any() else None
+        for r in range(R):
+            lo, hi = offsets[r], offsets[r + 1]
+            u[lo:hi] = np.random.rand(int(cnt[r]))
+            if has_st[r]:
+                u_delay[lo:hi] = np.random.rand(int(cnt[r]))
+    x = np.arange(cdf_lb, cdf_ub, dt)
+    G = x.shape[0]
+    if G < 2:
+        raise ValueError("the grid np.arange(cdf_lb, cdf_ub, dt) needs at least two points")
+    ws = 0 if max_workspace is None else int(max_workspace)
+    if ws < 0:
+        raise ValueError("max_workspace must be positive")
+    c = _lib.context()
+    out = np.empty(total, dtype=np.float64)
+    seed = 0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+    pu = _lib.dptr(u) if u is not None else None
+    pd_ = _lib.dptr(u_delay) if u_delay is not None else None
+    if return_debug:
+        dbg = {"x": x, "pdf": np.empty((R, G - 1)), "cdf": np.empty((R, G - 1)),
+               "idx": np.empty(total, dtype=np.int64), "u": np.empty(total),
+               "u_delay": np.empty(total)}
+        rc = _lib.wfpt_gen_rts_nodes_ex(
+            c.handle, _lib.dptr(x), G, table.ctypes.data_as(_lib._PP), R, _i64ptr(cnt), pu, pd_,
+            seed, ws, _lib.dptr(out), _lib.dptr(dbg["pdf"]), _lib.dptr(dbg["cdf"]),
+            _i64ptr(dbg["idx"]), _lib.dptr(dbg["u"]), _lib.dptr(dbg["u_delay"]))
+    else:
+        rc = _lib.wfpt_gen_rts_nodes(c.handle, _lib.dptr(x), G, table.ctypes.data_as(_lib._PP), R,
+                                     _i64ptr(cnt), pu, pd_, seed, ws, _lib.dptr(out))
+    if rc == 4 and b"has no CDF" in _lib.wfpt_last_error():
+        raise RuntimeError("wfpt_amd: " + _lib.wfpt_last_error().decode(errors="replace"))
+    _lib.check(rc)
+    return (out, offsets, dbg) if return_debug else (out, offsets)
 
 
 class Dataset:

@@ -19,6 +19,8 @@
  *   wfpt_wiener_like_multi <- wfpt.wiener_like_multi   src/wfpt.pyx:244-274
  *   wfpt_dmat_cdf_array    <- cdfdif_wrapper.dmat_cdf_array
  *                             src/cdfdif_wrapper.pyx:16-53, src/cdfdif.c:59-221
+ *   wfpt_gen_rts_nodes     <- wfpt.gen_rts_from_cdf, one call for many rows
+ *                             src/wfpt.pyx:323-354
  * The Python binding that keeps the reference signatures is
  * hddm_amd/wfpt.py (ctypes); INTEGRATION.md shows the drop-in.
  */
@@ -350,7 +352,51 @@ int wfpt_result_poison(double r[3]);
  * stay apart under the sum. */
 int wfpt_decode_result(const double r[3], double *out_logp);
 
+/* ---- RT sampler --------------------------------------------------------- */
+/* gen_rts_from_cdf (src/wfpt.pyx:323-354) for R parameter rows in one call:
+ * per row the density full_pdf(x, v, sv, a, z, sz, 0, 0, 1e-4) at grid[1 .. G),
+ * its running sum in the reference's order, the division by the last sum,
+ * np.searchsorted(side='left') of each choice uniform, and the
+ * non-decision-time shift rt + sign(rt) t (st == 0) or rt + sign(rt) (u st +
+ * (t - st / 2)). Grid, CDF and search stay on the device; only the draws come
+ * back.
+ *   grid      G >= 2 rising doubles (the caller's: np.arange's own values)
+ *   rows      R >= 1 parameter rows (p_outlier ignored)
+ *   counts    R draws per row, >= 0
+ *   u_choice, u_delay   sum(counts) uniforms in [0, 1) each, row after row, or
+ *             both NULL: then each uniform is a Philox4x32-10 draw with the
+ *             key {seed lo, seed hi} at counter {draw lo, draw hi, row, stream}
+ *             (stream 0 choice, 1 delay; draw = the index inside the row), u =
+ *             ((w0 >> 5) 2^26 + (w1 >> 6)) 2^-53. u_delay may be NULL when
+ *             every row has st == 0.
+ *   workspace_bytes   device bytes for the rows' grids (0: 1 GiB); the rows
+ *             are processed in tiles of max(1, workspace_bytes / (8 (G - 1)))
+ *             rows, and the result does not depend on the tiling (the
+ *             allocation is rounded up to whole blocks of 64 rows)
+ *   out       sum(counts) signed RTs, row after row
+ * A row whose densities do not sum to a finite positive value (invalid
+ * parameters: all zero; a == 0: NaN) fails the call with WFPT_ERR_UNSUPPORTED
+ * and a message naming the first such row; nothing is written to out. */
+int wfpt_gen_rts_nodes(wfpt_ctx *ctx, const double *grid, int64_t G, const wfpt_params *rows,
+                       int64_t R, const int64_t *counts, const double *u_choice,
+                       const double *u_delay, uint64_t seed, int64_t workspace_bytes,
+                       double *out);
+/* As wfpt_gen_rts_nodes (wfpt.pyx:323-354), with the intermediate arrays of a
+ * debugging call (each nullable): out_pdf / out_cdf [R x (G - 1)] the grid
+ * densities and the normalised CDF, out_idx [sum(counts)] each draw's grid
+ * index, out_u_choice / out_u_delay [sum(counts)] the uniforms used (the delay
+ * uniform of a row with st == 0 is 0). */
+int wfpt_gen_rts_nodes_ex(wfpt_ctx *ctx, const double *grid, int64_t G, const wfpt_params *rows,
+                          int64_t R, const int64_t *counts, const double *u_choice,
+                          const double *u_delay, uint64_t seed, int64_t workspace_bytes,
+                          double *out, double *out_pdf, double *out_cdf, int64_t *out_idx,
+                          double *out_u_choice, double *out_u_delay);
+
 /* ---- measurement -------------------------------------------------------- */
+/* Under WFPT_PROF_EVENTS: device milliseconds of the RT sampler's stages
+ * {density, running sum, normalisation, draws} since the last reset (they are
+ * also part of wfpt_profile_read's total, four launches per tile). */
+int wfpt_profile_stages(wfpt_ctx *ctx, double stage_ms[4], int reset);
 /* flags & WFPT_PROF_EVENTS: bracket the main likelihood kernel of each call
  * with HIP events on the context's stream (per-launch device time);
  * flags & WFPT_PROF_EVALS: count pdf_sv evaluations (a separate kernel build

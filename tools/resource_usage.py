@@ -1,7 +1,7 @@
 """Register / scratch / LDS / occupancy of the gfx950 kernels, from the
 compiler's own resource-usage remarks (the numbers the code object carries).
 
-    python tools/resource_usage.py [name-filter ...] [-D NAME=VAL ...]
+    python tools/resource_usage.py [name-filter ...] [-D NAME=VAL ...] [--src sim_kernels.hip]
 """
 import os
 import re
@@ -21,10 +21,10 @@ def demangle(names):
     return out if len(out) == len(names) else names
 
 
-def usage(defines=()):
+def usage(defines=(), src=SRC):
     with tempfile.TemporaryDirectory() as td:
         cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-               "-fPIC", "--offload-arch=gfx950", *[f"-D{d}" for d in defines], "-c", SRC, "-o",
+               "-fPIC", "--offload-arch=gfx950", *[f"-D{d}" for d in defines], "-c", src, "-o",
                os.path.join(td, "k.o"), "-Rpass-analysis=kernel-resource-usage"]
         txt = subprocess.run(cmd, capture_output=True, text=True, cwd=td).stderr
     rows, cur = [], None
@@ -46,14 +46,16 @@ def usage(defines=()):
 
 def main():
     args = sys.argv[1:]
-    defines, filt = [], []
+    defines, filt, src = [], [], SRC
     while args:
         a = args.pop(0)
         if a == "-D":
             defines.append(args.pop(0))
+        elif a == "--src":  # another unit of hddm_amd/csrc
+            src = os.path.join(os.path.dirname(SRC), args.pop(0))
         else:
             filt.append(a)
-    for r in usage(defines):
+    for r in usage(defines, src):
         if filt and not any(f in r["name"] for f in filt):
             continue
         print(f"{r['name'][:70]:70s} " + " ".join(f"{k.split()[0]}={r.get(k, '-')}" for k in FIELDS))
