@@ -163,6 +163,26 @@ wfpt_wiener_like_rlddm_nodes = _sig("wfpt_wiener_like_rlddm_nodes", _I,
                                     [_VP, _VP, _PD, _PP, _PK, _PD])
 wfpt_wiener_like_rlddm_nodes_ex = _sig("wfpt_wiener_like_rlddm_nodes_ex", _I,
                                        [_VP, _VP, _PD, _PP, _PK, _PD, _PD, _PD])
+# regression likelihoods (include/wfpt_amd.h)
+LINK_IDENTITY, LINK_EXP, LINK_INVLOGIT = 0, 1, 2
+
+
+class RegTerm(ctypes.Structure):
+    _fields_ = [(n, _I32) for n in ("param", "link", "col0", "ncol")]
+
+
+_PT = ctypes.POINTER(RegTerm)
+wfpt_reg_dataset_create = _sig("wfpt_reg_dataset_create", _I,
+                               [_VP, _PD, _I64, _PD, _I32, ctypes.POINTER(_I32), _I32,
+                                ctypes.POINTER(_VP)])
+wfpt_reg_dataset_destroy = _sig("wfpt_reg_dataset_destroy", None, [_VP])
+wfpt_wiener_like_reg = _sig("wfpt_wiener_like_reg", _I, [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD])
+wfpt_wiener_like_reg_ex = _sig("wfpt_wiener_like_reg_ex", _I,
+                               [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD, _PD, _PD])
+wfpt_wiener_like_reg_groups = _sig("wfpt_wiener_like_reg_groups", _I,
+                                   [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD])
+wfpt_wiener_like_reg_groups_ex = _sig("wfpt_wiener_like_reg_groups_ex", _I,
+                                      [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD, _PD, _PD])
 # RT sampler (include/wfpt_amd.h)
 _U64 = ctypes.c_uint64
 wfpt_gen_rts_nodes = _sig("wfpt_gen_rts_nodes", _I,
@@ -190,6 +210,8 @@ EXPORTED = [
     "wfpt_wiener_like_multi_rlddm", "wfpt_wiener_like_multi_rlddm_ex",
     "wfpt_wiener_like_rlddm_nodes", "wfpt_wiener_like_rlddm_nodes_ex",
     "wfpt_gen_rts_nodes", "wfpt_gen_rts_nodes_ex", "wfpt_profile_stages",
+    "wfpt_reg_dataset_create", "wfpt_reg_dataset_destroy", "wfpt_wiener_like_reg",
+    "wfpt_wiener_like_reg_ex", "wfpt_wiener_like_reg_groups", "wfpt_wiener_like_reg_groups_ex",
 ]
 
 # error encoding of a result triple (include/wfpt_amd.h: wfpt_decode_result)

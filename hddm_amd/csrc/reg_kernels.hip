@@ -1,0 +1,81 @@
+// reg_kernels.hip — the regression front end on gfx950 (HDDMRegressor's
+// wiener_multi_like, hddm/models/hddm_regression.py:26-36: trial-wise
+// parameters link(design matrix . coefficients) into wfpt.wiener_like_multi).
+//
+//   reg_fill_kernel   one trial per lane: every regression term's linear
+//                     predictor and link, and the group rows of the
+//                     non-regressed parameters, into per-trial arrays
+//
+// The densities are not computed here: the arrays go into the per-trial-
+// parameter pass (wfpt_kernels.hip: multi_fast_kernel / multi_kernel through
+// launch_multi_fast / launch_multi), the per-group sums come from
+// rl_kernels.hip's launch_rl_node_sum.
+#include <hip/hip_runtime.h>
+
+#include "reg_internal.h"
+#include "wfpt_crlibm.hpp"
+#include "wfpt_device.hpp"
+
+#pragma clang fp contract(off)
+
+namespace wfpt {
+namespace {
+
+constexpr int kRegBlock = 256;
+
+// The order of the predictor is part of the contract (reg_internal.h): one
+// product, one sum per column, left to right. The empty asm keeps each product
+// out of a fused multiply-add whatever the contraction setting, as
+// rl_scan_kernel guards its update. A column is contiguous over trials, so a
+// wave reads 512 consecutive bytes per column; the coefficient row is the
+// same address for every lane of a group.
+__global__ __launch_bounds__(kRegBlock) void reg_fill_kernel(RegFill F) {
+  const int64_t i = (int64_t)blockIdx.x * kRegBlock + threadIdx.x;
+  if (i >= F.n) return;
+  const int32_t g = F.group ? F.group[i] : 0;
+  const double* b = F.coef + (int64_t)g * F.C;
+  const int64_t ci = F.pred_in ? (F.caller ? F.caller[i] : i) : 0;
+#pragma unroll 1
+  for (int k = 0; k < F.n_terms; ++k) {
+    const RegTerm T = F.term[k];
+    const double* col = F.X + (int64_t)T.col0 * F.n + i;
+    double eta = col[0] * b[T.col0];
+    asm volatile("" : "+v"(eta));
+    for (int c = 1; c < T.ncol; ++c) {
+      double prod = col[(int64_t)c * F.n] * b[T.col0 + c];
+      asm volatile("" : "+v"(prod));
+      eta = eta + prod;
+    }
+    double y = eta;
+    if (T.link == kRegExp) {
+      y = wfpt_cr::cr_exp(eta);
+    } else if (T.link == kRegInvLogit) {
+      const double e = wfpt_cr::cr_exp(-eta);
+      const double den = 1.0 + e;
+      y = 1.0 / den;
+    }
+    F.arr[(int64_t)k * F.n + i] = y;
+    if (F.pred_in) F.pred_in[(int64_t)k * F.n + ci] = y;
+  }
+  if (F.expand) {
+    const double* row = reinterpret_cast<const double*>(F.P + g);
+    int slot = F.n_terms;
+#pragma unroll
+    for (int f = 0; f < 7; ++f) {
+      if (F.expand & (1 << f)) {
+        F.arr[(int64_t)slot * F.n + i] = row[f];
+        ++slot;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+void launch_reg_fill(const RegFill& F, hipStream_t s) {
+  const int64_t nb = (F.n + kRegBlock - 1) / kRegBlock;
+  if (nb == 0 || (F.n_terms == 0 && F.expand == 0)) return;
+  hipLaunchKernelGGL(reg_fill_kernel, dim3(nb), dim3(kRegBlock), 0, s, F);
+}
+
+}  // namespace wfpt

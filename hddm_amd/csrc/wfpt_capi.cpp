@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/wfpt_amd.h"
+#include "reg_internal.h"
 #include "rl_internal.h"
 #include "sim_internal.h"
 #include "wfpt_device.hpp"
@@ -121,6 +122,7 @@ struct MappedBuf {
 };
 
 struct wfpt_rl_ds;
+struct wfpt_reg_ds;
 
 struct wfpt_ctx {
   int device = 0;
@@ -215,6 +217,14 @@ struct wfpt_ctx {
   DevBuf<wfpt::RlRow> rl_rows; // node batch: the nodes' Q-learning rows
   DevBuf<wfpt::Params> rl_par; // node batch: the nodes' DDM rows
   std::vector<wfpt_rl_ds*> rl_dsets;
+  // regression front end (reg_kernels.hip): per-call workspaces and the live
+  // regression datasets
+  DevBuf<double> reg_arr;      // per-trial parameter arrays (reg_fill_kernel), stored order
+  DevBuf<double> reg_pred;     // the predicted parameters in the caller's order (_ex calls)
+  DevBuf<double> reg_coef;     // the call's coefficient rows
+  DevBuf<wfpt::Params> reg_par;  // groups call: the groups' DDM rows
+  DevBuf<double> reg_npart;    // groups call: block partials of the per-group sums
+  std::vector<wfpt_reg_ds*> reg_dsets;
   // RT sampler (sim_kernels.hip): the call's grid, rows, draw offsets, row
   // totals, tile workspace, uniforms, draws and (debugging calls) grid indices
   DevBuf<double> sim_grid;
@@ -293,6 +303,7 @@ struct DeviceGuard {
 
 void ds_free_device(wfpt_ds* d);  // defined with wfpt_dataset_destroy
 void rl_detach(wfpt_rl_ds* d);    // defined with wfpt_rl_dataset_destroy
+void reg_detach(wfpt_reg_ds* d);  // defined with wfpt_reg_dataset_destroy
 
 wfpt::Params to_params(const wfpt_params* p) {
   wfpt::Params q;
@@ -810,6 +821,13 @@ void wfpt_close(wfpt_ctx* c) {
   c->rl_npart.release();
   c->rl_rows.release();
   c->rl_par.release();
+  for (wfpt_reg_ds* d : c->reg_dsets) reg_detach(d);
+  c->reg_dsets.clear();
+  c->reg_arr.release();
+  c->reg_pred.release();
+  c->reg_coef.release();
+  c->reg_par.release();
+  c->reg_npart.release();
   c->sim_grid.release();
   c->sim_rows.release();
   c->sim_off.release();
@@ -2497,6 +2515,328 @@ int wfpt_wiener_like_rlddm_nodes(wfpt_ctx* c, const wfpt_rl_ds* d, const double*
                                  const wfpt_params* per_node, const wfpt_knobs* k,
                                  double* out_logp) {
   return wfpt_wiener_like_rlddm_nodes_ex(c, d, rl_rows, per_node, k, out_logp, nullptr, nullptr);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Regression likelihoods (hddm/models/hddm_regression.py:26-36 into
+// wfpt.pyx:244-274; reg_kernels.hip).
+
+// The fixed inputs of a regression likelihood, resident: signed RTs and the
+// design matrix, group-major (the caller's order kept inside a group), the
+// design matrix column-major so that a column is contiguous over trials.
+struct wfpt_reg_ds {
+  wfpt_ctx* ctx = nullptr;
+  int64_t n = 0;
+  int32_t C = 0;
+  int32_t n_groups = 1;      // 1 without group ids
+  double* x = nullptr;       // [n] signed RTs, stored order (+-999 kept: a missing response)
+  double* X = nullptr;       // [C * n] column c at X + c * n, stored order
+  int32_t* group = nullptr;  // [n] group of a stored trial (null without group ids)
+  int64_t* off = nullptr;    // [n_groups + 1] stored range of each group
+  int64_t* caller = nullptr; // [n] the caller's index of a stored trial (null: identity)
+  std::vector<int64_t> off_host;
+  std::vector<int64_t> caller_host;  // empty: identity
+  int64_t group_max = 0;     // most trials in one group
+};
+
+namespace {
+
+void reg_free_device(wfpt_reg_ds* d) {
+  void** ptrs[] = {(void**)&d->x, (void**)&d->X, (void**)&d->group, (void**)&d->off,
+                   (void**)&d->caller};
+  for (void** p : ptrs) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+}
+
+void reg_detach(wfpt_reg_ds* d) {
+  reg_free_device(d);
+  d->ctx = nullptr;
+}
+
+// The checks of a term list that need no data set: parameter 0..6, each named
+// once, a known link, ncol >= 1, col0 >= 0.
+int reg_check_terms(const wfpt_reg_term* terms, int32_t n_terms) {
+  if (n_terms < 0 || n_terms > wfpt::kRegMaxTerms)
+    return fail(WFPT_ERR_ARG, "n_terms must be 0..7 (one term per parameter)");
+  if (n_terms > 0 && !terms) return fail(WFPT_ERR_ARG, "null pointer (terms)");
+  unsigned seen = 0;
+  for (int32_t k = 0; k < n_terms; ++k) {
+    const wfpt_reg_term& T = terms[k];
+    const std::string at = " (term " + std::to_string(k) + ")";
+    if (T.param < 0 || T.param > 6)
+      return fail(WFPT_ERR_ARG, "term parameter outside 0..6 (v, sv, a, z, sz, t, st)" + at);
+    if (seen & (1u << T.param)) return fail(WFPT_ERR_ARG, "a parameter is named twice" + at);
+    seen |= 1u << T.param;
+    if (T.link != WFPT_LINK_IDENTITY && T.link != WFPT_LINK_EXP && T.link != WFPT_LINK_INVLOGIT)
+      return fail(WFPT_ERR_ARG, "unknown link" + at);
+    if (T.ncol < 1) return fail(WFPT_ERR_ARG, "ncol < 1" + at);
+    if (T.col0 < 0) return fail(WFPT_ERR_ARG, "column range outside [0, C)" + at);
+  }
+  return WFPT_OK;
+}
+
+// The rest of an entry's checks, still before any device work.
+int reg_check_call(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                   int32_t n_terms) {
+  if (!wfpt::reg_kernels_linked() || !wfpt::rl_kernels_linked())
+    return fail(WFPT_ERR_UNSUPPORTED, "this build does not contain the regression kernels");
+  if (d->ctx != c) return fail(WFPT_ERR_ARG, "regression dataset belongs to another context");
+  for (int32_t k = 0; k < n_terms; ++k)
+    if ((int64_t)terms[k].col0 + terms[k].ncol > d->C)
+      return fail(WFPT_ERR_ARG,
+                  "column range outside [0, C) (term " + std::to_string(k) + ")");
+  return WFPT_OK;
+}
+
+// Uploads the call's coefficient rows, opens the profile bracket and launches
+// reg_fill_kernel: term k's predictions into c->reg_arr[k n ..], the fields of
+// `expand` after them. by_group: coefficients and rows are read through the
+// trial's group, else row 0 serves every trial.
+int reg_fill(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms, int32_t n_terms,
+             const double* coef, int32_t rows, bool by_group, int expand, bool want_pred) {
+  int slots = n_terms;
+  for (int f = 0; f < 7; ++f) slots += (expand >> f) & 1;
+  HIP_TRY(c->reg_arr.reserve(std::max<int64_t>((int64_t)slots * d->n, 1)));
+  HIP_TRY(c->reg_coef.reserve(std::max<int64_t>((int64_t)rows * d->C, 1)));
+  if (want_pred) HIP_TRY(c->reg_pred.reserve(std::max<int64_t>((int64_t)n_terms * d->n, 1)));
+  HIP_TRY(hipMemcpyAsync(c->reg_coef.p, coef, (size_t)rows * d->C * sizeof(double),
+                         hipMemcpyHostToDevice, c->stream));
+  if (c->count) HIP_TRY(hipMemsetAsync(c->evals, 0, sizeof(unsigned long long), c->stream));
+  if (c->profile) HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  wfpt::RegFill F;
+  F.n = d->n;
+  F.C = d->C;
+  F.n_terms = n_terms;
+  F.X = d->X;
+  F.group = by_group ? d->group : nullptr;
+  F.coef = c->reg_coef.p;
+  F.P = expand ? c->reg_par.p : nullptr;
+  F.expand = expand;
+  F.arr = c->reg_arr.p;
+  F.pred_in = want_pred ? c->reg_pred.p : nullptr;
+  F.caller = d->caller;
+  for (int k = 0; k < wfpt::kRegMaxTerms; ++k)
+    F.term[k] = k < n_terms ? wfpt::RegTerm{terms[k].param, terms[k].link, terms[k].col0,
+                                            terms[k].ncol}
+                            : wfpt::RegTerm{0, 0, 0, 0};
+  wfpt::launch_reg_fill(F, c->stream);
+  HIP_TRY(hipGetLastError());
+  return WFPT_OK;
+}
+
+// The _ex outputs of a finished call, in the caller's order.
+int reg_outputs(wfpt_ctx* c, const wfpt_reg_ds* d, int32_t n_terms, double* out_trial,
+                double* out_pred) {
+  if (out_trial && d->n > 0) {
+    if (d->caller_host.empty()) {
+      HIP_TRY(hipMemcpy(out_trial, c->lp.p, d->n * sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+      std::vector<double> h(d->n);
+      HIP_TRY(hipMemcpy(h.data(), c->lp.p, d->n * sizeof(double), hipMemcpyDeviceToHost));
+      for (int64_t i = 0; i < d->n; ++i) out_trial[d->caller_host[i]] = h[i];
+    }
+  }
+  if (out_pred && d->n > 0 && n_terms > 0)
+    HIP_TRY(hipMemcpy(out_pred, c->reg_pred.p, (size_t)n_terms * d->n * sizeof(double),
+                      hipMemcpyDeviceToHost));
+  return WFPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wfpt_reg_dataset_create(wfpt_ctx* c, const double* rt, int64_t n, const double* X, int32_t C,
+                            const int32_t* group_id, int32_t n_groups, wfpt_reg_ds** out) {
+  if (!c || !out) return fail(WFPT_ERR_ARG, "null pointer");
+  if (n < 0) return fail(WFPT_ERR_ARG, "n < 0");
+  if (C < 1) return fail(WFPT_ERR_ARG, "the design matrix needs at least one column");
+  if (n > 0 && (!rt || !X)) return fail(WFPT_ERR_ARG, "null rt / design matrix");
+  if (group_id && n_groups <= 0) return fail(WFPT_ERR_ARG, "group ids need n_groups > 0");
+  const int32_t G = group_id ? n_groups : 1;
+  for (int64_t i = 0; group_id && i < n; ++i)
+    if (group_id[i] < 0 || group_id[i] >= G)
+      return fail(WFPT_ERR_ARG, "group id out of range at trial " + std::to_string(i));
+  WFPT_RANGE("wfpt_reg_dataset_create");
+  std::vector<int64_t> idx(n);
+  for (int64_t i = 0; i < n; ++i) idx[i] = i;
+  bool identity = true;
+  if (group_id) {
+    std::stable_sort(idx.begin(), idx.end(),
+                     [&](int64_t a, int64_t b) { return group_id[a] < group_id[b]; });
+    for (int64_t i = 0; i < n && identity; ++i) identity = idx[i] == i;
+  }
+  std::vector<double> xs(n), Xc((size_t)C * n);
+  std::vector<int32_t> gs(group_id ? n : 0);
+  std::vector<int64_t> off(G + 1, 0);
+  for (int64_t j = 0; j < n; ++j) {
+    const int64_t src = idx[j];
+    xs[j] = rt[src];
+    for (int32_t col = 0; col < C; ++col) Xc[(size_t)col * n + j] = X[(size_t)src * C + col];
+    const int32_t g = group_id ? group_id[src] : 0;
+    if (group_id) gs[j] = g;
+    off[g + 1]++;
+  }
+  auto* d = new wfpt_reg_ds();
+  for (int32_t g = 0; g < G; ++g) {
+    d->group_max = std::max(d->group_max, off[g + 1]);
+    off[g + 1] += off[g];
+  }
+  d->ctx = c;
+  d->n = n;
+  d->C = C;
+  d->n_groups = G;
+  d->off_host = off;
+  if (!identity) d->caller_host = idx;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  hipError_t e = rl_up(&d->x, xs);
+  if (e == hipSuccess) e = rl_up(&d->X, Xc);
+  if (e == hipSuccess && group_id) e = rl_up(&d->group, gs);
+  if (e == hipSuccess) e = rl_up(&d->off, off);
+  if (e == hipSuccess && !identity) e = rl_up(&d->caller, idx);
+  if (e != hipSuccess) {
+    reg_free_device(d);
+    delete d;
+    return fail(WFPT_ERR_HIP, std::string("regression dataset upload: ") + hipGetErrorString(e));
+  }
+  c->reg_dsets.push_back(d);
+  *out = d;
+  return WFPT_OK;
+}
+
+void wfpt_reg_dataset_destroy(wfpt_reg_ds* d) {
+  if (!d) return;
+  if (wfpt_ctx* c = d->ctx) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    c->reg_dsets.erase(std::remove(c->reg_dsets.begin(), c->reg_dsets.end(), d),
+                       c->reg_dsets.end());
+    reg_free_device(d);
+  }
+  delete d;
+}
+
+int wfpt_wiener_like_reg_ex(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                            int32_t n_terms, const double* coef, const wfpt_params* p,
+                            const wfpt_knobs* k, double* out, double* out_trial,
+                            double* out_pred) {
+  if (int rc = reg_check_terms(terms, n_terms)) return rc;
+  if (!c || !d || !coef || !p || !k || !out) return fail(WFPT_ERR_ARG, "null pointer");
+  if (int rc = reg_check_call(c, d, terms, n_terms)) return rc;
+  const wfpt::Knobs K = to_knobs(k);
+  WFPT_RANGE("wfpt_wiener_like_reg");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const int64_t n = d->n;
+  if (int rc = reg_fill(c, d, terms, n_terms, coef, 1, false, 0, out_pred != nullptr)) return rc;
+  // a regressed parameter is an array of the pass, every other one its scalar,
+  // as wiener_like_multi(multi=[the regressed ones]) passes them
+  double* dptr[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double scal[7] = {p->v, p->sv, p->a, p->z, p->sz, p->t, p->st};
+  for (int32_t t = 0; t < n_terms; ++t) {
+    dptr[terms[t].param] = c->reg_arr.p + (int64_t)t * n;
+    scal[terms[t].param] = 0.0;
+  }
+  if (int rc = rl_score_reserve(c, n, 1, dptr, scal)) return rc;
+  if (n > 0)
+    if (int rc = rl_score_launch(c, d->x, n, 0, dptr, scal, K, p->p_outlier, c->lp.p)) return rc;
+  if (int rc = rl_finish(c, n, out)) return rc;
+  return reg_outputs(c, d, n_terms, out_trial, out_pred);
+}
+
+int wfpt_wiener_like_reg(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                         int32_t n_terms, const double* coef, const wfpt_params* p,
+                         const wfpt_knobs* k, double* out) {
+  return wfpt_wiener_like_reg_ex(c, d, terms, n_terms, coef, p, k, out, nullptr, nullptr);
+}
+
+int wfpt_wiener_like_reg_groups_ex(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                                   int32_t n_terms, const double* coef,
+                                   const wfpt_params* per_group, const wfpt_knobs* k,
+                                   double* out_logp, double* out_trial, double* out_pred) {
+  if (int rc = reg_check_terms(terms, n_terms)) return rc;
+  if (!c || !d || !coef || !per_group || !k || !out_logp)
+    return fail(WFPT_ERR_ARG, "null pointer");
+  if (int rc = reg_check_call(c, d, terms, n_terms)) return rc;
+  const int32_t G = d->n_groups;
+  if (d->group_max > wfpt::kRlNodeMax)
+    return fail(WFPT_ERR_UNSUPPORTED, "a group holds more trials than the per-group sum takes");
+  for (int32_t j = 1; j < G; ++j)  // the per-trial-parameter pass takes one p_outlier
+    if (per_group[j].p_outlier != per_group[0].p_outlier)
+      return fail(WFPT_ERR_UNSUPPORTED, "the groups call needs one p_outlier for all groups");
+  const double p_outlier = per_group[0].p_outlier;
+  const wfpt::Knobs K = to_knobs(k);
+  WFPT_RANGE("wfpt_wiener_like_reg_groups");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const int64_t n = d->n;
+  int term_of[7] = {-1, -1, -1, -1, -1, -1, -1};
+  for (int32_t t = 0; t < n_terms; ++t) term_of[terms[t].param] = t;
+  // v, sv, a, z and t per trial from the group rows unless regressed; sz and st
+  // stay scalars of the pass unless regressed, as in the single call, so a
+  // group's trials take the kernel the single call on that group takes
+  int expand = 0;
+  for (int f : {0, 1, 2, 3, 5})
+    if (term_of[f] < 0) expand |= 1 << f;
+  std::vector<wfpt::Params> par(G);
+  for (int32_t j = 0; j < G; ++j) par[j] = to_params(&per_group[j]);
+  HIP_TRY(c->reg_par.reserve(G));
+  HIP_TRY(hipMemcpyAsync(c->reg_par.p, par.data(), G * sizeof(wfpt::Params),
+                         hipMemcpyHostToDevice, c->stream));
+  if (int rc = reg_fill(c, d, terms, n_terms, coef, G, true, expand, out_pred != nullptr))
+    return rc;
+  const bool sz_fix = term_of[4] < 0, st_fix = term_of[6] < 0;
+  std::vector<int32_t> run_lo;  // first group of each run
+  for (int32_t j = 0; j < G; ++j)
+    if (j == 0 || (sz_fix && per_group[j].sz != per_group[j - 1].sz) ||
+        (st_fix && per_group[j].st != per_group[j - 1].st))
+      run_lo.push_back(j);
+  const int nruns = (int)run_lo.size();
+  run_lo.push_back(G);
+  std::vector<double*> tabs(7 * (size_t)nruns, nullptr);
+  std::vector<double> scals(7 * (size_t)nruns, 0.0);
+  for (int r = 0; r < nruns; ++r) {
+    const int64_t lo = d->off_host[run_lo[r]];
+    int slot = n_terms;
+    for (int f = 0; f < 7; ++f) {
+      if (term_of[f] >= 0)
+        tabs[7 * r + f] = c->reg_arr.p + (int64_t)term_of[f] * n + lo;
+      else if (expand & (1 << f))
+        tabs[7 * r + f] = c->reg_arr.p + (int64_t)slot++ * n + lo;
+    }
+    if (sz_fix) scals[7 * r + 4] = per_group[run_lo[r]].sz;
+    if (st_fix) scals[7 * r + 6] = per_group[run_lo[r]].st;
+  }
+  if (int rc = rl_score_reserve(c, n, nruns, tabs.data(), scals.data())) return rc;
+  for (int r = 0; r < nruns; ++r) {
+    const int64_t lo = d->off_host[run_lo[r]], hi = d->off_host[run_lo[r + 1]];
+    if (hi == lo) continue;
+    if (int rc = rl_score_launch(c, d->x + lo, hi - lo, r, &tabs[7 * r], &scals[7 * r], K,
+                                 p_outlier, c->lp.p + lo))
+      return rc;
+  }
+  HIP_TRY(c->reg_npart.reserve(wfpt::rl_node_partials(n, G)));
+  HIP_TRY(c->res.reserve(G));
+  wfpt::launch_rl_node_sum(c->lp.p, d->off, G, c->reg_npart.p, c->res.p, c->stream);
+  HIP_TRY(hipGetLastError());
+  double total;  // a finalize over no partials: the status word and the call's completion
+  if (int rc = rl_finish(c, 0, &total)) return rc;
+  HIP_TRY(hipMemcpy(out_logp, c->res.p, G * sizeof(double), hipMemcpyDeviceToHost));
+  return reg_outputs(c, d, n_terms, out_trial, out_pred);
+}
+
+int wfpt_wiener_like_reg_groups(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                                int32_t n_terms, const double* coef,
+                                const wfpt_params* per_group, const wfpt_knobs* k,
+                                double* out_logp) {
+  return wfpt_wiener_like_reg_groups_ex(c, d, terms, n_terms, coef, per_group, k, out_logp,
+                                        nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------

@@ -243,13 +243,18 @@ class HDDM:
             self.node_level[fam] = lv_codes
             self.node_unit[fam] = self.node_subj * n_lv + lv_codes
             self.n_units[fam] = self.n_subj * n_lv
-        self.dataset = _wfpt.Dataset(rt, node_id=node_codes, n_nodes=self.n_nodes, device=device)
+        self.dataset = self._make_dataset(rt, node_codes, device)
         self.n_trials = rt.size
         self.node_counts = np.bincount(node_codes, minlength=self.n_nodes).astype(np.int64)
         self.likelihood_calls = 0
         self.likelihood_seconds = 0.0
         self.call_stats = {}  # updated parameter -> [calls, seconds]
         self._init_values()
+
+    def _make_dataset(self, rt, node_codes, device):
+        """The resident data the node likelihoods are scored over (a subclass
+        with another likelihood keeps its own kind, regression.py)."""
+        return _wfpt.Dataset(rt, node_id=node_codes, n_nodes=self.n_nodes, device=device)
 
     # -- state ---------------------------------------------------------------
     def _init_values(self):

@@ -1,0 +1,400 @@
+"""HDDMRegressor on one MI355X: trial-wise parameters link(design . coefficients).
+
+The reference's HDDMRegressor (hddm/models/hddm_regression.py) builds a patsy
+design matrix per regressed outcome, multiplies it by the coefficient nodes
+in pandas on every likelihood evaluation and hands the trial-wise arrays to
+wfpt.wiener_like_multi (hddm_regression.py:26-36). Here the design matrix is
+resident (wfpt.RegDataset), the predictor runs on the device, and every
+evaluation is ONE `wiener_like_reg_groups` call that returns a sum per
+(subject x condition) node, so subject-level coefficients take the same block
+slice update over subjects as HDDM's subject nodes (hierarchical.py).
+
+* design_matrix: the subset of patsy's formula language the reference's
+  docstring examples use (`1`, `0`, numeric columns, `C(name)`, joined by
+  `+`); anything else goes to patsy when it is installed.
+* priors (hddm_regression.py:250-284): a coefficient whose name contains
+  `Intercept` (or, without an intercept, every plain `C(...)` column) takes
+  the outcome's own prior (hierarchical.py's header); every other coefficient
+  Normal(0, sd 15). With group_only_regressors=False every coefficient also
+  has subject nodes: the intercept in the outcome's family, the others
+  Normal(g, std) with std ~ Uniform(1e-10, 100) (base.py:310-369).
+* slice width 0.05 for every coefficient node (hddm_regression.py:284).
+* links run on the device and are named: identity, exp, invlogit.
+"""
+import re
+import time
+
+import numpy as np
+
+from . import wfpt as _wfpt
+from .hierarchical import (HDDM, SLICE_WIDTHS, beta_logpdf, gamma_logpdf_mean_sd,
+                           halfnormal_logpdf, normal_logpdf, slice_step)
+
+LINKS = ("identity", "exp", "invlogit")
+COEF_SLICE_WIDTH = 0.05  # hddm_regression.py:284
+_NAME = r"[A-Za-z_][A-Za-z_0-9.]*"
+
+
+# ---------------------------------------------------------------- design matrix
+
+def _patsy_or_raise(formula_rhs, data, term):
+    try:
+        import patsy
+    except ImportError:
+        raise NotImplementedError(
+            f"design_matrix: term {term!r} needs patsy, which is not installed; without it "
+            "only `1`, `0`, numeric columns and C(name) joined by `+` are supported")
+    return patsy.dmatrix(formula_rhs, data, return_type="dataframe")
+
+
+def design_matrix(formula_rhs, data):
+    """The design matrix of `formula_rhs` over DataFrame `data` as a float64
+    DataFrame with patsy's column names and column order: `Intercept` (implicit
+    unless `0` is given), then the `C(name)` terms in formula order (treatment
+    coding over the sorted levels, `C(name)[T.level]`; the first one full-coded
+    as `C(name)[level]` when there is no intercept), then the numeric columns
+    in formula order."""
+    import pandas as pd
+    terms = [t.strip() for t in formula_rhs.split("+")]
+    intercept = True
+    cats, nums = [], []
+    for t in terms:
+        if t == "1":
+            intercept = True
+        elif t in ("0", "-1"):
+            intercept = False
+        elif re.fullmatch(rf"C\(\s*({_NAME})\s*\)", t):
+            name = re.fullmatch(rf"C\(\s*({_NAME})\s*\)", t).group(1)
+            if name not in cats:
+                cats.append(name)
+        elif re.fullmatch(_NAME, t):
+            if t not in nums:
+                nums.append(t)
+        else:
+            return _patsy_or_raise(formula_rhs, data, t)
+    for name in cats + nums:
+        if name not in data:
+            raise KeyError(f"design_matrix: no column {name!r} in the data")
+    n = len(data)
+    cols = {}
+    if intercept:
+        cols["Intercept"] = np.ones(n)
+    for k, name in enumerate(cats):
+        val = data[name].to_numpy()
+        levels = sorted(pd.unique(val))
+        full = k == 0 and not intercept
+        for lv in (levels if full else levels[1:]):
+            cols[f"C({name})[{lv}]" if full else f"C({name})[T.{lv}]"] = (val == lv).astype(
+                np.float64)
+    for name in nums:
+        cols[name] = data[name].to_numpy(dtype=np.float64)
+    return pd.DataFrame(cols, index=data.index, dtype=np.float64)
+
+
+# ---------------------------------------------------------------- the model
+
+def _parse_models(models):
+    if isinstance(models, (str, dict)):
+        models = [models]
+    out = []
+    for m in models:
+        if isinstance(m, str):
+            m = {"model": m}
+        link = m.get("link_func", "identity")
+        if callable(link):
+            raise TypeError("HDDMRegressor: the link runs on the device, so link_func is a "
+                            f"name, one of {LINKS}, not a Python callable")
+        if link not in LINKS:
+            raise ValueError(f"HDDMRegressor: unknown link_func {link!r}; expected one of {LINKS}")
+        if "~" not in m["model"]:
+            raise ValueError(f"HDDMRegressor: model {m['model']!r} is not 'outcome ~ terms'")
+        outcome, rhs = (s.strip() for s in m["model"].split("~", 1))
+        if outcome not in ("v", "a", "t"):
+            raise NotImplementedError(
+                f"HDDMRegressor: outcome {outcome!r} is not supported at model level (v, a, t)")
+        if any(d["outcome"] == outcome for d in out):
+            raise ValueError(f"HDDMRegressor: outcome {outcome!r} has two models")
+        out.append({"outcome": outcome, "rhs": rhs, "link": link})
+    return out
+
+
+class HDDMRegressor(HDDM):
+    """HDDMRegressor(data, 'v ~ BOLD').sample(n) on one MI355X.
+
+    models: 'v ~ 1 + BOLD', {'model': ..., 'link_func': 'identity' | 'exp' |
+    'invlogit'}, or a list of these; outcomes v, a, t. Coefficients are named
+    `{outcome}_{design column}`. The non-regressed families stay as in HDDM.
+    """
+
+    _GROUP_PRIOR = {"a": lambda x: gamma_logpdf_mean_sd(x, 1.5, 0.75),
+                    "v": lambda x: normal_logpdf(x, 2.0, 3.0),
+                    "t": lambda x: gamma_logpdf_mean_sd(x, 0.4, 0.2)}
+    _STD_SD = {"a": 2.0, "v": 2.0, "t": 1.0}
+    _START = {"a": (1.5, 1.0), "v": (2.0, 2.0), "t": (0.4, 0.001)}  # group, subject
+
+    def __init__(self, data, models, group_only_regressors=True, include=(), p_outlier=0.05,
+                 wiener_params=None, seed=None, device=None, depends_on=None):
+        import pandas as pd
+        self.model_descrs = _parse_models(models)
+        self.reg_outcomes = [d["outcome"] for d in self.model_descrs]
+        for k in (depends_on or {}):
+            if k in self.reg_outcomes:  # hddm_regression.py:214-216
+                raise ValueError(f"HDDMRegressor: '{k}' is a regression outcome and cannot be "
+                                 "used in depends_on")
+        self.group_only_regressors = bool(group_only_regressors)
+        self.FAMILIES = tuple(f for f in ("a", "v", "t") if f not in self.reg_outcomes)
+        frame = pd.DataFrame(data).reset_index(drop=True)
+        mats, col0 = [], 0
+        self.coef_names, self.coef_outcome, self.coef_intercept = [], [], []
+        self.reg_model = []  # RegDataset's (param, col0, ncol, link) terms
+        for d in self.model_descrs:
+            X = design_matrix(d["rhs"], frame)
+            names = [f"{d['outcome']}_{c}" for c in X.columns]
+            inter = ["Intercept" in nm for nm in names]
+            if not any(inter):  # 0 + C(...): every condition is an intercept (:257-260)
+                inter = ["C(" in nm and ":" not in nm for nm in names]
+            d["params"] = names
+            self.coef_names += names
+            self.coef_outcome += [d["outcome"]] * len(names)
+            self.coef_intercept += inter
+            self.reg_model.append((d["outcome"], col0, X.shape[1], d["link"]))
+            col0 += X.shape[1]
+            mats.append(X.to_numpy(dtype=np.float64))
+        self.design = np.ascontiguousarray(np.hstack(mats))
+        self.n_coef = col0
+        super().__init__(frame, depends_on=depends_on, include=include, p_outlier=p_outlier,
+                         wiener_params=wiener_params, seed=seed, device=device,
+                         paired_probes=False)
+
+    def _make_dataset(self, rt, node_codes, device):
+        return _wfpt.RegDataset(rt, self.design, group_id=node_codes, n_groups=self.n_nodes,
+                                device=device)
+
+    # -- state ---------------------------------------------------------------
+    def _init_values(self):
+        """HDDM's starting values (hddm_info.py:121-140) for the non-regressed
+        families; an intercept starts where its outcome would, every other
+        coefficient at 0."""
+        fams = self.FAMILIES
+        self.group = {f: np.full(len(self.levels[f]), self._START[f][0]) for f in fams}
+        self.std = {f: {"a": 0.1, "v": 0.1, "t": 0.2}[f] for f in fams}
+        self.subj = {f: np.full(self.n_units[f], self._START[f][1]) for f in fams}
+        self.inter = {"sv": 1.0 if "sv" in self.include else 0.0,
+                      "sz": 0.01 if "sz" in self.include else 0.0,
+                      "st": 0.001 if "st" in self.include else 0.0}
+        self.coef, self.coef_std, self.coef_subj = {}, {}, {}
+        for nm, out, inter in zip(self.coef_names, self.coef_outcome, self.coef_intercept):
+            g0, s0 = self._START[out] if inter else (0.0, 0.0)
+            if self.group_only_regressors:
+                # the group node feeds the likelihood directly: start where a
+                # subject node would (t below every RT)
+                self.coef[nm] = s0
+            else:
+                self.coef[nm] = g0
+                self.coef_std[nm] = 0.1
+                self.coef_subj[nm] = np.full(self.n_subj, s0)
+
+    def coef_table(self, over=None):
+        """(n_nodes, C) coefficient rows: a group-only coefficient in every
+        row, a subject-level one through the node's subject. `over` replaces
+        named coefficients (a scalar, or one value per subject)."""
+        B = np.empty((self.n_nodes, self.n_coef))
+        for j, nm in enumerate(self.coef_names):
+            val = over[nm] if over and nm in over else (
+                self.coef[nm] if self.group_only_regressors else self.coef_subj[nm])
+            B[:, j] = val if np.ndim(val) == 0 else np.asarray(val)[self.node_subj]
+        return B
+
+    def node_table(self, over=None):
+        """(n_nodes, 8) parameter table as HDDM.node_table; a regressed
+        outcome's column is unused by the likelihood (0)."""
+        P = np.zeros((self.n_nodes, 8))
+        over = over or {}
+        for fam in self.FAMILIES:
+            x = over.get(fam, self.subj[fam])
+            P[:, self._COL[fam]] = x[self.node_unit[fam]]
+        P[:, 3] = 0.5
+        for name in ("sv", "sz", "st"):
+            P[:, self._COL[name]] = over.get(name, self.inter[name])
+        P[:, 7] = self.p_outlier
+        return P
+
+    def node_logp(self, over=None):
+        """One wiener_like_reg_groups call: the (n_nodes,) sums. Keys of `over`
+        that name coefficients go to the coefficient table, the others to the
+        parameter table."""
+        over = over or {}
+        t0 = time.perf_counter()
+        out = self.dataset.wiener_like_reg_groups(self.reg_model, self.coef_table(over),
+                                                  self.node_table(over), **self.wp)
+        dt = time.perf_counter() - t0
+        self.likelihood_seconds += dt
+        self.likelihood_calls += 1
+        st = self.call_stats.setdefault(",".join(sorted(over)) if over else "-", [0, 0.0])
+        st[0] += 1
+        st[1] += dt
+        return out
+
+    def node_logp_multi(self, overs):
+        raise NotImplementedError("HDDMRegressor scores one table per call")
+
+    # -- priors --------------------------------------------------------------
+    def _coef_group_prior(self, nm, x):
+        j = self.coef_names.index(nm)
+        if self.coef_intercept[j]:
+            return self._GROUP_PRIOR[self.coef_outcome[j]](x)
+        return normal_logpdf(x, 0.0, 15.0)
+
+    def _coef_subj_prior(self, nm, x, g=None, std=None):
+        j = self.coef_names.index(nm)
+        g = float(self.coef[nm] if g is None else g)
+        std = float(self.coef_std[nm] if std is None else std)
+        if self.coef_intercept[j] and self.coef_outcome[j] != "v":
+            return gamma_logpdf_mean_sd(x, g, std)
+        return normal_logpdf(x, g, std)
+
+    def _coef_std_prior(self, nm, s):
+        j = self.coef_names.index(nm)
+        if self.coef_intercept[j]:
+            return float(halfnormal_logpdf(s, self._STD_SD[self.coef_outcome[j]]))
+        return -np.log(100.0 - 1e-10) if 1e-10 <= s <= 100.0 else -np.inf
+
+    def _coef_lower(self, nm):
+        j = self.coef_names.index(nm)
+        return 0.0 if self.coef_intercept[j] and self.coef_outcome[j] in ("a", "t") else None
+
+    def logp(self):
+        """Joint log density of the model at the current values."""
+        lp = float(np.sum(self.node_logp()))
+        for fam in self.FAMILIES:
+            lp += float(np.sum(self.subj_prior(fam, self.subj[fam])))
+            lp += float(np.sum(self._GROUP_PRIOR[fam](self.group[fam])))
+            lp += float(halfnormal_logpdf(self.std[fam], self._STD_SD[fam]))
+        for nm in self.coef_names:
+            lp += float(self._coef_group_prior(nm, self.coef[nm]))
+            if not self.group_only_regressors:
+                lp += float(np.sum(self._coef_subj_prior(nm, self.coef_subj[nm])))
+                lp += self._coef_std_prior(nm, self.coef_std[nm])
+        inter_prior = {"sv": lambda x: halfnormal_logpdf(x, 2.0),
+                       "sz": lambda x: beta_logpdf(x, 1, 3),
+                       "st": lambda x: halfnormal_logpdf(x, 0.3)}
+        for name in ("sv", "sz", "st"):
+            if name in self.include:
+                lp += float(inter_prior[name](self.inter[name]))
+        return lp
+
+    # -- updates -------------------------------------------------------------
+    def _update_coef_group_only(self, nm):
+        def logp(x):
+            val = float(x[0])
+            pr = float(self._coef_group_prior(nm, val))
+            if not np.isfinite(pr):
+                return np.array([-np.inf])
+            return np.array([pr + float(np.sum(self.node_logp({nm: val})))])
+
+        new, _ = slice_step(np.array([self.coef[nm]]), logp, COEF_SLICE_WIDTH, self.rng,
+                            lower=self._coef_lower(nm))
+        self.coef[nm] = float(new[0])
+
+    def _update_coef_subject(self, nm):
+        """All subjects' nodes of one coefficient in one block slice step from
+        the per-node sums, like HDDM._update_subject."""
+        def logp(x):
+            ll = np.bincount(self.node_subj, weights=self.node_logp({nm: x}),
+                             minlength=self.n_subj)
+            return ll + self._coef_subj_prior(nm, x)
+
+        self.coef_subj[nm], _ = slice_step(self.coef_subj[nm], logp, COEF_SLICE_WIDTH, self.rng,
+                                           lower=self._coef_lower(nm))
+
+    def _update_coef_group(self, nm):
+        x = self.coef_subj[nm]
+
+        def logp(g):
+            val = float(g[0])
+            pr = float(self._coef_group_prior(nm, val))
+            if not np.isfinite(pr):
+                return np.array([-np.inf])
+            return np.array([pr + float(np.sum(self._coef_subj_prior(nm, x, g=val)))])
+
+        new, _ = slice_step(np.array([self.coef[nm]]), logp, COEF_SLICE_WIDTH, self.rng,
+                            lower=self._coef_lower(nm))
+        self.coef[nm] = float(new[0])
+
+        def logp_std(s):
+            val = float(s[0])
+            pr = self._coef_std_prior(nm, val) if val > 0 else -np.inf
+            if not np.isfinite(pr):
+                return np.array([-np.inf])
+            return np.array([pr + float(np.sum(self._coef_subj_prior(nm, x, std=val)))])
+
+        new, _ = slice_step(np.array([self.coef_std[nm]]), logp_std, SLICE_WIDTHS["v_std"],
+                            self.rng, lower=0.0)
+        self.coef_std[nm] = float(new[0])
+
+    def sweep(self):
+        """One MCMC iteration: every stochastic updated once."""
+        for fam in self.FAMILIES:
+            self._update_group(fam)
+            self._update_subject(fam)
+        for nm in self.coef_names:
+            if self.group_only_regressors:
+                self._update_coef_group_only(nm)
+            else:
+                self._update_coef_group(nm)
+                self._update_coef_subject(nm)
+        for name in ("sv", "sz", "st"):
+            if name in self.include:
+                self._update_inter(name)
+
+    def sample(self, iter, burn=0, thin=1, progress=None):
+        """Run `iter` sweeps; keep every `thin`-th after `burn`. Returns traces
+        of the group-level nodes (dict name -> array): HDDM's names for the
+        non-regressed families, the coefficient names, `{coefficient}_std`
+        with subject-level coefficients."""
+        names = []
+        for fam in self.FAMILIES:
+            for k, lv in enumerate(self.levels[fam]):
+                names.append((f"{fam}" + (f"({','.join(map(str, lv))})" if lv else ""), fam, k))
+        trace = {name: [] for name, _, _ in names}
+        for fam in self.FAMILIES:
+            trace[f"{fam}_std"] = []
+        for nm in self.coef_names:
+            trace[nm] = []
+            if not self.group_only_regressors:
+                trace[f"{nm}_std"] = []
+        inter = [name for name in ("sv", "sz", "st") if name in self.include]
+        for name in inter:
+            trace[name] = []
+        subj_keys = list(self.FAMILIES) + ([] if self.group_only_regressors else self.coef_names)
+        trace_subj = {k: [] for k in subj_keys}
+        t0 = time.perf_counter()
+        for it in range(iter):
+            self.sweep()
+            if it >= burn and (it - burn) % thin == 0:
+                for name, fam, k in names:
+                    trace[name].append(self.group[fam][k])
+                for fam in self.FAMILIES:
+                    trace[f"{fam}_std"].append(self.std[fam])
+                    trace_subj[fam].append(self.subj[fam].copy())
+                for nm in self.coef_names:
+                    trace[nm].append(self.coef[nm])
+                    if not self.group_only_regressors:
+                        trace[f"{nm}_std"].append(self.coef_std[nm])
+                        trace_subj[nm].append(self.coef_subj[nm].copy())
+                for name in inter:
+                    trace[name].append(self.inter[name])
+            if progress and (it + 1) % progress == 0:
+                el = time.perf_counter() - t0
+                print(f"  [{it + 1}/{iter}] {el:.1f}s, {self.likelihood_calls} batched "
+                      f"likelihood calls", flush=True)
+        self.trace = {k: np.asarray(v) for k, v in trace.items()}
+        self.trace_subj = {k: np.asarray(v) for k, v in trace_subj.items()}
+        self.sample_seconds = time.perf_counter() - t0
+        return self.trace
+
+    def post_pred_rows(self, samples=500):
+        raise NotImplementedError("the regressor's posterior predictive is not implemented")
+
+    def post_pred_gen(self, samples=500, seed=None, cdf_range=(-5, 5), dt=1e-4):
+        raise NotImplementedError("the regressor's posterior predictive is not implemented")

@@ -21,7 +21,9 @@ Additions for resident data (the reference re-reads host memory every call):
 signature minus `x`. `Dataset(rt, node_id=...)` + `wiener_like_nodes` scores
 many PyMC nodes in one launch. `gen_rts_from_cdf_nodes` draws RTs for many
 parameter rows in one call, grid, CDF and search on the device (posterior
-predictive data sets: HDDM.post_pred_gen).
+predictive data sets: HDDM.post_pred_gen). `RegDataset(rt, design)` keeps a
+design matrix resident and forms HDDMRegressor's trial-wise parameters
+link(design . coefficients) on the device (hddm_regression.py:26-36).
 """
 import ctypes
 
@@ -32,7 +34,7 @@ from . import _lib
 __all__ = ["pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "gen_rts_from_cdf",
            "gen_rts_from_cdf_nodes", "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl",
            "wiener_like_multi_rlddm", "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_terms",
-           "wiener_like_rl_terms", "wiener_like_multi_rlddm_terms"]
+           "wiener_like_rl_terms", "wiener_like_multi_rlddm_terms", "RegDataset"]
 
 
 def _check_x(x, name="x"):
@@ -685,6 +687,152 @@ class RLDataset:
             self.ctx.handle, self.handle, _lib.dptr(rr), pm.ctypes.data_as(_lib._PP),
             ctypes.byref(K), _lib.dptr(out), ptr, pdr))
         return (out, tr, dr) if terms else out
+
+
+# ---------------------------------------------------------------------------
+# Regression likelihoods (hddm/models/hddm_regression.py:26-36)
+
+REG_PARAMS = ("v", "sv", "a", "z", "sz", "t", "st")
+REG_LINKS = {"identity": _lib.LINK_IDENTITY, "exp": _lib.LINK_EXP,
+             "invlogit": _lib.LINK_INVLOGIT}
+
+
+def _reg_terms(model, n_cols):
+    """[(param_name, col0, ncol, link_name), ...] -> a wfpt_reg_term array.
+    Checks that need no device: known names, one term per parameter, column
+    ranges inside the design matrix."""
+    model = list(model)
+    arr = (_lib.RegTerm * max(len(model), 1))()
+    seen = set()
+    for k, term in enumerate(model):
+        try:
+            name, col0, ncol, link = term
+        except (TypeError, ValueError):
+            raise ValueError("a model term is (param_name, col0, ncol, link_name)")
+        if name not in REG_PARAMS:
+            raise ValueError(f"unknown parameter {name!r}; expected one of {REG_PARAMS}")
+        if name in seen:
+            raise ValueError(f"parameter {name!r} is named twice")
+        seen.add(name)
+        if link not in REG_LINKS:
+            raise ValueError(f"unknown link {link!r}; the link runs on the device and is one "
+                             f"of {tuple(REG_LINKS)}")
+        col0, ncol = int(col0), int(ncol)
+        if ncol < 1 or col0 < 0 or col0 + ncol > n_cols:
+            raise ValueError(f"columns [{col0}, {col0 + ncol}) of term {name!r} lie outside "
+                             f"the design matrix's {n_cols} columns")
+        arr[k] = _lib.RegTerm(REG_PARAMS.index(name), REG_LINKS[link], col0, ncol)
+    return arr, len(model)
+
+
+class RegDataset:
+    """The fixed inputs of a regression likelihood (signed RTs and the design
+    matrix) resident in HBM: per call only the coefficients go to the device,
+    and the trial-wise parameters link(design . coefficients) are formed there.
+    `design` is an (n, C) array or DataFrame. Optional `group_id` groups the
+    trials into `n_groups` groups (subjects) scored together by
+    `wiener_like_reg_groups`. |rt| == 999 is a missing response, as in
+    wiener_like_multi (wfpt.pyx:261-270)."""
+
+    def __init__(self, rt, design, group_id=None, n_groups=None, device=None, ctx=None):
+        rt = np.ascontiguousarray(np.asarray(rt, dtype=np.float64).ravel())
+        n = rt.shape[0]
+        self.columns = list(getattr(design, "columns", ()))
+        X = np.ascontiguousarray(np.asarray(design, dtype=np.float64))
+        if X.ndim != 2 or X.shape[0] != n or X.shape[1] < 1:
+            raise ValueError(f"design must have shape ({n}, C) with C >= 1, got {X.shape}")
+        node = nptr = None
+        self.n_groups = 1
+        if group_id is not None:
+            node = np.ascontiguousarray(np.asarray(group_id, dtype=np.int32).ravel())
+            _same_length(n, group_id=node)
+            self.n_groups = int(n_groups if n_groups is not None else (node.max() + 1 if node.size
+                                                                       else 0))
+            if self.n_groups < 1:
+                raise ValueError("group ids need n_groups >= 1")
+            if node.size and (node.min() < 0 or node.max() >= self.n_groups):
+                raise ValueError(f"group ids must lie in [0, {self.n_groups})")
+            nptr = node.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        self.n = n
+        self.n_cols = int(X.shape[1])
+        self.grouped = group_id is not None
+        self.ctx = ctx if ctx is not None else _lib.context(device)
+        h = _lib._VP()
+        _lib.check(_lib.wfpt_reg_dataset_create(
+            self.ctx.handle, _lib.dptr(rt), n, _lib.dptr(X), self.n_cols, nptr, self.n_groups,
+            ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.wfpt_reg_dataset_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.n
+
+    def _outputs(self, terms, n_terms):
+        if not terms:
+            return None, None, None, None
+        tr = np.empty(self.n, dtype=np.float64)
+        pr = np.empty((max(n_terms, 1), self.n), dtype=np.float64)
+        return tr, pr, _lib.dptr(tr), _lib.dptr(pr)
+
+    def wiener_like_reg(self, model, coef, v, sv, a, z, sz, t, st, err, n_st=10, n_sz=10,
+                        use_adaptive=1, simps_err=1e-3, p_outlier=0, w_outlier=0, terms=False):
+        """The reference's regression node (hddm_regression.py:26-36 into
+        wiener_like_multi, wfpt.pyx:244-274) over the resident trials: `model`
+        is a list of (param_name, col0, ncol, link_name), `coef` one
+        coefficient per design column; a regressed parameter's scalar argument
+        is ignored. terms=True: (sum, per-trial terms, {param: predicted
+        array}), caller order."""
+        model = list(model)
+        T, nt = _reg_terms(model, self.n_cols)
+        b = np.ascontiguousarray(np.asarray(coef, dtype=np.float64).ravel())
+        if b.shape != (self.n_cols,):
+            raise ValueError(f"coef must have one entry per design column ({self.n_cols})")
+        P = _lib.make_params(v, sv, a, z, sz, t, st, p_outlier)
+        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        out = ctypes.c_double()
+        tr, pr, ptr, ppr = self._outputs(terms, nt)
+        _lib.check(_lib.wfpt_wiener_like_reg_ex(
+            self.ctx.handle, self.handle, T, nt, _lib.dptr(b), ctypes.byref(P), ctypes.byref(K),
+            ctypes.byref(out), ptr, ppr))
+        if not terms:
+            return out.value
+        return out.value, tr, {m[0]: pr[k] for k, m in enumerate(model)}
+
+    def wiener_like_reg_groups(self, model, coef_table, params, err=1e-4, n_st=2, n_sz=2,
+                               use_adaptive=1, simps_err=1e-3, w_outlier=0.1, terms=False):
+        """One regression node per group in one fill launch and one scoring
+        pass: coef_table (G, C) one coefficient row per group, params (G, 8) of
+        v, sv, a, z, sz, t, st, p_outlier (one p_outlier for all groups).
+        Returns the (G,) per-group sums; terms=True: (sums, per-trial terms,
+        {param: predicted array})."""
+        model = list(model)
+        T, nt = _reg_terms(model, self.n_cols)
+        G = self.n_groups
+        bt = np.ascontiguousarray(coef_table, dtype=np.float64)
+        pm = np.ascontiguousarray(params, dtype=np.float64)
+        if bt.shape != (G, self.n_cols):
+            raise ValueError(f"coef_table must have shape ({G}, {self.n_cols})")
+        if pm.shape != (G, 8):
+            raise ValueError(f"params must have shape ({G}, 8)")
+        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        out = np.empty(G, dtype=np.float64)
+        tr, pr, ptr, ppr = self._outputs(terms, nt)
+        _lib.check(_lib.wfpt_wiener_like_reg_groups_ex(
+            self.ctx.handle, self.handle, T, nt, _lib.dptr(bt), pm.ctypes.data_as(_lib._PP),
+            ctypes.byref(K), _lib.dptr(out), ptr, ppr))
+        if not terms:
+            return out
+        return out, tr, {m[0]: pr[k] for k, m in enumerate(model)}
 
 
 def _rl_dataset(x, response, feedback, split_by):

@@ -261,6 +261,80 @@ int wfpt_wiener_like_rlddm_nodes_ex(wfpt_ctx *ctx, const wfpt_rl_ds *ds, const d
                                     const wfpt_params *per_node, const wfpt_knobs *k,
                                     double *out_logp, double *out_trial, double *out_drift);
 
+/* ---- regression likelihoods (HDDMRegressor) ------------------------------ */
+/* The reference's regression node (hddm/models/hddm_regression.py:26-36,
+ * wiener_multi_like) computes each regressed parameter per trial on the host
+ * as link(design matrix . coefficients) and passes the arrays to
+ * wfpt.wiener_like_multi (src/wfpt.pyx:244-274). Here the design matrix is
+ * resident and the predictor runs on the device (reg_fill_kernel); only the
+ * coefficients go up per call.
+ *   wfpt_wiener_like_reg*        <- wiener_multi_like  hddm_regression.py:26-36
+ *                                   + wiener_like_multi src/wfpt.pyx:244-274
+ *   wfpt_wiener_like_reg_groups* <- one such node per subject, batched
+ * Order contract: a term's linear predictor is
+ *   eta = X[i, col0] * b[col0]; eta = eta + X[i, col0 + 1] * b[col0 + 1]; ...
+ * left to right, every product and every sum rounded separately (no fused
+ * multiply-add). Link contract: IDENTITY eta; EXP the correctly rounded
+ * exponential of eta; INVLOGIT 1 / (1 + exp(-eta)) with that exponential, the
+ * sum and the quotient each rounded once.
+ * Semantics are wiener_like_multi's: no p_outlier range check, |rt| == 999 is
+ * a missing response scored by prob_ub (wfpt.pyx:261-270), a zero mixture
+ * density contributes -inf. */
+#define WFPT_LINK_IDENTITY 0
+#define WFPT_LINK_EXP 1
+#define WFPT_LINK_INVLOGIT 2
+typedef struct {
+  int32_t param, link, col0, ncol; /* param 0..6 = v, sv, a, z, sz, t, st */
+} wfpt_reg_term;
+typedef struct wfpt_reg_ds wfpt_reg_ds;
+/* Uploads n signed RTs and the row-major (n, C) design matrix X once (the
+ * `data` and design matrices hddm_regression.py:84-101 keeps per node).
+ * group_id (nullable, n_groups): trials are stored group-major, the caller's
+ * order kept inside a group; without it there is one group in the caller's
+ * order. WFPT_ERR_ARG: n < 0, C < 1, a null array with n > 0, a group id out
+ * of range. The caller's arrays are not retained. */
+int wfpt_reg_dataset_create(wfpt_ctx *ctx, const double *rt, int64_t n, const double *X,
+                            int32_t C, const int32_t *group_id, int32_t n_groups,
+                            wfpt_reg_ds **out);
+void wfpt_reg_dataset_destroy(wfpt_reg_ds *ds);
+/* The reference's wfpt_reg node (hddm_regression.py:26-36, 103-113): one
+ * coefficient vector coef[C], one parameter row; out_logp = the sum over all
+ * trials. A regressed parameter's field of p is ignored; the others are the
+ * scalars of the per-trial-parameter pass, so the result is bit for bit
+ * wfpt_wiener_like_multi_resident given the predicted arrays.
+ * WFPT_ERR_ARG, before any device work: null pointers, more than 7 terms, a
+ * term parameter outside 0..6, a parameter named twice, an unknown link,
+ * ncol < 1, a column range outside [0, C), a data set of another context. */
+int wfpt_wiener_like_reg(wfpt_ctx *ctx, const wfpt_reg_ds *ds, const wfpt_reg_term *terms,
+                         int32_t n_terms, const double *coef, const wfpt_params *p,
+                         const wfpt_knobs *k, double *out_logp);
+/* out_trial (nullable, n): each trial's log term; out_pred (nullable,
+ * n_terms * n): term k's predicted parameter of trial i at [k * n + i]. Both
+ * in the caller's order. */
+int wfpt_wiener_like_reg_ex(wfpt_ctx *ctx, const wfpt_reg_ds *ds, const wfpt_reg_term *terms,
+                            int32_t n_terms, const double *coef, const wfpt_params *p,
+                            const wfpt_knobs *k, double *out_logp, double *out_trial,
+                            double *out_pred);
+/* One regression node per group (subject) in one fill launch and one scoring
+ * pass (the per-subject nodes hddm_regression.py:214-236 builds when
+ * group_only_regressors is False, and what a block update over subjects
+ * needs): coef[n_groups * C] one coefficient row per group, per_group[n_groups]
+ * its parameter row, out_logp[n_groups]. Group g's sum is bit for bit
+ * wfpt_wiener_like_reg on that group's trials alone with row g; a group
+ * without trials sums to 0.0. sz and st stay scalars of the pass unless
+ * regressed: one scoring launch per run of consecutive groups that share them.
+ * The groups must share p_outlier and a group may hold at most 2^22 trials
+ * (WFPT_ERR_UNSUPPORTED otherwise). */
+int wfpt_wiener_like_reg_groups(wfpt_ctx *ctx, const wfpt_reg_ds *ds, const wfpt_reg_term *terms,
+                                int32_t n_terms, const double *coef,
+                                const wfpt_params *per_group, const wfpt_knobs *k,
+                                double *out_logp);
+int wfpt_wiener_like_reg_groups_ex(wfpt_ctx *ctx, const wfpt_reg_ds *ds,
+                                   const wfpt_reg_term *terms, int32_t n_terms,
+                                   const double *coef, const wfpt_params *per_group,
+                                   const wfpt_knobs *k, double *out_logp, double *out_trial,
+                                   double *out_pred);
+
 /* ---- DMAT / Tuerlinckx CDF ---------------------------------------------- */
 /* Per-trial CDF of signed RTs with the outlier mixture, exactly
  * cdfdif_wrapper.dmat_cdf_array(x, v, sv, a, z, sz, t, st, p_outlier, w_outlier)
