@@ -190,6 +190,11 @@ wfpt_gen_rts_nodes = _sig("wfpt_gen_rts_nodes", _I,
 wfpt_gen_rts_nodes_ex = _sig("wfpt_gen_rts_nodes_ex", _I,
                              [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD, _PD,
                               _PD, _PI64, _PD, _PD])
+wfpt_gen_rts_drift_nodes = _sig("wfpt_gen_rts_drift_nodes", _I,
+                                [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64, _PD, _PI64])
+wfpt_gen_rts_drift_nodes_ex = _sig("wfpt_gen_rts_drift_nodes_ex", _I,
+                                   [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64, _I64, _I32,
+                                    _PD, _PI64, _PD, _PD, _PD, _PD, _PI64, _PI64])
 wfpt_profile_stages = _sig("wfpt_profile_stages", _I, [_VP, _PD, _I])
 
 EXPORTED = [
@@ -210,6 +215,7 @@ EXPORTED = [
     "wfpt_wiener_like_multi_rlddm", "wfpt_wiener_like_multi_rlddm_ex",
     "wfpt_wiener_like_rlddm_nodes", "wfpt_wiener_like_rlddm_nodes_ex",
     "wfpt_gen_rts_nodes", "wfpt_gen_rts_nodes_ex", "wfpt_profile_stages",
+    "wfpt_gen_rts_drift_nodes", "wfpt_gen_rts_drift_nodes_ex",
     "wfpt_reg_dataset_create", "wfpt_reg_dataset_destroy", "wfpt_wiener_like_reg",
     "wfpt_wiener_like_reg_ex", "wfpt_wiener_like_reg_groups", "wfpt_wiener_like_reg_groups_ex",
 ]

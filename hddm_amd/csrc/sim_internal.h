@@ -61,7 +61,46 @@ struct SimDraw {
 WFPT_SIM_WEAK void launch_sim_draw(const SimTile& T, const SimDraw& D, int64_t first,
                                    int64_t ndraws, hipStream_t s);
 
+// The diffusion-path simulator (hddm/generate.py:208-319): one
+// row of the call's table. nn: the first step that uses the switched drift
+// (round(t_switch / dt)), kDriftNoSwitch for a row without a switch.
+constexpr uint32_t kDriftNoSwitch = 0xFFFFFFFFu;
+struct DriftRow {
+  double v, sv, a, z, sz, t, st;
+  double v_switch, V_switch;
+  uint32_t nn;
+  uint32_t pad;
+};
+
+// Draw j of global row row0 + r is element off[r] + j of out and of the
+// (nullable) per-draw arrays. step = sqrt(dt) * intra_sv and scale = sqrt(dt) /
+// intra_sv are formed on the host as generate.py:258,279 forms them. Every
+// random number is a Philox4x32-10 word keyed by seed at counter (j lo, j hi,
+// row0 + r, stream), so neither the launch shape nor wave_draws (draws handed
+// to one wave, a multiple of 64) can change a value. A draw that has not
+// crossed after max_steps steps is NaN.
+struct DriftCall {
+  const DriftRow* rows;  // [R]
+  const int64_t* off;    // [R + 1] prefix sums of the counts
+  int64_t R;
+  int64_t row0;
+  int64_t total;
+  double dt, step, scale;
+  uint32_t max_steps;    // 1 .. 2^31
+  int32_t wave_draws;
+  uint64_t seed;
+  double* out;
+  double* y0;            // start point
+  double* delay;         // non-decision time of the draw
+  double* drift;         // drift rate
+  double* drift_switch;  // drift rate from step nn on (0 for a row without a switch)
+  int64_t* n_steps;      // steps taken: the crossing step's index + 1, or max_steps
+  int64_t* wave_steps;   // [ceil(total / wave_draws)] steps each wave's loop ran
+};
+WFPT_SIM_WEAK void launch_sim_drift(const DriftCall& C, hipStream_t s);
+
 inline bool sim_kernels_linked() {
-  return launch_sim_pdf && launch_sim_scan && launch_sim_norm && launch_sim_draw;
+  return launch_sim_pdf && launch_sim_scan && launch_sim_norm && launch_sim_draw &&
+         launch_sim_drift;
 }
 }  // namespace wfpt

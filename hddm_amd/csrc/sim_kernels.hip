@@ -10,6 +10,10 @@
 //   sim_draw_kernel   one draw per lane: uniforms (supplied or Philox),
 //                     searchsorted(side='left') by bisection, the
 //                     non-decision-time shift
+// and the diffusion-path simulator (_gen_rts_from_simulated_drift,
+// hddm/generate.py:208-319):
+//   sim_drift_kernel  one walk per lane at a time, lanes refilled from their
+//                     wave's range of draws, Philox step outcomes
 #include <hip/hip_runtime.h>
 
 #include "sim_internal.h"
@@ -221,6 +225,139 @@ __global__ __launch_bounds__(kSimBlock) void sim_draw_kernel(SimTile T, SimDraw 
   if (D.ud_out) D.ud_out[e] = u;
 }
 
+// ---------------------------------------------------------------------------
+// The diffusion-path simulator (_gen_rts_from_simulated_drift,
+// hddm/generate.py:208-319).
+
+constexpr int kDriftBlock = 64;  // one wave per block: a wave's slot is free again when it ends
+constexpr int kDriftRefill = 8;  // idle lanes that trigger a refill while others still walk
+
+// 53-bit uniform from two Philox words, as philox_uniform forms it.
+__device__ inline double drift_uniform(uint32_t hi, uint32_t lo) {
+  return ((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+// Box-Muller: u1 from words 0 and 1, u2 from words 2 and 3 of one Philox call.
+__device__ inline double philox_normal(uint64_t seed, uint64_t draw, uint32_t row,
+                                       uint32_t stream) {
+  const Philox o = philox4x32_10((uint32_t)draw, (uint32_t)(draw >> 32), row, stream,
+                                 (uint32_t)seed, (uint32_t)(seed >> 32));
+  const double u1 = drift_uniform(o.w[0], o.w[1]), u2 = drift_uniform(o.w[2], o.w[3]);
+  return sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);
+}
+
+// The step goes up iff (double)w * 2^-32 < prob_up (generate.py:287 with a
+// 32-bit uniform). Both sides scaled by 2^32 are exact, and for an integer w,
+// w < x iff w < ceil(x): the loop compares integers. prob_up <= 0 or NaN never
+// goes up, prob_up >= 1 always does.
+__device__ inline uint64_t drift_threshold(double prob_up) {
+  if (!(prob_up > 0.0)) return 0;
+  if (prob_up >= 1.0) return (uint64_t)1 << 32;
+  return (uint64_t)ceil(prob_up * 4294967296.0);
+}
+
+// One wave owns draws [blockIdx.x * wave_draws, + wave_draws) of the call.
+// Its lanes take the next draw of that range when theirs has crossed (the
+// range's cursor is wave-uniform; a finished lane's draw is the cursor plus
+// its rank among the idle lanes), so a wave's time is about the mean of its
+// trial lengths and not their maximum. Nothing about a draw depends on the
+// lane or the wave that ran it: its random words are functions of (seed, row,
+// draw index, step index). Each pass of the loop is four steps, one Philox
+// call.
+__global__ __launch_bounds__(kDriftBlock) void sim_drift_kernel(DriftCall C) {
+  const int64_t lo = (int64_t)blockIdx.x * C.wave_draws;
+  const int64_t hi = (C.total - lo < C.wave_draws) ? C.total : lo + C.wave_draws;
+  const uint32_t key0 = (uint32_t)C.seed, key1 = (uint32_t)(C.seed >> 32);
+  int64_t next = lo;
+  uint32_t passes = 0;
+  bool live = false;
+  int64_t e = 0;         // the lane's draw: element of out
+  uint64_t j = 0;        // its index inside the row
+  uint32_t row = 0;      // global row index
+  uint32_t k = 0, nn = kDriftNoSwitch;
+  uint64_t thr = 0, thr_switch = 0;
+  double y = 0.0, a = 0.0, delay = 0.0;
+  for (;;) {
+    const uint64_t idle = __ballot(!live);
+    const int n_idle = __popcll(idle);
+    if (next < hi && (n_idle >= kDriftRefill || n_idle == kDriftBlock)) {
+      if (!live) {
+        const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
+                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+        e = next + rank;
+        if (e < hi) {
+          int64_t r0 = 0, r1 = C.R;  // the last row with off[row] <= e
+          while (r1 - r0 > 1) {
+            const int64_t mid = r0 + ((r1 - r0) >> 1);
+            if (C.off[mid] <= e) r0 = mid;
+            else r1 = mid;
+          }
+          const DriftRow Q = C.rows[r0];
+          j = (uint64_t)(e - C.off[r0]);
+          row = (uint32_t)(C.row0 + r0);
+          a = Q.a;
+          nn = Q.nn;
+          const double u_t = Q.st != 0 ? philox_uniform(C.seed, j, row, 1u) : 0.0;
+          const double u_z = Q.sz != 0 ? philox_uniform(C.seed, j, row, 2u) : 0.0;
+          delay = (Q.t + Q.st * u_t) - Q.st / 2.;         // generate.py:245-246
+          y = ((Q.z + Q.sz * u_z) - Q.sz / 2.) * a;       // generate.py:252-253
+          const double drift = Q.sv != 0 ? Q.v + Q.sv * philox_normal(C.seed, j, row, 3u) : Q.v;
+          thr = drift_threshold(0.5 * (1 + C.scale * drift));  // generate.py:279
+          double drift_switch = 0.0;
+          thr_switch = 0;
+          if (nn != kDriftNoSwitch) {  // generate.py:272-277, 284-286
+            drift_switch = Q.V_switch != 0
+                               ? Q.v_switch + Q.V_switch * philox_normal(C.seed, j, row, 4u)
+                               : Q.v_switch;
+            thr_switch = drift_threshold(0.5 * (1 + C.scale * drift_switch));
+          }
+          k = 0;
+          live = true;
+          if (C.y0) C.y0[e] = y;
+          if (C.delay) C.delay[e] = delay;
+          if (C.drift) C.drift[e] = drift;
+          if (C.drift_switch) C.drift_switch[e] = drift_switch;
+        }
+      }
+      next += n_idle;
+    }
+    if (__ballot(live) == 0) break;
+    ++passes;
+    if (live) {
+      // k is a multiple of 4 here: word k % 4 of stream 16 + k / 4 decides step k
+      const Philox o = philox4x32_10((uint32_t)j, (uint32_t)(j >> 32), row, 16u + (k >> 2), key0,
+                                     key1);
+      bool crossed = false, spent = false;
+      double y2 = 0.0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {  // selects, no branches: a lane that has stopped keeps its state
+        const uint64_t th = k >= nn ? thr_switch : thr;
+        const double yn = y + ((uint64_t)o.w[i] < th ? C.step : -C.step);  // generate.py:287-289
+        const bool outside = yn < 0 || yn > a;                             // generate.py:291
+        const bool cross = live && outside, move = live && !outside;
+        y2 = cross ? yn : y2;
+        crossed = crossed || cross;
+        y = move ? yn : y;
+        k += move ? 1u : 0u;
+        const bool last = move && k == C.max_steps;
+        spent = spent || last;
+        live = move && !last;
+      }
+      if (crossed) {  // generate.py:301-313: y1 = y, the crossing step's index = k
+        const double m = (y2 - y) / C.dt;
+        const double b = y2 - (m * (double)k) * C.dt;
+        const double rt = y2 < 0 ? (0 - b) / m : (a - b) / m;
+        C.out[e] = (rt + delay) * (y2 < 0 ? -1.0 : 1.0);
+        if (C.n_steps) C.n_steps[e] = (int64_t)k + 1;
+      } else if (spent) {
+        C.out[e] = __builtin_nan("");
+        if (C.n_steps) C.n_steps[e] = (int64_t)k;
+      }
+    }
+  }
+  if (C.wave_steps && threadIdx.x == 0) C.wave_steps[blockIdx.x] = 4 * (int64_t)passes;
+}
+
 int sim_blocks_per_row(int64_t m) { return (int)((m + kSimBlock - 1) / kSimBlock); }
 
 }  // namespace
@@ -250,6 +387,13 @@ void launch_sim_draw(const SimTile& T, const SimDraw& D, int64_t first, int64_t 
   if (ndraws <= 0) return;
   hipLaunchKernelGGL(sim_draw_kernel, dim3((unsigned)((ndraws + kSimBlock - 1) / kSimBlock)),
                      dim3(kSimBlock), 0, s, T, D, first, ndraws);
+}
+
+// The caller checks that the wave count fits a grid's x dimension.
+void launch_sim_drift(const DriftCall& C, hipStream_t s) {
+  if (C.total <= 0) return;
+  const int64_t waves = (C.total + C.wave_draws - 1) / C.wave_draws;
+  hipLaunchKernelGGL(sim_drift_kernel, dim3((unsigned)waves), dim3(kDriftBlock), 0, s, C);
 }
 
 }  // namespace wfpt

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/wfpt_amd.h"
@@ -235,6 +236,7 @@ struct wfpt_ctx {
   DevBuf<double> sim_u;
   DevBuf<double> sim_out;
   DevBuf<int64_t> sim_idx;
+  DevBuf<wfpt::DriftRow> drift_rows;  // the diffusion-path simulator's row table
   hipEvent_t sim_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   double sim_ms[4] = {0, 0, 0, 0};  // profiled time by stage: density, scan, normalise, draws
 };
@@ -836,6 +838,7 @@ void wfpt_close(wfpt_ctx* c) {
   c->sim_u.release();
   c->sim_out.release();
   c->sim_idx.release();
+  c->drift_rows.release();
   for (hipEvent_t& ev : c->sim_ev)
     if (ev) (void)hipEventDestroy(ev);
   if (c->comm) (void)ncclCommDestroy(c->comm);
@@ -2998,6 +3001,161 @@ int wfpt_gen_rts_nodes(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_pa
                        double* out) {
   return wfpt_gen_rts_nodes_ex(c, grid, G, rows, R, counts, u_choice, u_delay, seed,
                                workspace_bytes, out, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// Diffusion-path simulator (sim_drift_kernel; hddm/generate.py:208-319)
+
+int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx* c, const wfpt_params* rows, int64_t R,
+                                const double* sw, const int64_t* counts, double dt,
+                                double intra_sv, int64_t max_steps, uint64_t seed, int64_t row0,
+                                int32_t wave_draws, double* out, int64_t* n_unfinished,
+                                double* out_y0, double* out_delay, double* out_drift,
+                                double* out_drift_switch, int64_t* out_n_steps,
+                                int64_t* out_wave_steps) {
+  if (!rows || !counts || !n_unfinished)
+    return fail(WFPT_ERR_ARG, "null pointer (rows / counts / n_unfinished)");
+  if (R < 1) return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: R < 1");
+  if (R >= (int64_t)1 << 31) return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: R must be < 2^31");
+  if (row0 < 0 || row0 >= (int64_t)1 << 31)
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: row0 outside [0, 2^31)");
+  if (!(dt > 0) || !std::isfinite(dt)) return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: dt <= 0");
+  if (!(intra_sv > 0) || !std::isfinite(intra_sv))
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: intra_sv <= 0");
+  if (max_steps < 1 || max_steps > (int64_t)1 << 31)
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: max_steps outside [1, 2^31]");
+  if (wave_draws < 0 || wave_draws % 64 != 0)
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: wave_draws must be a multiple of 64 (0: default)");
+  if (out_wave_steps && wave_draws == 0)
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: out_wave_steps needs an explicit wave_draws");
+  const double root = std::sqrt(dt);
+  const double step = root * intra_sv, scale = root / intra_sv;  // generate.py:258, 279
+  if (!(step > 0) || !std::isfinite(step) || !std::isfinite(scale))
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: sqrt(dt) * intra_sv is not a usable step");
+  std::vector<int64_t> off((size_t)R + 1, 0);
+  for (int64_t r = 0; r < R; ++r) {
+    if (counts[r] < 0)
+      return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: negative count in row " + std::to_string(r));
+    off[r + 1] = off[r] + counts[r];
+  }
+  const int64_t total = off[R];
+  if (!out && total > 0) return fail(WFPT_ERR_ARG, "null pointer (out)");
+  std::vector<wfpt::DriftRow> tab((size_t)R);
+  for (int64_t r = 0; r < R; ++r) {
+    const wfpt_params& P = rows[r];
+    wfpt::DriftRow& Q = tab[r];
+    Q = wfpt::DriftRow{P.v, P.sv, P.a, P.z, P.sz, P.t, P.st, 0.0, 0.0, wfpt::kDriftNoSwitch, 0u};
+    if (sw) {
+      const double nn = std::nearbyint(sw[3 * r + 2] / dt);  // int(round(t_switch / dt))
+      if (!(nn >= 1))
+        return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: t_switch / dt rounds below 1 in row " +
+                                      std::to_string(r));
+      Q.v_switch = sw[3 * r];
+      Q.V_switch = sw[3 * r + 1];
+      // a switch past the step bound is never reached
+      Q.nn = nn < 4294967295.0 ? (uint32_t)nn : wfpt::kDriftNoSwitch - 1;
+    }
+  }
+  if (!c) return fail(WFPT_ERR_ARG, "null pointer (context)");
+  for (int64_t r = 0; r < R; ++r) {
+    const wfpt::DriftRow& Q = tab[r];
+    const bool finite = std::isfinite(Q.v) && std::isfinite(Q.sv) && std::isfinite(Q.a) &&
+                        std::isfinite(Q.z) && std::isfinite(Q.sz) && std::isfinite(Q.t) &&
+                        std::isfinite(Q.st) && std::isfinite(Q.v_switch) &&
+                        std::isfinite(Q.V_switch);
+    if (!finite || !(Q.a > 0) || Q.z - Q.sz / 2. < 0 || Q.z + Q.sz / 2. > 1)
+      return fail(WFPT_ERR_UNSUPPORTED,
+                  "gen_rts_drift_nodes: row " + std::to_string(r) +
+                      " cannot be simulated (a non-finite parameter, a <= 0, or a start "
+                      "point outside [0, 1]); no draws are returned");
+  }
+  if (!wfpt::sim_kernels_linked())
+    return fail(WFPT_ERR_UNSUPPORTED, "this build does not contain the RT sampler kernels");
+  // Draws per wave: one per lane until that gives every SIMD four waves
+  // (1024 SIMDs), then up to 16 per lane, taken in turn as lanes finish
+  // (fewer, longer waves idle less but must still fill the chip).
+  const int64_t wd = wave_draws > 0 ? wave_draws
+                                    : 64 * std::min<int64_t>(16, std::max<int64_t>(1, total / (64 * 4096)));
+  const int64_t waves = (total + wd - 1) / wd;
+  if (waves >= (int64_t)1 << 31)
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: too many draws for one call");
+  *n_unfinished = 0;
+  if (total == 0) return WFPT_OK;
+  WFPT_RANGE("wfpt_gen_rts_drift_nodes");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const bool dbg = out_y0 || out_delay || out_drift || out_drift_switch;
+  HIP_TRY(c->drift_rows.reserve(R));
+  HIP_TRY(c->sim_off.reserve(R + 1));
+  HIP_TRY(c->sim_out.reserve(total));
+  if (dbg) HIP_TRY(c->sim_u.reserve(4 * total));
+  if (out_n_steps || out_wave_steps) HIP_TRY(c->sim_idx.reserve(total + waves));
+  HIP_TRY(hipMemcpyAsync(c->drift_rows.p, tab.data(), R * sizeof(wfpt::DriftRow),
+                         hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->sim_off.p, off.data(), (R + 1) * sizeof(int64_t),
+                         hipMemcpyHostToDevice, c->stream));
+  if (c->profile)
+    for (int k = 0; k < 2; ++k)
+      if (!c->sim_ev[k]) HIP_TRY(hipEventCreate(&c->sim_ev[k]));
+  wfpt::DriftCall C;
+  C.rows = c->drift_rows.p;
+  C.off = c->sim_off.p;
+  C.R = R;
+  C.row0 = row0;
+  C.total = total;
+  C.dt = dt;
+  C.step = step;
+  C.scale = scale;
+  C.max_steps = (uint32_t)max_steps;
+  C.wave_draws = (int32_t)wd;
+  C.seed = seed;
+  C.out = c->sim_out.p;
+  C.y0 = out_y0 ? c->sim_u.p : nullptr;
+  C.delay = out_delay ? c->sim_u.p + total : nullptr;
+  C.drift = out_drift ? c->sim_u.p + 2 * total : nullptr;
+  C.drift_switch = out_drift_switch ? c->sim_u.p + 3 * total : nullptr;
+  C.n_steps = out_n_steps ? c->sim_idx.p : nullptr;
+  C.wave_steps = out_wave_steps ? c->sim_idx.p + total : nullptr;
+  if (c->profile) HIP_TRY(hipEventRecord(c->sim_ev[0], c->stream));
+  wfpt::launch_sim_drift(C, c->stream);
+  HIP_TRY(hipGetLastError());
+  if (c->profile) {
+    HIP_TRY(hipEventRecord(c->sim_ev[1], c->stream));
+    HIP_TRY(hipEventSynchronize(c->sim_ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->sim_ev[0], c->sim_ev[1]));
+    c->k_ms += ms;
+    c->launches += 1;
+  }
+  HIP_TRY(hipMemcpyAsync(out, c->sim_out.p, total * sizeof(double), hipMemcpyDeviceToHost,
+                         c->stream));
+  const std::pair<double*, const double*> copies[] = {
+      {out_y0, C.y0}, {out_delay, C.delay}, {out_drift, C.drift},
+      {out_drift_switch, C.drift_switch}};
+  for (const auto& cp : copies)
+    if (cp.first)
+      HIP_TRY(hipMemcpyAsync(cp.first, cp.second, total * sizeof(double), hipMemcpyDeviceToHost,
+                             c->stream));
+  if (out_n_steps)
+    HIP_TRY(hipMemcpyAsync(out_n_steps, C.n_steps, total * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, c->stream));
+  if (out_wave_steps)
+    HIP_TRY(hipMemcpyAsync(out_wave_steps, C.wave_steps, waves * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int64_t nan = 0;  // only a draw that ran out of steps is NaN
+  for (int64_t i = 0; i < total; ++i) nan += std::isnan(out[i]) ? 1 : 0;
+  *n_unfinished = nan;
+  return WFPT_OK;
+}
+
+int wfpt_gen_rts_drift_nodes(wfpt_ctx* c, const wfpt_params* rows, int64_t R, const double* sw,
+                             const int64_t* counts, double dt, double intra_sv,
+                             int64_t max_steps, uint64_t seed, double* out,
+                             int64_t* n_unfinished) {
+  return wfpt_gen_rts_drift_nodes_ex(c, rows, R, sw, counts, dt, intra_sv, max_steps, seed, 0, 0,
+                                     out, n_unfinished, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr);
 }
 
 int wfpt_profile_stages(wfpt_ctx* c, double stage_ms[4], int reset) {

@@ -511,13 +511,16 @@ class HDDM:
         P[:, :, 7] = self.p_outlier
         return picked, P
 
-    def post_pred_gen(self, samples=500, seed=None, cdf_range=(-5, 5), dt=1e-4):
+    def post_pred_gen(self, samples=500, seed=None, cdf_range=(-5, 5), dt=1e-4, method="cdf"):
         """Posterior predictive data (kabuki.analyze.post_pred_gen over the
         stochastic's random(), hddm/utils.py:384-387): for each of `samples`
         evenly spaced kept sweeps and each observed node, as many RTs as the
         node has trials, drawn at the sweep's parameters by ONE batched
         sampler call (wfpt.gen_rts_from_cdf_nodes with a device seed). The
         draws come from the DDM alone: p_outlier's mixture is not simulated.
+        method='drift' simulates every RT as a diffusion path with time step
+        dt instead (wfpt.gen_rts_from_drift_nodes, generate.py:208-319;
+        cdf_range is not used).
 
         Returns a DataFrame with columns sample (index of the kept sweep), node
         (index into node_keys), rt (signed) and response (1 upper / 0 lower)."""
@@ -527,9 +530,15 @@ class HDDM:
         S = picked.size
         if seed is None:
             seed = int(self.rng.integers(0, 2 ** 63))
-        rts, off = _wfpt.gen_rts_from_cdf_nodes(P.reshape(S * self.n_nodes, 8), np.tile(counts, S),
-                                                cdf_lb=cdf_range[0], cdf_ub=cdf_range[1], dt=dt,
-                                                seed=seed)
+        if method not in ("cdf", "drift"):
+            raise ValueError("method must be 'cdf' or 'drift'")
+        if method == "drift":
+            rts, off = _wfpt.gen_rts_from_drift_nodes(P.reshape(S * self.n_nodes, 8),
+                                                      np.tile(counts, S), dt=dt, seed=seed)
+        else:
+            rts, off = _wfpt.gen_rts_from_cdf_nodes(P.reshape(S * self.n_nodes, 8),
+                                                    np.tile(counts, S), cdf_lb=cdf_range[0],
+                                                    cdf_ub=cdf_range[1], dt=dt, seed=seed)
         per = np.diff(off)
         return pd.DataFrame({"sample": np.repeat(np.repeat(picked, self.n_nodes), per),
                              "node": np.repeat(np.tile(np.arange(self.n_nodes), S), per),

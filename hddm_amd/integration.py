@@ -70,12 +70,32 @@ def _patch(inst, key, target, ours, names):
     return target
 
 
-def install(wfpt_module=None, cdfdif_module=None, likelihoods_module=None, rl=False):
+def _simulated_drift(params, samples=1000, dt=1e-4, intra_sv=1.):
+    """hddm.generate._gen_rts_from_simulated_drift (generate.py:208-319) on the
+    device. The reference also returns every trial's path; those are not
+    produced here: the second element is an empty list."""
+    from . import wfpt as amd_wfpt
+    switch = {k: params[k] for k in ("v_switch", "V_switch", "t_switch") if k in params}
+    rts = amd_wfpt.gen_rts_from_drift(
+        params["v"], params.get("sv", 0), params["a"], params.get("z", .5), params.get("sz", 0),
+        params["t"], params.get("st", 0), 1 if samples is None else samples, dt, intra_sv,
+        **switch)
+    return rts, []
+
+
+def install(wfpt_module=None, cdfdif_module=None, likelihoods_module=None, rl=False,
+            drift=False, generate_module=None):
     """Route HDDM's likelihood and CDF calls to libwfpt_amd.so.
 
     `rl=True` also rebinds the reinforcement-learning likelihoods (RL_PATH)
     that HDDMrl, Hrl and HDDMrlRegressor call (hddm/models/hddm_rl.py:61-73,
     rl.py:145-158); by default they stay the reference's.
+
+    `drift=True` also rebinds `_gen_rts_from_simulated_drift` of the reference's
+    `hddm.generate` (given as `generate_module`, or already imported) to the
+    device's diffusion-path simulator, which `gen_rts(method='drift')` then
+    calls (generate.py:188-189). It returns the RTs without the paths, which is
+    why it is opt-in; by default `generate` is left alone.
 
     `wfpt_module` / `cdfdif_module` default to the already-imported (or
     importable) reference extensions `wfpt` and `cdfdif_wrapper`; when one is
@@ -105,4 +125,10 @@ def install(wfpt_module=None, cdfdif_module=None, likelihoods_module=None, rl=Fa
         if hasattr(lk, "Wfpt"):
             inst._attrs.append((lk, "Wfpt", lk.Wfpt))
             lk.Wfpt = amd_lk.generate_wfpt_stochastic_class()
+    if drift:
+        gen = generate_module if generate_module is not None else sys.modules.get("hddm.generate")
+        if gen is not None:
+            name = "_gen_rts_from_simulated_drift"
+            inst._attrs.append((gen, name, getattr(gen, name, _MISSING)))
+            setattr(gen, name, _simulated_drift)
     return inst

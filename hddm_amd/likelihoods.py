@@ -136,8 +136,10 @@ def gen_random(parents, size, sampling_method="cdf", cdf_range=(-5, 5), sampling
     (generate.py:134-205, structured=True) followed by hddm.utils.flip_errors
     (utils.py:15-37), i.e. a DataFrame with signed 'rt' and 'response'
     (1 upper / 0 lower). method 'cdf' samples on the MI355X density grid
-    (gen_rts_from_cdf); the host-only simulators ('drift', 'cdf_py') are the
-    reference's own and are delegated to it when it is importable."""
+    (gen_rts_from_cdf) and method 'drift' simulates the diffusion paths on the
+    device (gen_rts_from_drift, generate.py:208-319; it alone honours the
+    parents v_switch / V_switch / t_switch); the host-only simulator 'cdf_py'
+    is the reference's own and is delegated to it when it is importable."""
     import pandas as pd
     p = {k: parents[k] for k in ("v", "sv", "a", "z", "sz", "t", "st") if k in parents}
     for k in ("sv", "sz", "st"):        # generate.py:169-177 defaults
@@ -145,13 +147,18 @@ def gen_random(parents, size, sampling_method="cdf", cdf_range=(-5, 5), sampling
     p.setdefault("z", .5)
     if isinstance(size, tuple):         # generate.py:180-184 (PyMC shapes)
         size = 1 if size == () else size[0]
-    if sampling_method != "cdf":
+    if sampling_method == "drift":
+        switch = {k: parents[k] for k in ("v_switch", "V_switch", "t_switch") if k in parents}
+        rts = _wfpt.gen_rts_from_drift(p["v"], p["sv"], p["a"], p["z"], p["sz"], p["t"], p["st"],
+                                       size, sampling_dt, **switch)
+    elif sampling_method != "cdf":
         import hddm  # reference simulators (not on the accelerated path)
         return hddm.utils.flip_errors(hddm.generate.gen_rts(
             method=sampling_method, size=size, dt=sampling_dt, range_=cdf_range,
             structured=True, **parents))
-    rts = _wfpt.gen_rts_from_cdf(p["v"], p["sv"], p["a"], p["z"], p["sz"], p["t"], p["st"],
-                                 size, cdf_range[0], cdf_range[1], sampling_dt)
+    else:
+        rts = _wfpt.gen_rts_from_cdf(p["v"], p["sv"], p["a"], p["z"], p["sz"], p["t"], p["st"],
+                                     size, cdf_range[0], cdf_range[1], sampling_dt)
     # generate.py:200-203 then utils.py:27-35: |rt| with response, lower flipped back
     response = np.where(rts < 0, 0.0, 1.0)
     rt = np.abs(rts)

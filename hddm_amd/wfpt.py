@@ -21,7 +21,10 @@ Additions for resident data (the reference re-reads host memory every call):
 signature minus `x`. `Dataset(rt, node_id=...)` + `wiener_like_nodes` scores
 many PyMC nodes in one launch. `gen_rts_from_cdf_nodes` draws RTs for many
 parameter rows in one call, grid, CDF and search on the device (posterior
-predictive data sets: HDDM.post_pred_gen). `RegDataset(rt, design)` keeps a
+predictive data sets: HDDM.post_pred_gen). `gen_rts_from_drift_nodes` /
+`gen_rts_from_drift` are the reference's 'drift' sampling method
+(hddm/generate.py:208-319: every RT a simulated diffusion path, with the
+in-trial drift switch) on the device. `RegDataset(rt, design)` keeps a
 design matrix resident and forms HDDMRegressor's trial-wise parameters
 link(design . coefficients) on the device (hddm_regression.py:26-36).
 """
@@ -32,7 +35,7 @@ import numpy as np
 from . import _lib
 
 __all__ = ["pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "gen_rts_from_cdf",
-           "gen_rts_from_cdf_nodes", "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl",
+           "gen_rts_from_cdf_nodes", "gen_rts_from_drift_nodes", "gen_rts_from_drift", "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl",
            "wiener_like_multi_rlddm", "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_terms",
            "wiener_like_rl_terms", "wiener_like_multi_rlddm_terms", "RegDataset"]
 
@@ -266,6 +269,125 @@ def gen_rts_from_cdf_nodes(params, samples, cdf_lb=-6, cdf_ub=6, dt=1e-2, u=None
         raise RuntimeError("wfpt_amd: " + _lib.wfpt_last_error().decode(errors="replace"))
     _lib.check(rc)
     return (out, offsets, dbg) if return_debug else (out, offsets)
+
+
+def gen_rts_from_drift_nodes(params, samples, dt=1e-4, intra_sv=1., seed=None, switch=None,
+                             max_t=20., unfinished='raise', return_debug=False, row0=0,
+                             wave_draws=None):
+    """_gen_rts_from_simulated_drift (hddm/generate.py:208-319), the 'drift'
+    sampling method, for R parameter rows in one call on the GPU
+    (wfpt_gen_rts_drift_nodes): every draw is one +-sqrt(dt) * intra_sv random
+    walk between the boundaries with the crossing time interpolated, in the
+    reference's arithmetic.
+
+    params: (R, 7) or (R, 8) rows of v, sv, a, z, sz, t, st[, p_outlier]
+    (p_outlier is ignored). samples: draws per row, an int or R ints. switch:
+    None, or (R, 3) rows of v_switch, V_switch, t_switch: from step
+    round(t_switch / dt) on the walk uses the drift v_switch (+ V_switch times a
+    normal draw when V_switch != 0). Returns (rts, offsets): row r's draws are
+    rts[offsets[r]:offsets[r + 1]].
+
+    seed: the device's Philox4x32-10 streams; a draw depends on the seed, its
+    row's index and its index in the row only. None takes a seed from NumPy's
+    global RNG, so np.random.seed makes the call reproducible. A walk is cut
+    after ceil(max_t / dt) steps: unfinished='raise' raises RuntimeError with
+    the number of such draws, 'nan' returns them as NaN.
+
+    return_debug: also a dict of each draw's start point `y0`, `delay`,
+    `drift`, `drift_switch` and steps taken `n_steps`. row0 is added to the
+    row index of the random streams (a slice of a larger table draws what it
+    draws there). wave_draws: draws handed to one wave (a multiple of 64; a
+    measurement knob that changes no value); with return_debug the dict then
+    also holds `wave_steps`, the steps each wave's loop ran.
+    """
+    pm = np.asarray(params, dtype=np.float64)
+    if pm.ndim != 2 or pm.shape[1] not in (7, 8) or pm.shape[0] < 1:
+        raise ValueError("params must have shape (R, 7) or (R, 8), R >= 1")
+    R = pm.shape[0]
+    table = np.zeros((R, 8))
+    table[:, :pm.shape[1]] = pm
+    cnt = np.asarray(samples)
+    if cnt.ndim == 0:
+        cnt = np.full(R, int(cnt))
+    if cnt.shape != (R,) or not np.issubdtype(cnt.dtype, np.integer):
+        raise ValueError(f"samples must be an int or {R} ints")
+    cnt = np.ascontiguousarray(cnt, dtype=np.int64)
+    if np.any(cnt < 0):
+        raise ValueError("samples must be non-negative")
+    dt, intra_sv = float(dt), float(intra_sv)
+    if not (dt > 0 and np.isfinite(dt)):
+        raise ValueError("dt must be positive")
+    if not (intra_sv > 0 and np.isfinite(intra_sv)):
+        raise ValueError("intra_sv must be positive")
+    if not max_t > 0:
+        raise ValueError("max_t must be positive")
+    max_steps = int(np.ceil(float(max_t) / dt))
+    if not 1 <= max_steps <= 2 ** 31:
+        raise ValueError("ceil(max_t / dt) must lie in [1, 2^31]")
+    if unfinished not in ("raise", "nan"):
+        raise ValueError("unfinished must be 'raise' or 'nan'")
+    sw = None
+    if switch is not None:
+        sw = np.ascontiguousarray(switch, dtype=np.float64)
+        if sw.shape != (R, 3):
+            raise ValueError(f"switch must have shape ({R}, 3): v_switch, V_switch, t_switch")
+        if not np.all(np.round(sw[:, 2] / dt) >= 1):  # generate.py:237-239
+            raise ValueError("t_switch / dt must round to at least one step")
+    row0 = int(row0)
+    if not 0 <= row0 < 2 ** 31:
+        raise ValueError("row0 must lie in [0, 2^31)")
+    wd = 0 if wave_draws is None else int(wave_draws)
+    if wd < 0 or wd % 64:
+        raise ValueError("wave_draws must be a positive multiple of 64")
+    offsets = np.zeros(R + 1, dtype=np.int64)
+    np.cumsum(cnt, out=offsets[1:])
+    total = int(offsets[R])
+    if seed is None:
+        lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
+        seed = int(lo) | (int(hi) << 32)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    c = _lib.context()
+    out = np.empty(total, dtype=np.float64)
+    nun = ctypes.c_int64()
+    psw = _lib.dptr(sw) if sw is not None else None
+    if return_debug or row0 or wd:
+        dbg = {k: np.empty(total) for k in ("y0", "delay", "drift", "drift_switch")}
+        dbg["n_steps"] = np.empty(total, dtype=np.int64)
+        if wd:
+            dbg["wave_steps"] = np.empty(-(-total // wd), dtype=np.int64)
+        rc = _lib.wfpt_gen_rts_drift_nodes_ex(
+            c.handle, table.ctypes.data_as(_lib._PP), R, psw, _i64ptr(cnt), dt, intra_sv,
+            max_steps, seed, row0, wd, _lib.dptr(out), ctypes.byref(nun), _lib.dptr(dbg["y0"]),
+            _lib.dptr(dbg["delay"]), _lib.dptr(dbg["drift"]), _lib.dptr(dbg["drift_switch"]),
+            _i64ptr(dbg["n_steps"]), _i64ptr(dbg["wave_steps"]) if wd else None)
+    else:
+        rc = _lib.wfpt_gen_rts_drift_nodes(c.handle, table.ctypes.data_as(_lib._PP), R, psw,
+                                           _i64ptr(cnt), dt, intra_sv, max_steps, seed,
+                                           _lib.dptr(out), ctypes.byref(nun))
+    if rc == 4 and b"cannot be simulated" in _lib.wfpt_last_error():
+        raise RuntimeError("wfpt_amd: " + _lib.wfpt_last_error().decode(errors="replace"))
+    _lib.check(rc)
+    if nun.value and unfinished == "raise":
+        raise RuntimeError(f"wfpt_amd: {nun.value} of {total} draws had not crossed a boundary "
+                           f"after {max_steps} steps (max_t = {max_t})")
+    return (out, offsets, dbg) if return_debug else (out, offsets)
+
+
+def gen_rts_from_drift(v, sv, a, z, sz, t, st, samples=1000, dt=1e-4, intra_sv=1., seed=None,
+                       **switch):
+    """generate.py:208-319 for one parameter set: `samples` signed RTs of the
+    simulated diffusion path. switch: v_switch, t_switch and optionally
+    V_switch, the reference's in-trial change of the drift rate."""
+    unknown = set(switch) - {"v_switch", "V_switch", "t_switch"}
+    if unknown:
+        raise TypeError(f"unexpected keyword arguments {sorted(unknown)}")
+    sw = None
+    if "v_switch" in switch:
+        if "t_switch" not in switch:
+            raise ValueError("v_switch needs t_switch")
+        sw = [[switch["v_switch"], switch.get("V_switch", 0.0), switch["t_switch"]]]
+    return gen_rts_from_drift_nodes([[v, sv, a, z, sz, t, st]], int(samples), dt, intra_sv, seed,
+                                    switch=sw)[0]
 
 
 class Dataset:

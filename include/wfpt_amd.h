@@ -21,6 +21,8 @@
  *                             src/cdfdif_wrapper.pyx:16-53, src/cdfdif.c:59-221
  *   wfpt_gen_rts_nodes     <- wfpt.gen_rts_from_cdf, one call for many rows
  *                             src/wfpt.pyx:323-354
+ *   wfpt_gen_rts_drift_nodes <- generate._gen_rts_from_simulated_drift, many rows
+ *                             hddm/generate.py:208-319
  * The Python binding that keeps the reference signatures is
  * hddm_amd/wfpt.py (ctypes); INTEGRATION.md shows the drop-in.
  */
@@ -465,6 +467,56 @@ int wfpt_gen_rts_nodes_ex(wfpt_ctx *ctx, const double *grid, int64_t G, const wf
                           const double *u_delay, uint64_t seed, int64_t workspace_bytes,
                           double *out, double *out_pdf, double *out_cdf, int64_t *out_idx,
                           double *out_u_choice, double *out_u_delay);
+
+/* _gen_rts_from_simulated_drift (hddm/generate.py:208-319), the 'drift'
+ * sampling method, for R parameter rows in one call: every draw is one
+ * +-sqrt(dt) intra_sv random walk from y0 = ((z + sz u_z) - sz / 2) a between 0
+ * and a, going up with probability 0.5 (1 + sqrt(dt) / intra_sv drift), until
+ * the first step k whose position y2 is < 0 or > a; the crossing time is
+ * interpolated on the last segment (m = (y2 - y1) / dt, b = y2 - (m k) dt, rt
+ * = ((y2 < 0 ? 0 : a) - b) / m) and the draw is (rt + delay) sign, delay = (t +
+ * st u_t) - st / 2. drift = v, or v + sv n when sv != 0. The arithmetic is the
+ * reference's, operation for operation.
+ *   rows      R >= 1 parameter rows (p_outlier ignored)
+ *   sw        NULL, or R triples {v_switch, V_switch, t_switch}: steps k >=
+ *             nn = round(t_switch / dt) (half to even; >= 1) use the drift
+ *             v_switch, or v_switch + V_switch n' when V_switch != 0
+ *   counts    R draws per row, >= 0
+ *   max_steps 1 .. 2^31: a draw that has not crossed after max_steps steps is
+ *             NaN; *n_unfinished is the number of such draws
+ *   out       sum(counts) signed RTs, row after row
+ * Random numbers: Philox4x32-10 with the key {seed lo, seed hi} at counter
+ * {draw lo, draw hi, row, stream}, draw = the index inside the row. Stream 1:
+ * u_t, stream 2: u_z (53-bit uniforms as in wfpt_gen_rts_nodes; stream 0 stays
+ * that sampler's choice); stream 3: n = sqrt(-2 log(1 - u1)) cos(2 pi u2) with
+ * u1 from words 0, 1 and u2 from words 2, 3; stream 4: n' likewise; stream 16 +
+ * k / 4: word k % 4 decides step k, up iff w 2^-32 < the probability. A draw's
+ * value therefore depends on (seed, row, draw) and the row's parameters only.
+ * WFPT_ERR_ARG before any device work: null pointers, dt <= 0, intra_sv <= 0,
+ * a negative count, max_steps out of range, round(t_switch / dt) < 1.
+ * WFPT_ERR_UNSUPPORTED, naming the first such row, also before any device
+ * work: a non-finite parameter, a <= 0, z - sz / 2 < 0 or z + sz / 2 > 1. */
+int wfpt_gen_rts_drift_nodes(wfpt_ctx *ctx, const wfpt_params *rows, int64_t R, const double *sw,
+                             const int64_t *counts, double dt, double intra_sv,
+                             int64_t max_steps, uint64_t seed, double *out,
+                             int64_t *n_unfinished);
+/* As wfpt_gen_rts_drift_nodes (generate.py:208-319), for tests and
+ * measurements. row0: added to the row index in the Philox counter (a slice
+ * of a larger table draws what it draws there). wave_draws: draws handed to
+ * one wave, a multiple of 64 (0: the library's choice; 64: one draw per lane;
+ * more: lanes take the next draw as they finish) -- it changes no value. Per
+ * draw, each nullable: out_y0 the start point, out_delay, out_drift,
+ * out_drift_switch (0 without a switch), out_n_steps the steps taken (the
+ * crossing step's index + 1, or max_steps). out_wave_steps
+ * [ceil(sum(counts) / wave_draws), wave_draws > 0]: the steps each wave's loop
+ * ran. */
+int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx *ctx, const wfpt_params *rows, int64_t R,
+                                const double *sw, const int64_t *counts, double dt,
+                                double intra_sv, int64_t max_steps, uint64_t seed, int64_t row0,
+                                int32_t wave_draws, double *out, int64_t *n_unfinished,
+                                double *out_y0, double *out_delay, double *out_drift,
+                                double *out_drift_switch, int64_t *out_n_steps,
+                                int64_t *out_wave_steps);
 
 /* ---- measurement -------------------------------------------------------- */
 /* Under WFPT_PROF_EVENTS: device milliseconds of the RT sampler's stages
