@@ -10,6 +10,11 @@ package (hddm_amd) never imports it; it fails loudly without its HIP library.
 Parity pins (tests/test_oracle.py): bit-exact vs oracle/_ref (the reference's
 own kernels compiled by oracle/build_ref.py) on branch-covering vectors, and the
 20 Navarro-Fuss MATLAB tuples of hddm/tests/matlab_values.py to 1e-9.
+
+The DMAT CDF (oracle/cdfdif_oracle.c) also comes as a probe, `cdf_probe` (the
+series cap as a parameter; per trial the branch, each series' stop index and
+the scale S of the output), and in long double, `dmat_cdf_array_ld` (the same
+source, summing the terms the double run summed): tests/test_cdfdif_tiers.py.
 """
 import ctypes
 import os
@@ -22,11 +27,25 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liboracle_wfpt.so")
 SRC = os.path.join(HERE, "wfpt_oracle.c")
 SRC_CDF = os.path.join(HERE, "cdfdif_oracle.c")
+SRC_CDF_LD = os.path.join(HERE, "cdfdif_oracle_ld.c")  # the same source in long double
 
 _D = ctypes.c_double
 _I = ctypes.c_int
 _I64 = ctypes.c_int64
 _PD = ctypes.POINTER(ctypes.c_double)
+
+CDF_NSTOP = 43        # cd_record.stop slots (oracle/cdfdif_oracle.c)
+CDF_SLOT_ZERO = 36    # zero-drift series of node m at 36 + m; (m, i) at m * 6 + i
+CDF_SLOT_BEYOND = 42  # the series beyond the Ter window
+CDF_VMAX = 5000       # the reference's series cap; as a stop index: never converged
+
+
+class _CdfRecord(ctypes.Structure):
+    _fields_ = [("branch", _I), ("stop", _I * CDF_NSTOP)]
+
+
+class _CdfProbe(ctypes.Structure):
+    _fields_ = [("S", _D), ("prob", _D), ("rec", _CdfRecord)]
 
 
 def build(force=False):
@@ -34,10 +53,11 @@ def build(force=False):
     os.makedirs(LIBDIR, exist_ok=True)
     hdr = os.path.join(HERE, "wfpt_oracle.h")
     if (not force and os.path.exists(LIB)
-            and all(os.path.getmtime(LIB) > os.path.getmtime(f) for f in (SRC, SRC_CDF, hdr))):
+            and all(os.path.getmtime(LIB) > os.path.getmtime(f)
+                    for f in (SRC, SRC_CDF, SRC_CDF_LD, hdr))):
         return LIB
     subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-fPIC",
-                    "-shared", "-o", LIB, SRC, SRC_CDF, "-lm"], check=True)
+                    "-shared", "-o", LIB, SRC, SRC_CDF, SRC_CDF_LD, "-lm"], check=True)
     return LIB
 
 
@@ -77,6 +97,16 @@ def lib():
         L.oracle_dmat_cdf_array.argtypes = [_PD, _I64] + [_D] * 9 + [_PD]
         L.oracle_dmat_cdf_array_omp.restype = _I
         L.oracle_dmat_cdf_array_omp.argtypes = [_PD, _I64] + [_D] * 9 + [_PD, _I]
+        L.oracle_cdfdif_probe.restype = _D
+        L.oracle_cdfdif_probe.argtypes = [_D, _I, _PD, _I, ctypes.POINTER(_CdfProbe)]
+        L.oracle_cdfdif_replay.restype = _D
+        L.oracle_cdfdif_replay.argtypes = [_D, _I, _PD, _I, ctypes.POINTER(_CdfProbe)]
+        L.oracle_dmat_cdf_probe_array.restype = _I
+        L.oracle_dmat_cdf_probe_array.argtypes = [_PD, _I64] + [_D] * 9 + [_I, _PD, _PD, _PD,
+                                                                           ctypes.c_void_p]
+        L.oracle_dmat_cdf_array_ld.restype = _I
+        L.oracle_dmat_cdf_array_ld.argtypes = [_PD, _I64] + [_D] * 9 + [_I, ctypes.c_void_p,
+                                                                        ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -172,6 +202,80 @@ def dmat_cdf_array(x, v, sv, a, z, sz, t, st, p_outlier, w_outlier, n_threads=No
     if rc < 0:
         raise ValueError("at least one of the parameters is out of the support")
     return out
+
+
+class CdfProbe:
+    """What oracle_dmat_cdf_probe_array returns for x[n]: `out` the wrapper's
+    outputs, `F` cdfdif's values, `S` the scale of each output (the sum of the
+    absolute values of every addend that enters it, after its multipliers),
+    `branch` (0 below the Ter window, 1 beyond it, 2 inside it) and `stop`
+    [n, 43]: the index of the last term each series added (window series
+    (m, i) at m * 6 + i, zero-drift series of node m at 36 + m, the series
+    beyond the window at 42; 5000 = never converged, -1 = did not run)."""
+
+    def __init__(self, vcap, out, F, S, rec):
+        self.vcap, self.out, self.F, self.S, self.rec = vcap, out, F, S, rec
+        self.branch = rec["branch"]
+        self.stop = rec["stop"]
+
+    @property
+    def longest(self):
+        """The largest stop index of each trial (-1 where no series ran)."""
+        return self.stop.max(axis=1)
+
+
+_CDF_REC = np.dtype([("branch", np.int32), ("stop", np.int32, (CDF_NSTOP,))])
+assert _CDF_REC.itemsize == ctypes.sizeof(_CdfRecord)
+
+
+def cdf_probe(x, v, sv, a, z, sz, t, st, p_outlier, w_outlier, vcap=CDF_VMAX):
+    """dmat_cdf_array with the series cap as a parameter (vcap = 5000: the
+    reference, bit for bit), returning a CdfProbe."""
+    x, px = _arr(x)
+    out, F, S = np.empty_like(x), np.empty_like(x), np.empty_like(x)
+    rec = np.zeros(x.size, dtype=_CDF_REC)
+    rc = lib().oracle_dmat_cdf_probe_array(px, x.size, v, sv, a, z, sz, t, st, p_outlier,
+                                           w_outlier, int(vcap), out.ctypes.data_as(_PD),
+                                           F.ctypes.data_as(_PD), S.ctypes.data_as(_PD),
+                                           rec.ctypes.data)
+    if rc < 0:
+        raise ValueError("at least one of the parameters is out of the support")
+    return CdfProbe(int(vcap), out, F, S, rec)
+
+
+def dmat_cdf_array_ld(x, v, sv, a, z, sz, t, st, p_outlier, w_outlier, probe=None):
+    """dmat_cdf_array in long double (x86-64 80-bit; np.longdouble): the same
+    source, formulae and order, summing exactly the terms that the double run
+    `probe` (default: cdf_probe at the reference's cap) summed, on its branch,
+    with no convergence test of its own."""
+    if np.finfo(np.longdouble).nmant < 63:
+        raise RuntimeError("np.longdouble is not the 80-bit extended format here")
+    x, px = _arr(x)
+    if probe is None:
+        probe = cdf_probe(x, v, sv, a, z, sz, t, st, p_outlier, w_outlier)
+    rec = np.ascontiguousarray(probe.rec)
+    assert rec.size == x.size
+    out = np.empty(x.size, dtype=np.longdouble)
+    rc = lib().oracle_dmat_cdf_array_ld(px, x.size, v, sv, a, z, sz, t, st, p_outlier, w_outlier,
+                                        probe.vcap, rec.ctypes.data, out.ctypes.data)
+    if rc < 0:
+        raise ValueError("at least one of the parameters is out of the support")
+    return out
+
+
+def cdfdif_probe(t, x, par, vcap=CDF_VMAX, replay=None):
+    """One cdfdif(t, x, par) call through the probe: (F, S, prob, branch,
+    stop[43]). replay = (branch, stop) sums those terms without testing."""
+    par, pp = _arr(par)
+    pr = _CdfProbe()
+    if replay is None:
+        F = lib().oracle_cdfdif_probe(float(t), int(x), pp, int(vcap), ctypes.byref(pr))
+    else:
+        pr.rec.branch = int(replay[0])
+        for k, s in enumerate(replay[1]):
+            pr.rec.stop[k] = int(s)
+        F = lib().oracle_cdfdif_replay(float(t), int(x), pp, int(vcap), ctypes.byref(pr))
+    return F, pr.S, pr.prob, pr.rec.branch, np.array(pr.rec.stop[:], dtype=np.int32)
 
 
 def count_evals(x, v, sv, a, z, sz, t, st, err=1e-4, n_st=2, n_sz=2, use_adaptive=1,

@@ -10,6 +10,15 @@ Rows cover every branch of cdfdif (src/cdfdif.c): t below the Ter window
 wrapper's sz = st = 0 substitution (cdfdif_wrapper.pyx:38-41, HDDM's default
 model); the outlier mixture (:11-12, :51).
 
+Branches of the reference, not tiers of the kernels: every row has a <= 2 and
+no trial lies within 1e-4 of the window edge, so the series beyond the window
+stops by v ~ 377 and the window series by v ~ 136. These fixtures reach the
+quad pass, the wave pass's first rounds and the window tables below 512; the
+hand-offs, the terms past the per-call tables (v >= 512), the 8-term tail
+round, rows with some drift nodes at zero and others not, and the launch
+geometry are covered by tests/test_cdfdif_tiers.py, whose inputs are
+constructed against oracle/cdfdif_oracle.c.
+
 Usage: python tests/golden/make_golden_cdfdif.py [--reference /root/reference]
 """
 import argparse
