@@ -1,0 +1,287 @@
+// capi_reg.cpp — the regression likelihoods of the C ABI
+// (hddm/models/hddm_regression.py:26-36 into wfpt.pyx:244-274;
+// reg_kernels.hip).
+#include "capi_internal.hpp"
+#include "capi_layout.hpp"
+#include "reg_internal.h"
+#include "rl_internal.h"  // kRlNodeMax: the per-group sum is the RL unit's launch_rl_node_sum
+
+using namespace wfpt::capi;
+
+// The fixed inputs of a regression likelihood, resident: signed RTs and the
+// design matrix, group-major (reg_layout_host).
+#pragma GCC visibility push(hidden)
+struct wfpt_reg_ds : DsBase {
+  int64_t n = 0;
+  int32_t C = 0;
+  int32_t n_groups = 1;     // 1 without group ids
+  DevBuf<double> x;         // [n] signed RTs, stored order (+-999 kept: a missing response)
+  DevBuf<double> X;         // [C * n] column c at X + c * n, stored order
+  DevBuf<int32_t> group;    // [n] group of a stored trial (null without group ids)
+  DevBuf<int64_t> off;      // [n_groups + 1] stored range of each group
+  DevBuf<int64_t> caller;   // [n] the caller's index of a stored trial (null: identity)
+  std::vector<int64_t> off_host;
+  std::vector<int64_t> caller_host;  // empty: identity
+  int64_t group_max = 0;    // most trials in one group
+  void free_device() override { release_all(x, X, group, off, caller); }
+};
+#pragma GCC visibility pop
+
+namespace wfpt {
+namespace capi {
+
+RegHostLayout reg_layout_host(const double* rt, int64_t n, const double* X, int32_t C,
+                              const int32_t* group_id, int32_t n_groups) {
+  RegHostLayout H;
+  const int32_t G = group_id ? n_groups : 1;
+  for (int64_t i = 0; group_id && i < n; ++i)
+    if (group_id[i] < 0 || group_id[i] >= G) {
+      H.rc = WFPT_ERR_ARG;
+      H.msg = "group id out of range at trial " + std::to_string(i);
+      return H;
+    }
+  std::vector<int64_t>& idx = H.caller;
+  idx = std::vector<int64_t>(n);
+  for (int64_t i = 0; i < n; ++i) idx[i] = i;
+  if (group_id) {
+    std::stable_sort(idx.begin(), idx.end(),
+                     [&](int64_t a, int64_t b) { return group_id[a] < group_id[b]; });
+    for (int64_t i = 0; i < n && H.identity; ++i) H.identity = idx[i] == i;
+  }
+  H.x = std::vector<double>(n);
+  H.X = std::vector<double>((size_t)C * n);
+  H.group = std::vector<int32_t>(group_id ? n : 0);
+  H.off = std::vector<int64_t>(G + 1, 0);
+  for (int64_t j = 0; j < n; ++j) {
+    const int64_t src = idx[j];
+    H.x[j] = rt[src];
+    for (int32_t col = 0; col < C; ++col) H.X[(size_t)col * n + j] = X[(size_t)src * C + col];
+    const int32_t g = group_id ? group_id[src] : 0;
+    if (group_id) H.group[j] = g;
+    H.off[g + 1]++;
+  }
+  for (int32_t g = 0; g < G; ++g) {
+    H.group_max = std::max(H.group_max, H.off[g + 1]);
+    H.off[g + 1] += H.off[g];
+  }
+  return H;
+}
+
+}  // namespace capi
+}  // namespace wfpt
+
+namespace {
+
+// The checks of a term list that need no data set: parameter 0..6, each named
+// once, a known link, ncol >= 1, col0 >= 0.
+int reg_check_terms(const wfpt_reg_term* terms, int32_t n_terms) {
+  if (n_terms < 0 || n_terms > wfpt::kRegMaxTerms)
+    return fail(WFPT_ERR_ARG, "n_terms must be 0..7 (one term per parameter)");
+  if (n_terms > 0 && !terms) return fail(WFPT_ERR_ARG, "null pointer (terms)");
+  unsigned seen = 0;
+  for (int32_t k = 0; k < n_terms; ++k) {
+    const wfpt_reg_term& T = terms[k];
+    const std::string at = " (term " + std::to_string(k) + ")";
+    if (T.param < 0 || T.param > 6)
+      return fail(WFPT_ERR_ARG, "term parameter outside 0..6 (v, sv, a, z, sz, t, st)" + at);
+    if (seen & (1u << T.param)) return fail(WFPT_ERR_ARG, "a parameter is named twice" + at);
+    seen |= 1u << T.param;
+    if (T.link != WFPT_LINK_IDENTITY && T.link != WFPT_LINK_EXP && T.link != WFPT_LINK_INVLOGIT)
+      return fail(WFPT_ERR_ARG, "unknown link" + at);
+    if (T.ncol < 1) return fail(WFPT_ERR_ARG, "ncol < 1" + at);
+    if (T.col0 < 0) return fail(WFPT_ERR_ARG, "column range outside [0, C)" + at);
+  }
+  return WFPT_OK;
+}
+
+// The rest of an entry's checks, still before any device work.
+int reg_check_call(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                   int32_t n_terms) {
+  if (d->ctx != c) return fail(WFPT_ERR_ARG, "regression dataset belongs to another context");
+  for (int32_t k = 0; k < n_terms; ++k)
+    if ((int64_t)terms[k].col0 + terms[k].ncol > d->C)
+      return fail(WFPT_ERR_ARG,
+                  "column range outside [0, C) (term " + std::to_string(k) + ")");
+  return WFPT_OK;
+}
+
+// Uploads the call's coefficient rows, opens the profile bracket and launches
+// reg_fill_kernel: term k's predictions into c->reg.arr[k n ..], the fields of
+// `expand` after them. by_group: coefficients and rows are read through the
+// trial's group, else row 0 serves every trial.
+int reg_fill(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms, int32_t n_terms,
+             const double* coef, int32_t rows, bool by_group, int expand, bool want_pred) {
+  int slots = n_terms;
+  for (int f = 0; f < 7; ++f) slots += (expand >> f) & 1;
+  HIP_TRY(c->reg.arr.reserve(std::max<int64_t>((int64_t)slots * d->n, 1)));
+  HIP_TRY(c->reg.coef.reserve(std::max<int64_t>((int64_t)rows * d->C, 1)));
+  if (want_pred) HIP_TRY(c->reg.pred.reserve(std::max<int64_t>((int64_t)n_terms * d->n, 1)));
+  HIP_TRY(hipMemcpyAsync(c->reg.coef.p, coef, (size_t)rows * d->C * sizeof(double),
+                         hipMemcpyHostToDevice, c->stream));
+  if (c->count) HIP_TRY(hipMemsetAsync(c->evals.p, 0, sizeof(unsigned long long), c->stream));
+  if (c->profile) HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  wfpt::RegFill F;
+  F.n = d->n;
+  F.C = d->C;
+  F.n_terms = n_terms;
+  F.X = d->X.p;
+  F.group = by_group ? d->group.p : nullptr;
+  F.coef = c->reg.coef.p;
+  F.P = expand ? c->reg.par.p : nullptr;
+  F.expand = expand;
+  F.arr = c->reg.arr.p;
+  F.pred_in = want_pred ? c->reg.pred.p : nullptr;
+  F.caller = d->caller.p;
+  for (int k = 0; k < wfpt::kRegMaxTerms; ++k)
+    F.term[k] = k < n_terms ? wfpt::RegTerm{terms[k].param, terms[k].link, terms[k].col0,
+                                            terms[k].ncol}
+                            : wfpt::RegTerm{0, 0, 0, 0};
+  wfpt::launch_reg_fill(F, c->stream);
+  HIP_TRY(hipGetLastError());
+  return WFPT_OK;
+}
+
+// The _ex outputs of a finished call, in the caller's order.
+int reg_outputs(wfpt_ctx* c, const wfpt_reg_ds* d, int32_t n_terms, double* out_trial,
+                double* out_pred) {
+  if (out_trial && d->n > 0) {
+    if (d->caller_host.empty()) {
+      HIP_TRY(hipMemcpy(out_trial, c->lp.p, d->n * sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+      std::vector<double> h(d->n);
+      HIP_TRY(hipMemcpy(h.data(), c->lp.p, d->n * sizeof(double), hipMemcpyDeviceToHost));
+      for (int64_t i = 0; i < d->n; ++i) out_trial[d->caller_host[i]] = h[i];
+    }
+  }
+  if (out_pred && d->n > 0 && n_terms > 0)
+    HIP_TRY(hipMemcpy(out_pred, c->reg.pred.p, (size_t)n_terms * d->n * sizeof(double),
+                      hipMemcpyDeviceToHost));
+  return WFPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wfpt_reg_dataset_create(wfpt_ctx* c, const double* rt, int64_t n, const double* X, int32_t C,
+                            const int32_t* group_id, int32_t n_groups, wfpt_reg_ds** out) {
+  if (!c || !out) return fail(WFPT_ERR_ARG, "null pointer");
+  if (n < 0) return fail(WFPT_ERR_ARG, "n < 0");
+  if (C < 1) return fail(WFPT_ERR_ARG, "the design matrix needs at least one column");
+  if (n > 0 && (!rt || !X)) return fail(WFPT_ERR_ARG, "null rt / design matrix");
+  if (group_id && n_groups <= 0) return fail(WFPT_ERR_ARG, "group ids need n_groups > 0");
+  RegHostLayout H = reg_layout_host(rt, n, X, C, group_id, n_groups);
+  if (H.rc) return fail(H.rc, H.msg);
+  WFPT_RANGE("wfpt_reg_dataset_create");
+  auto* d = new wfpt_reg_ds();
+  d->n = n;
+  d->C = C;
+  d->n_groups = group_id ? n_groups : 1;
+  d->group_max = H.group_max;
+  d->off_host = H.off;
+  if (!H.identity) d->caller_host = H.caller;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  hipError_t e = upload_vec(d->x, H.x);
+  if (e == hipSuccess) e = upload_vec(d->X, H.X);
+  if (e == hipSuccess && group_id) e = upload_vec(d->group, H.group);
+  if (e == hipSuccess) e = upload_vec(d->off, H.off);
+  if (e == hipSuccess && !H.identity) e = upload_vec(d->caller, H.caller);
+  if (e != hipSuccess) {
+    delete d;  // frees what was uploaded (the context's device is current)
+    return fail(WFPT_ERR_HIP, std::string("regression dataset upload: ") + hipGetErrorString(e));
+  }
+  ds_register(c, d);
+  *out = d;
+  return WFPT_OK;
+}
+
+void wfpt_reg_dataset_destroy(wfpt_reg_ds* d) { ds_destroy(d); }
+
+int wfpt_wiener_like_reg_ex(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                            int32_t n_terms, const double* coef, const wfpt_params* p,
+                            const wfpt_knobs* k, double* out, double* out_trial,
+                            double* out_pred) {
+  if (int rc = reg_check_terms(terms, n_terms)) return rc;
+  if (!c || !d || !coef || !p || !k || !out) return fail(WFPT_ERR_ARG, "null pointer");
+  if (int rc = reg_check_call(c, d, terms, n_terms)) return rc;
+  const wfpt::Knobs K = to_knobs(k);
+  WFPT_RANGE("wfpt_wiener_like_reg");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const int64_t n = d->n;
+  if (int rc = reg_fill(c, d, terms, n_terms, coef, 1, false, 0, out_pred != nullptr)) return rc;
+  // a regressed parameter is an array of the pass, every other one its scalar,
+  // as wiener_like_multi(multi=[the regressed ones]) passes them
+  double* dptr[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double scal[7] = {p->v, p->sv, p->a, p->z, p->sz, p->t, p->st};
+  for (int32_t t = 0; t < n_terms; ++t) {
+    dptr[terms[t].param] = c->reg.arr.p + (int64_t)t * n;
+    scal[terms[t].param] = 0.0;
+  }
+  if (int rc = multi_score(c, d->x.p, n, dptr, scal, K, p->p_outlier)) return rc;
+  if (int rc = multi_finish(c, n, out)) return rc;
+  return reg_outputs(c, d, n_terms, out_trial, out_pred);
+}
+
+int wfpt_wiener_like_reg(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                         int32_t n_terms, const double* coef, const wfpt_params* p,
+                         const wfpt_knobs* k, double* out) {
+  return wfpt_wiener_like_reg_ex(c, d, terms, n_terms, coef, p, k, out, nullptr, nullptr);
+}
+
+int wfpt_wiener_like_reg_groups_ex(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                                   int32_t n_terms, const double* coef,
+                                   const wfpt_params* per_group, const wfpt_knobs* k,
+                                   double* out_logp, double* out_trial, double* out_pred) {
+  if (int rc = reg_check_terms(terms, n_terms)) return rc;
+  if (!c || !d || !coef || !per_group || !k || !out_logp)
+    return fail(WFPT_ERR_ARG, "null pointer");
+  if (int rc = reg_check_call(c, d, terms, n_terms)) return rc;
+  const int32_t G = d->n_groups;
+  if (d->group_max > wfpt::kRlNodeMax)
+    return fail(WFPT_ERR_UNSUPPORTED, "a group holds more trials than the per-group sum takes");
+  for (int32_t j = 1; j < G; ++j)  // the per-trial-parameter pass takes one p_outlier
+    if (per_group[j].p_outlier != per_group[0].p_outlier)
+      return fail(WFPT_ERR_UNSUPPORTED, "the groups call needs one p_outlier for all groups");
+  const double p_outlier = per_group[0].p_outlier;
+  const wfpt::Knobs K = to_knobs(k);
+  WFPT_RANGE("wfpt_wiener_like_reg_groups");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const int64_t n = d->n;
+  int term_of[7] = {-1, -1, -1, -1, -1, -1, -1};
+  for (int32_t t = 0; t < n_terms; ++t) term_of[terms[t].param] = t;
+  // v, sv, a, z and t per trial from the group rows unless regressed; sz and st
+  // stay scalars of the pass unless regressed, as in the single call, so a
+  // group's trials take the kernel the single call on that group takes
+  int expand = 0;
+  for (int f : {0, 1, 2, 3, 5})
+    if (term_of[f] < 0) expand |= 1 << f;
+  std::vector<wfpt::Params> par(G);
+  for (int32_t j = 0; j < G; ++j) par[j] = to_params(&per_group[j]);
+  HIP_TRY(c->reg.par.reserve(G));
+  HIP_TRY(hipMemcpyAsync(c->reg.par.p, par.data(), G * sizeof(wfpt::Params),
+                         hipMemcpyHostToDevice, c->stream));
+  if (int rc = reg_fill(c, d, terms, n_terms, coef, G, true, expand, out_pred != nullptr))
+    return rc;
+  double* field[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int f = 0, slot = n_terms; f < 7; ++f) {
+    if (term_of[f] >= 0) field[f] = c->reg.arr.p + (int64_t)term_of[f] * n;
+    else if (expand & (1 << f)) field[f] = c->reg.arr.p + (int64_t)slot++ * n;
+  }
+  if (int rc = score_runs(c, d->x.p, field, per_group, G, d->off_host.data(), d->off.p,
+                          c->reg.npart, K, p_outlier, out_logp))
+    return rc;
+  return reg_outputs(c, d, n_terms, out_trial, out_pred);
+}
+
+int wfpt_wiener_like_reg_groups(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                                int32_t n_terms, const double* coef,
+                                const wfpt_params* per_group, const wfpt_knobs* k,
+                                double* out_logp) {
+  return wfpt_wiener_like_reg_groups_ex(c, d, terms, n_terms, coef, per_group, k, out_logp,
+                                        nullptr, nullptr);
+}
+
+}  // extern "C"

@@ -1,0 +1,324 @@
+// capi_sim.cpp — the samplers of the C ABI (include/wfpt_amd.h): the batched
+// inverse-CDF RT sampler and the diffusion-path simulator (sim_kernels.hip).
+#include "capi_internal.hpp"
+#include "sim_internal.h"
+
+using namespace wfpt::capi;
+
+extern "C" {
+
+// ---------------------------------------------------------------------------
+// RT sampler (sim_kernels.hip; wfpt.pyx:323-354 for R parameter rows)
+
+int wfpt_gen_rts_nodes_ex(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_params* rows,
+                          int64_t R, const int64_t* counts, const double* u_choice,
+                          const double* u_delay, uint64_t seed, int64_t workspace_bytes,
+                          double* out, double* out_pdf, double* out_cdf, int64_t* out_idx,
+                          double* out_u_choice, double* out_u_delay) {
+  if (!grid || !rows || !counts) return fail(WFPT_ERR_ARG, "null pointer (grid / rows / counts)");
+  if (G < 2) return fail(WFPT_ERR_ARG, "gen_rts_nodes: G < 2 (the grid needs two points)");
+  if (R < 1) return fail(WFPT_ERR_ARG, "gen_rts_nodes: R < 1");
+  if (R >= (int64_t)1 << 31) return fail(WFPT_ERR_ARG, "gen_rts_nodes: R must be < 2^31");
+  if (workspace_bytes < 0) return fail(WFPT_ERR_ARG, "gen_rts_nodes: negative workspace_bytes");
+  std::vector<int64_t> off;
+  if (int rc = counts_to_offsets("gen_rts_nodes", counts, R, &off)) return rc;
+  bool any_st = false;
+  for (int64_t r = 0; r < R; ++r) any_st = any_st || rows[r].st != 0;
+  const int64_t total = off[R];
+  if ((u_delay && !u_choice) || (u_choice && !u_delay && any_st))
+    return fail(WFPT_ERR_ARG,
+                "gen_rts_nodes: u_choice and u_delay go together when a row has st != 0");
+  if (!out && total > 0) return fail(WFPT_ERR_ARG, "null pointer (out)");
+  if (!c) return fail(WFPT_ERR_ARG, "null pointer (context)");
+  const int64_t m = G - 1;
+  const int64_t ws = workspace_bytes > 0 ? workspace_bytes : (int64_t)1 << 30;
+  // rows per tile: the workspace's, at most R, and few enough for one launch
+  // of 256-point blocks (a grid's x dimension is below 2^31)
+  int64_t rpt = std::max<int64_t>(1, ws / 8 / m);
+  rpt = std::min(rpt, R);
+  rpt = std::min(rpt, std::max<int64_t>(1, (((int64_t)1 << 31) - 1) / ((m + 255) / 256)));
+  rpt = std::min<int64_t>(rpt, (int64_t)1 << 30);
+  WFPT_RANGE("wfpt_gen_rts_nodes");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  std::vector<wfpt::Params> par((size_t)R);
+  for (int64_t r = 0; r < R; ++r) par[r] = to_params(&rows[r]);
+  const bool want_u = out_u_choice || out_u_delay;
+  HIP_TRY(c->sim.grid.reserve(G));
+  HIP_TRY(c->sim.rows.reserve(R));
+  HIP_TRY(c->sim.off.reserve(R + 1));
+  HIP_TRY(c->sim.tot.reserve(R));
+  HIP_TRY(c->sim.ws.reserve((size_t)wfpt::sim_ws_rows(rpt) * m));
+  HIP_TRY(c->sim.out.reserve(std::max<int64_t>(total, 1)));
+  // [0, total) the choice uniforms, [total, 2 total) the delay uniforms:
+  // supplied ones going in, generated ones coming out of a debugging call
+  if (u_choice || want_u) HIP_TRY(c->sim.u.reserve(std::max<int64_t>(2 * total, 1)));
+  if (out_idx) HIP_TRY(c->sim.idx.reserve(std::max<int64_t>(total, 1)));
+  HIP_TRY(hipMemcpyAsync(c->sim.grid.p, grid, G * sizeof(double), hipMemcpyHostToDevice,
+                         c->stream));
+  HIP_TRY(hipMemcpyAsync(c->sim.rows.p, par.data(), R * sizeof(wfpt::Params),
+                         hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->sim.off.p, off.data(), (R + 1) * sizeof(int64_t),
+                         hipMemcpyHostToDevice, c->stream));
+  if (u_choice && total > 0) {
+    HIP_TRY(hipMemcpyAsync(c->sim.u.p, u_choice, total * sizeof(double), hipMemcpyHostToDevice,
+                           c->stream));
+    if (u_delay)
+      HIP_TRY(hipMemcpyAsync(c->sim.u.p + total, u_delay, total * sizeof(double),
+                             hipMemcpyHostToDevice, c->stream));
+  }
+  if (c->profile)
+    for (hipEvent_t& ev : c->sim.ev)
+      if (!ev) HIP_TRY(hipEventCreate(&ev));
+  if (int rc = begin_status(c)) return rc;
+  wfpt::SimDraw D;
+  D.off = c->sim.off.p;
+  D.u_choice = u_choice ? c->sim.u.p : nullptr;
+  D.u_delay = (u_choice && u_delay) ? c->sim.u.p + total : nullptr;
+  D.seed = seed;
+  D.out = c->sim.out.p;
+  D.idx_out = out_idx ? c->sim.idx.p : nullptr;
+  // the uniforms of a supplied-uniform call are the caller's own: returned
+  // from the host arrays below
+  D.uc_out = (want_u && !u_choice) ? c->sim.u.p : nullptr;
+  D.ud_out = (want_u && !u_choice) ? c->sim.u.p + total : nullptr;
+  for (int64_t r0 = 0; r0 < R; r0 += rpt) {
+    wfpt::SimTile T;
+    T.grid = c->sim.grid.p;
+    T.m = m;
+    T.rows = c->sim.rows.p;
+    T.row0 = r0;
+    T.nrows = (int32_t)std::min(rpt, R - r0);
+    T.W = c->sim.ws.p;
+    T.tot = c->sim.tot.p;
+    const size_t tile_bytes = (size_t)T.nrows * m * sizeof(double);
+    if (c->profile) HIP_TRY(hipEventRecord(c->sim.ev[0], c->stream));
+    wfpt::launch_sim_pdf(T, c->status.p, c->stream);
+    HIP_TRY(hipGetLastError());
+    if (out_pdf)
+      HIP_TRY(hipMemcpyAsync(out_pdf + r0 * m, T.W, tile_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (c->profile) HIP_TRY(hipEventRecord(c->sim.ev[1], c->stream));
+    wfpt::launch_sim_scan(T, c->stream);
+    HIP_TRY(hipGetLastError());
+    if (c->profile) HIP_TRY(hipEventRecord(c->sim.ev[2], c->stream));
+    wfpt::launch_sim_norm(T, c->stream);
+    HIP_TRY(hipGetLastError());
+    if (out_cdf)
+      HIP_TRY(hipMemcpyAsync(out_cdf + r0 * m, T.W, tile_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (c->profile) HIP_TRY(hipEventRecord(c->sim.ev[3], c->stream));
+    wfpt::launch_sim_draw(T, D, off[r0], off[r0 + T.nrows] - off[r0], c->stream);
+    HIP_TRY(hipGetLastError());
+    if (c->profile) {
+      HIP_TRY(hipEventRecord(c->sim.ev[4], c->stream));
+      HIP_TRY(hipEventSynchronize(c->sim.ev[4]));
+      for (int k = 0; k < 4; ++k) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->sim.ev[k], c->sim.ev[k + 1]));
+        c->sim.ms[k] += ms;
+        c->k_ms += ms;
+      }
+      c->launches += 4;
+    }
+  }
+  std::vector<double> tot((size_t)R);
+  HIP_TRY(hipMemcpyAsync(tot.data(), c->sim.tot.p, R * sizeof(double), hipMemcpyDeviceToHost,
+                         c->stream));
+  if (int rc = fetch_status(c)) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // a tile workspace grown past 256 MiB is not kept between calls
+  if (c->sim.ws.cap * sizeof(double) > ((size_t)256 << 20)) c->sim.ws.release();
+  if (int rc = check_status(c)) return rc;
+  // wfpt.pyx:338 divides by the row's total: a total that is not finite and
+  // positive (invalid parameters: all-zero densities; a == 0: NaN) has no CDF
+  for (int64_t r = 0; r < R; ++r)
+    if (!(tot[r] > 0) || !std::isfinite(tot[r]))
+      return fail(WFPT_ERR_UNSUPPORTED, "gen_rts_nodes: row " + std::to_string(r) +
+                                    " has no CDF (the sum of its grid densities is " +
+                                    std::to_string(tot[r]) + "); no draws are returned");
+  if (total > 0) {
+    HIP_TRY(hipMemcpy(out, c->sim.out.p, total * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_idx)
+      HIP_TRY(hipMemcpy(out_idx, c->sim.idx.p, total * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (out_u_choice) {
+      if (u_choice) std::memcpy(out_u_choice, u_choice, total * sizeof(double));
+      else HIP_TRY(hipMemcpy(out_u_choice, c->sim.u.p, total * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (out_u_delay) {
+      if (u_choice && u_delay) std::memcpy(out_u_delay, u_delay, total * sizeof(double));
+      else if (u_choice) std::memset(out_u_delay, 0, total * sizeof(double));
+      else
+        HIP_TRY(hipMemcpy(out_u_delay, c->sim.u.p + total, total * sizeof(double),
+                          hipMemcpyDeviceToHost));
+    }
+  }
+  return WFPT_OK;
+}
+
+int wfpt_gen_rts_nodes(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_params* rows,
+                       int64_t R, const int64_t* counts, const double* u_choice,
+                       const double* u_delay, uint64_t seed, int64_t workspace_bytes,
+                       double* out) {
+  return wfpt_gen_rts_nodes_ex(c, grid, G, rows, R, counts, u_choice, u_delay, seed,
+                               workspace_bytes, out, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// Diffusion-path simulator (sim_drift_kernel; hddm/generate.py:208-319)
+
+int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx* c, const wfpt_params* rows, int64_t R,
+                                const double* sw, const int64_t* counts, double dt,
+                                double intra_sv, int64_t max_steps, uint64_t seed, int64_t row0,
+                                int32_t wave_draws, double* out, int64_t* n_unfinished,
+                                double* out_y0, double* out_delay, double* out_drift,
+                                double* out_drift_switch, int64_t* out_n_steps,
+                                int64_t* out_wave_steps) {
+  if (!rows || !counts || !n_unfinished)
+    return fail(WFPT_ERR_ARG, "null pointer (rows / counts / n_unfinished)");
+  if (R < 1) return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: R < 1");
+  if (R >= (int64_t)1 << 31) return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: R must be < 2^31");
+  if (row0 < 0 || row0 >= (int64_t)1 << 31)
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: row0 outside [0, 2^31)");
+  if (!(dt > 0) || !std::isfinite(dt)) return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: dt <= 0");
+  if (!(intra_sv > 0) || !std::isfinite(intra_sv))
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: intra_sv <= 0");
+  if (max_steps < 1 || max_steps > (int64_t)1 << 31)
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: max_steps outside [1, 2^31]");
+  if (wave_draws < 0 || wave_draws % 64 != 0)
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: wave_draws must be a multiple of 64 (0: default)");
+  if (out_wave_steps && wave_draws == 0)
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: out_wave_steps needs an explicit wave_draws");
+  const double root = std::sqrt(dt);
+  const double step = root * intra_sv, scale = root / intra_sv;  // generate.py:258, 279
+  if (!(step > 0) || !std::isfinite(step) || !std::isfinite(scale))
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: sqrt(dt) * intra_sv is not a usable step");
+  std::vector<int64_t> off;
+  if (int rc = counts_to_offsets("gen_rts_drift_nodes", counts, R, &off)) return rc;
+  const int64_t total = off[R];
+  if (!out && total > 0) return fail(WFPT_ERR_ARG, "null pointer (out)");
+  std::vector<wfpt::DriftRow> tab((size_t)R);
+  for (int64_t r = 0; r < R; ++r) {
+    const wfpt_params& P = rows[r];
+    wfpt::DriftRow& Q = tab[r];
+    Q = wfpt::DriftRow{P.v, P.sv, P.a, P.z, P.sz, P.t, P.st, 0.0, 0.0, wfpt::kDriftNoSwitch, 0u};
+    if (sw) {
+      const double nn = std::nearbyint(sw[3 * r + 2] / dt);  // int(round(t_switch / dt))
+      if (!(nn >= 1))
+        return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: t_switch / dt rounds below 1 in row " +
+                                      std::to_string(r));
+      Q.v_switch = sw[3 * r];
+      Q.V_switch = sw[3 * r + 1];
+      // a switch past the step bound is never reached
+      Q.nn = nn < 4294967295.0 ? (uint32_t)nn : wfpt::kDriftNoSwitch - 1;
+    }
+  }
+  if (!c) return fail(WFPT_ERR_ARG, "null pointer (context)");
+  for (int64_t r = 0; r < R; ++r) {
+    const wfpt::DriftRow& Q = tab[r];
+    const bool finite = std::isfinite(Q.v) && std::isfinite(Q.sv) && std::isfinite(Q.a) &&
+                        std::isfinite(Q.z) && std::isfinite(Q.sz) && std::isfinite(Q.t) &&
+                        std::isfinite(Q.st) && std::isfinite(Q.v_switch) &&
+                        std::isfinite(Q.V_switch);
+    if (!finite || !(Q.a > 0) || Q.z - Q.sz / 2. < 0 || Q.z + Q.sz / 2. > 1)
+      return fail(WFPT_ERR_UNSUPPORTED,
+                  "gen_rts_drift_nodes: row " + std::to_string(r) +
+                      " cannot be simulated (a non-finite parameter, a <= 0, or a start "
+                      "point outside [0, 1]); no draws are returned");
+  }
+  // Draws per wave: one per lane until that gives every SIMD four waves
+  // (1024 SIMDs), then up to 16 per lane, taken in turn as lanes finish
+  // (fewer, longer waves idle less but must still fill the chip).
+  const int64_t wd = wave_draws > 0 ? wave_draws
+                                    : 64 * std::min<int64_t>(16, std::max<int64_t>(1, total / (64 * 4096)));
+  const int64_t waves = (total + wd - 1) / wd;
+  if (waves >= (int64_t)1 << 31)
+    return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: too many draws for one call");
+  *n_unfinished = 0;
+  if (total == 0) return WFPT_OK;
+  WFPT_RANGE("wfpt_gen_rts_drift_nodes");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const bool dbg = out_y0 || out_delay || out_drift || out_drift_switch;
+  HIP_TRY(c->sim.drift_rows.reserve(R));
+  HIP_TRY(c->sim.off.reserve(R + 1));
+  HIP_TRY(c->sim.out.reserve(total));
+  if (dbg) HIP_TRY(c->sim.u.reserve(4 * total));
+  if (out_n_steps || out_wave_steps) HIP_TRY(c->sim.idx.reserve(total + waves));
+  HIP_TRY(hipMemcpyAsync(c->sim.drift_rows.p, tab.data(), R * sizeof(wfpt::DriftRow),
+                         hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->sim.off.p, off.data(), (R + 1) * sizeof(int64_t),
+                         hipMemcpyHostToDevice, c->stream));
+  if (c->profile)
+    for (int k = 0; k < 2; ++k)
+      if (!c->sim.ev[k]) HIP_TRY(hipEventCreate(&c->sim.ev[k]));
+  wfpt::DriftCall C;
+  C.rows = c->sim.drift_rows.p;
+  C.off = c->sim.off.p;
+  C.R = R;
+  C.row0 = row0;
+  C.total = total;
+  C.dt = dt;
+  C.step = step;
+  C.scale = scale;
+  C.max_steps = (uint32_t)max_steps;
+  C.wave_draws = (int32_t)wd;
+  C.seed = seed;
+  C.out = c->sim.out.p;
+  C.y0 = out_y0 ? c->sim.u.p : nullptr;
+  C.delay = out_delay ? c->sim.u.p + total : nullptr;
+  C.drift = out_drift ? c->sim.u.p + 2 * total : nullptr;
+  C.drift_switch = out_drift_switch ? c->sim.u.p + 3 * total : nullptr;
+  C.n_steps = out_n_steps ? c->sim.idx.p : nullptr;
+  C.wave_steps = out_wave_steps ? c->sim.idx.p + total : nullptr;
+  if (c->profile) HIP_TRY(hipEventRecord(c->sim.ev[0], c->stream));
+  wfpt::launch_sim_drift(C, c->stream);
+  HIP_TRY(hipGetLastError());
+  if (c->profile) {
+    HIP_TRY(hipEventRecord(c->sim.ev[1], c->stream));
+    HIP_TRY(hipEventSynchronize(c->sim.ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->sim.ev[0], c->sim.ev[1]));
+    c->k_ms += ms;
+    c->launches += 1;
+  }
+  HIP_TRY(hipMemcpyAsync(out, c->sim.out.p, total * sizeof(double), hipMemcpyDeviceToHost,
+                         c->stream));
+  const std::pair<double*, const double*> copies[] = {
+      {out_y0, C.y0}, {out_delay, C.delay}, {out_drift, C.drift},
+      {out_drift_switch, C.drift_switch}};
+  for (const auto& cp : copies)
+    if (cp.first)
+      HIP_TRY(hipMemcpyAsync(cp.first, cp.second, total * sizeof(double), hipMemcpyDeviceToHost,
+                             c->stream));
+  if (out_n_steps)
+    HIP_TRY(hipMemcpyAsync(out_n_steps, C.n_steps, total * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, c->stream));
+  if (out_wave_steps)
+    HIP_TRY(hipMemcpyAsync(out_wave_steps, C.wave_steps, waves * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int64_t nan = 0;  // only a draw that ran out of steps is NaN
+  for (int64_t i = 0; i < total; ++i) nan += std::isnan(out[i]) ? 1 : 0;
+  *n_unfinished = nan;
+  return WFPT_OK;
+}
+
+int wfpt_gen_rts_drift_nodes(wfpt_ctx* c, const wfpt_params* rows, int64_t R, const double* sw,
+                             const int64_t* counts, double dt, double intra_sv,
+                             int64_t max_steps, uint64_t seed, double* out,
+                             int64_t* n_unfinished) {
+  return wfpt_gen_rts_drift_nodes_ex(c, rows, R, sw, counts, dt, intra_sv, max_steps, seed, 0, 0,
+                                     out, n_unfinished, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr);
+}
+
+int wfpt_profile_stages(wfpt_ctx* c, double stage_ms[4], int reset) {
+  if (!c || !stage_ms) return fail(WFPT_ERR_ARG, "null pointer");
+  std::lock_guard<std::mutex> lk(c->mu);
+  for (int k = 0; k < 4; ++k) {
+    stage_ms[k] = c->sim.ms[k];
+    if (reset) c->sim.ms[k] = 0.0;
+  }
+  return WFPT_OK;
+}
+
+}  // extern "C"

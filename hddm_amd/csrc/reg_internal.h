@@ -1,4 +1,4 @@
-// reg_internal.h — launcher interface between the C ABI (wfpt_capi.cpp) and the
+// reg_internal.h — launcher interface between the C ABI (capi_*.cpp) and the
 // regression front end (reg_kernels.hip). Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,10 +7,6 @@
 namespace wfpt {
 struct Params;
 
-// Weak for the same reason as the RL launchers (rl_internal.h): the host-only
-// sanitizer build links wfpt_capi.cpp without this device unit, and the
-// regression entry points then fail with WFPT_ERR_UNSUPPORTED.
-#define WFPT_REG_WEAK __attribute__((weak))
 
 constexpr int kRegMaxTerms = 7;  // one term per parameter (v .. st) at the most
 constexpr int kRegIdentity = 0, kRegExp = 1, kRegInvLogit = 2;  // WFPT_LINK_*
@@ -46,6 +42,5 @@ struct RegFill {
 //   eta = X[i, col0] * b[col0]; eta = eta + X[i, col0 + 1] * b[col0 + 1]; ...
 // then IDENTITY: eta; EXP: cr_exp(eta) (correctly rounded, wfpt_crlibm.hpp);
 // INVLOGIT: 1 / (1 + cr_exp(-eta)), each operation rounded once.
-WFPT_REG_WEAK void launch_reg_fill(const RegFill& F, hipStream_t s);
-inline bool reg_kernels_linked() { return launch_reg_fill != nullptr; }
+void launch_reg_fill(const RegFill& F, hipStream_t s);
 }  // namespace wfpt

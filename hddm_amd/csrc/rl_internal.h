@@ -1,4 +1,4 @@
-// rl_internal.h — launcher interface between the C ABI (wfpt_capi.cpp) and the
+// rl_internal.h — launcher interface between the C ABI (capi_*.cpp) and the
 // reinforcement-learning kernels (rl_kernels.hip). Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,12 +7,6 @@
 namespace wfpt {
 struct Params;
 
-// The launchers are weak: the C ABI's host code also links without the device
-// unit (the host-only sanitizer build of tests/test_sanitizers.py links
-// wfpt_capi.cpp with the older kernel files alone). rl_kernels_linked() is
-// false there, and the RL entry points then fail with WFPT_ERR_UNSUPPORTED
-// instead of computing anything.
-#define WFPT_RL_WEAK __attribute__((weak))
 
 // One Q-learning row (wfpt.pyx:83): the start value of both Q values, the two
 // learning rates already squashed on the host (pow(2.718281828459, alpha) /
@@ -51,23 +45,23 @@ struct RlLayout {
 // every trial, in the caller's order. rows (nullable, device): one row per
 // node, else `one`. vmul / rate (nullable, device, n, stored order): the
 // trial's drift scaling / learning rate instead of the row's.
-WFPT_RL_WEAK void launch_rl_scan(const RlLayout& L, const RlRow& one, const RlRow* rows,
-                                 const double* vmul, const double* rate, double* drift_c,
-                                 double* drift_in, hipStream_t s);
+void launch_rl_scan(const RlLayout& L, const RlRow& one, const RlRow* rows,
+                    const double* vmul, const double* rate, double* drift_c,
+                    double* drift_in, hipStream_t s);
 
 // wiener_like_rl's choice probability (wfpt.pyx:210-227) of m compact trials:
 // lp[i] = log(p (1 - p_outlier) + wp_outlier), then the per-block sums into
 // part / zeros (blocks_for(m) of them, lp_sum_kernel's order) for
 // launch_finalize.
-WFPT_RL_WEAK void launch_rl_choice(const double* drift_c, const unsigned char* resp_c, int64_t m,
-                                   double z, double p_outlier, double wp_outlier, double* lp,
-                                   double* part, int* zeros, hipStream_t s);
+void launch_rl_choice(const double* drift_c, const unsigned char* resp_c, int64_t m,
+                      double z, double p_outlier, double wp_outlier, double* lp,
+                      double* part, int* zeros, hipStream_t s);
 
 // Node rows -> per-trial arrays: dst[slot * m + i] = field f of P[node_c[i]]
 // for every field f (1 = sv .. 6 = st; wfpt_params order) whose bit is set in
 // mask, slots counted over the set bits in rising order.
-WFPT_RL_WEAK void launch_rl_fill(const int32_t* node_c, int64_t m, const Params* P, int mask,
-                                 double* dst, hipStream_t s);
+void launch_rl_fill(const int32_t* node_c, int64_t m, const Params* P, int mask,
+                    double* dst, hipStream_t s);
 
 // res[j] = the sum of lp[off[j] .. off[j + 1]) in the order lp_sum_kernel +
 // finalize_kernel (one block) add a call's terms: bit for bit the sum of the
@@ -76,9 +70,6 @@ WFPT_RL_WEAK void launch_rl_fill(const int32_t* node_c, int64_t m, const Params*
 // it the single-node call's finalize splits over blocks, another order).
 constexpr int64_t kRlNodeMax = 2 * 8192 * 256;
 inline int64_t rl_node_partials(int64_t m, int32_t n_nodes) { return m / 256 + n_nodes + 1; }
-WFPT_RL_WEAK void launch_rl_node_sum(const double* lp, const int64_t* off, int32_t n_nodes,
-                                     double* scratch, double* res, hipStream_t s);
-inline bool rl_kernels_linked() {
-  return launch_rl_scan && launch_rl_choice && launch_rl_fill && launch_rl_node_sum;
-}
+void launch_rl_node_sum(const double* lp, const int64_t* off, int32_t n_nodes,
+                        double* scratch, double* res, hipStream_t s);
 }  // namespace wfpt

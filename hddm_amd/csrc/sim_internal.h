@@ -1,4 +1,4 @@
-// sim_internal.h — launcher interface between the C ABI (wfpt_capi.cpp) and the
+// sim_internal.h — launcher interface between the C ABI (capi_*.cpp) and the
 // RT sampler kernels (sim_kernels.hip). Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,10 +7,6 @@
 namespace wfpt {
 struct Params;
 
-// Weak like the RL launchers (rl_internal.h): the host-only sanitizer build
-// links wfpt_capi.cpp without this unit; sim_kernels_linked() is false there
-// and the sampler entry points fail with WFPT_ERR_UNSUPPORTED.
-#define WFPT_SIM_WEAK __attribute__((weak))
 
 // One tile of the batched inverse-CDF sampler (wfpt.pyx:323-354; DESIGN.md
 // §15): rows [row0, row0 + nrows) of the call's parameter table over the
@@ -30,17 +26,17 @@ struct SimTile {
 // W[r][i] = full_pdf(x[i + 1], v, sv, a, z, sz, 0, 0, 1e-4) with full_pdf's
 // defaults n_st = n_sz = 2, adaptive, simps_err = 1e-3 (wfpt.pyx:335): one grid
 // point per lane, one row per block. Depth / budget flags are OR-ed into status.
-WFPT_SIM_WEAK void launch_sim_pdf(const SimTile& T, int* status, hipStream_t s);
+void launch_sim_pdf(const SimTile& T, int* status, hipStream_t s);
 
 // W[r][i] <- W[r][0] + ... + W[r][i], added in index order from 0.0 as the
 // reference's loop does (wfpt.pyx:333-336), one lane per row; tot[row0 + r] =
 // the row's last sum. The scan moves whole blocks of 64 rows: W must hold
 // sim_ws_rows(nrows) rows (the rows past nrows are scratch).
 inline int64_t sim_ws_rows(int64_t nrows) { return (nrows + 63) / 64 * 64; }
-WFPT_SIM_WEAK void launch_sim_scan(const SimTile& T, hipStream_t s);
+void launch_sim_scan(const SimTile& T, hipStream_t s);
 
 // W[r][i] <- W[r][i] / tot[row0 + r] (wfpt.pyx:338).
-WFPT_SIM_WEAK void launch_sim_norm(const SimTile& T, hipStream_t s);
+void launch_sim_norm(const SimTile& T, hipStream_t s);
 
 // The draws of the tile's rows: draw j of global row r is element off[r] + j
 // of out / u_choice / u_delay / idx_out (off: [R + 1] prefix sums of the
@@ -58,8 +54,8 @@ struct SimDraw {
   double* uc_out;
   double* ud_out;
 };
-WFPT_SIM_WEAK void launch_sim_draw(const SimTile& T, const SimDraw& D, int64_t first,
-                                   int64_t ndraws, hipStream_t s);
+void launch_sim_draw(const SimTile& T, const SimDraw& D, int64_t first,
+                     int64_t ndraws, hipStream_t s);
 
 // The diffusion-path simulator (hddm/generate.py:208-319): one
 // row of the call's table. nn: the first step that uses the switched drift
@@ -97,10 +93,6 @@ struct DriftCall {
   int64_t* n_steps;      // steps taken: the crossing step's index + 1, or max_steps
   int64_t* wave_steps;   // [ceil(total / wave_draws)] steps each wave's loop ran
 };
-WFPT_SIM_WEAK void launch_sim_drift(const DriftCall& C, hipStream_t s);
+void launch_sim_drift(const DriftCall& C, hipStream_t s);
 
-inline bool sim_kernels_linked() {
-  return launch_sim_pdf && launch_sim_scan && launch_sim_norm && launch_sim_draw &&
-         launch_sim_drift;
-}
 }  // namespace wfpt

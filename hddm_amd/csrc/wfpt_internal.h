@@ -1,4 +1,4 @@
-// wfpt_internal.h — launcher interface between the C ABI (wfpt_capi.cpp) and
+// wfpt_internal.h — launcher interface between the C ABI (capi_*.cpp) and
 // the kernels (wfpt_kernels.hip). Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1705,7 +1705,7 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const double* lp, cons
 //      read res[] and store it to the mapped slot;
 //   5. __syncthreads, then thread 0 stores the completion word with a
 //      system-scope release; the host polls it with an acquire load
-//      (wfpt_capi.cpp: wait_word), so every sum is visible when it reads.
+//      (capi_core.cpp: wait_word), so every sum is visible when it reads.
 // r05 let each wave store its sum straight into the mapped slot, ordered
 // before the completion word by nothing: one GPU-suite run read a node sum
 // of the previous call (profiles/r06/stale_diag/ shows the test catching that

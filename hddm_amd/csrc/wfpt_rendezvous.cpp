@@ -35,9 +35,9 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/wfpt_amd.h"
+#include "capi_internal.hpp"
 
-int wfpt_rdv_fail(int code, const std::string& msg);  // wfpt_capi.cpp (last-error slot)
+using wfpt::capi::fail;
 
 namespace {
 
@@ -170,13 +170,13 @@ bool literal_loopback(const char* host) {
 extern "C" int wfpt_comm_exchange_id(int nranks, int rank, const char* host, int port,
                                      int timeout_ms, unsigned char id[128]) {
   if (!host || !id || nranks < 1 || rank < 0 || rank >= nranks || port <= 0 || port > 65535)
-    return wfpt_rdv_fail(WFPT_ERR_ARG, "wfpt_comm_exchange_id: bad arguments");
+    return fail(WFPT_ERR_ARG, "wfpt_comm_exchange_id: bad arguments");
   if (nranks == 1) return WFPT_OK;
   const auto deadline = Clock::now() + std::chrono::milliseconds(timeout_ms > 0 ? timeout_ms : 1);
   sockaddr_storage sa{};
   socklen_t slen = 0;
   if (!resolve(host, port, &sa, &slen))
-    return wfpt_rdv_fail(WFPT_ERR_COMM, std::string("rendezvous: cannot resolve ") + host);
+    return fail(WFPT_ERR_COMM, std::string("rendezvous: cannot resolve ") + host);
   if (rank == 0) {
     sockaddr_storage la = sa;
     socklen_t llen = slen;
@@ -192,11 +192,11 @@ extern "C" int wfpt_comm_exchange_id(int nranks, int rank, const char* host, int
                    host);
     Fd ls;
     ls.fd = ::socket(la.ss_family, SOCK_STREAM, 0);
-    if (ls.fd < 0) return wfpt_rdv_fail(WFPT_ERR_COMM, "rendezvous: socket() failed");
+    if (ls.fd < 0) return fail(WFPT_ERR_COMM, "rendezvous: socket() failed");
     const int one = 1;
     (void)::setsockopt(ls.fd, SOL_SOCKET, SO_REUSEADDR, &one, sizeof(one));
     if (::bind(ls.fd, (sockaddr*)&la, llen) != 0 || ::listen(ls.fd, nranks) != 0)
-      return wfpt_rdv_fail(WFPT_ERR_COMM, "rendezvous: cannot listen on port " +
+      return fail(WFPT_ERR_COMM, "rendezvous: cannot listen on port " +
                                               std::to_string(port) + " (" + strerror(errno) + ")");
     std::vector<bool> seen(nranks, false);
     for (int got = 0; got < nranks - 1;) {
@@ -205,7 +205,7 @@ extern "C" int wfpt_comm_exchange_id(int nranks, int rank, const char* host, int
       const int pr = t > 0 ? ::poll(&q, 1, t) : 0;
       if (pr < 0 && errno == EINTR) continue;
       if (pr <= 0)
-        return wfpt_rdv_fail(WFPT_ERR_COMM, "rendezvous: timed out with " + std::to_string(got) +
+        return fail(WFPT_ERR_COMM, "rendezvous: timed out with " + std::to_string(got) +
                                                 " of " + std::to_string(nranks - 1) +
                                                 " peers served" +
                                                 (lo_alias ? std::string(" (rank 0 listened on the "
@@ -238,7 +238,7 @@ extern "C" int wfpt_comm_exchange_id(int nranks, int rank, const char* host, int
   for (;;) {
     Fd c;
     c.fd = ::socket(sa.ss_family, SOCK_STREAM, 0);
-    if (c.fd < 0) return wfpt_rdv_fail(WFPT_ERR_COMM, "rendezvous: socket() failed");
+    if (c.fd < 0) return fail(WFPT_ERR_COMM, "rendezvous: socket() failed");
     if (connect_by(c.fd, sa, slen, deadline)) {
       const uint32_t hello[4] = {kMagic, (uint32_t)nranks, (uint32_t)rank, job_token()};
       unsigned char buf[128];
@@ -250,7 +250,7 @@ extern "C" int wfpt_comm_exchange_id(int nranks, int rank, const char* host, int
       }
     }
     if (ms_left(deadline) == 0)
-      return wfpt_rdv_fail(WFPT_ERR_COMM, std::string("rendezvous: no id from rank 0 at ") + host +
+      return fail(WFPT_ERR_COMM, std::string("rendezvous: no id from rank 0 at ") + host +
                                               ":" + std::to_string(port) + " before the deadline");
     std::this_thread::sleep_for(std::chrono::milliseconds(20));
   }

@@ -622,7 +622,7 @@ class HDDMChains(HDDM):
         # one launch per integration family: a table whose sz or st is 0 (a
         # probe at the slice's lower bound) selects another family, and a
         # launch over tables of several families takes the generic per-trial
-        # kernel (wfpt_capi.cpp: nodes_launch)
+        # kernel (capi_core.cpp: nodes_launch)
         fam = (tabs[:, 0, 4] > 0).astype(np.int8) * 2 + (tabs[:, 0, 6] > 0)
         if (fam == fam[0]).all():
             r = self.dataset.wiener_like_nodes_multi(tabs, **self.wp)

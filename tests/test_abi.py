@@ -180,3 +180,40 @@ def test_build_switch_inventory():
     named = {d.split("=")[0] for t in tables for v in t.values() for d in v
              if not d.startswith("-")}
     assert named <= found, sorted(named - found)
+
+
+@pytest.mark.gpu
+def test_close_detaches_live_datasets_of_every_kind(gpu):
+    """One context, one dataset of each kind (plain, RL, regression) at n = 65
+    (one trial past a 64-lane chunk), one likelihood on each; the context is
+    closed with all three alive, then they are destroyed: a detached destroy
+    frees only the host part. A second round in the same process reopens the
+    device and must give the same bits."""
+    from hddm_amd import _lib
+    n = 65
+    rng = np.random.default_rng(65)
+    rt = rng.uniform(0.4, 1.5, n) * np.where(rng.random(n) < 0.6, 1.0, -1.0)
+    response = (rt > 0).astype(np.int64)
+    feedback = rng.integers(0, 2, n).astype(np.float64)
+    split_by = (np.arange(n) % 3 == 0).astype(np.int64)  # two conditions, unequal lengths
+    X = np.column_stack([np.ones(n), rng.normal(size=n)])
+    rounds = []
+    for _ in range(2):
+        ctx = _lib.Context(_lib.default_device())
+        ds = gpu.Dataset(rt, ctx=ctx)
+        rl = gpu.RLDataset(rt, response, feedback, split_by, ctx=ctx)
+        reg = gpu.RegDataset(rt, X, ctx=ctx)
+        got = (ds.wiener_like(0.5, 0.1, 2.0, 0.5, 0.1, 0.3, 0.1, 1e-4, 2, 2, 1, 1e-3, 0.05, 0.1),
+               rl.wiener_like_rlddm(0.5, 0.2, 100.0, 1.5, 0.0, 2.0, 0.5, 0.0, 0.3, 0.0, 1e-4,
+                                    p_outlier=0.05, w_outlier=0.1),
+               reg.wiener_like_reg([("v", 0, 2, "identity")], [0.4, 0.2], 0.0, 0.1, 2.0, 0.5,
+                                   0.1, 0.3, 0.1, 1e-4, 2, 2, p_outlier=0.05, w_outlier=0.1))
+        assert all(np.isfinite(g) for g in got), got
+        ctx.close()  # the three datasets are still alive: detached here
+        assert _lib.wfpt_dataset_size(ds.handle) == n  # the host part survives
+        with pytest.raises(Exception):  # its context is gone: an argument error, no device work
+            ds.wiener_like(0.5, 0.1, 2.0, 0.5, 0.1, 0.3, 0.1, 1e-4, 2, 2, 1, 1e-3, 0.05, 0.1)
+        for d in (ds, rl, reg):
+            d.close()
+        rounds.append(got)
+    assert rounds[0] == rounds[1]

@@ -428,7 +428,7 @@ def test_resident_sizes_and_repeats(gpu, oracle_lib):
 
 def test_resident_fast_only_prediction(gpu, oracle_lib):
     """A resident dataset whose last call deferred no trial runs the level-0 pass
-    + finalize only (run_sum_fast in wfpt_capi.cpp); when that prediction is
+    + finalize only (run_sum_fast in capi_core.cpp); when that prediction is
     wrong the slow pass runs after all. Alternating deferring / non-deferring
     parameters on one dataset exercises both transitions; every result must
     equal the host-array path (always the full sequence) and the oracle."""

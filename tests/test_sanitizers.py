@@ -3,7 +3,7 @@
 
 tests/c/sanitize_driver.cpp is linked from the real sources — the oracle
 (oracle/wfpt_oracle.c), the exact path (wfpt_exact.hpp, wfpt_crlibm.hpp), the C
-ABI's host code (wfpt_capi.cpp, wfpt_rendezvous.cpp; the kernel objects only
+ABI's host code (every unit of hddm_amd.build.SOURCES; the kernel objects only
 for their host launch stubs) — with the sanitizers on the host side
 (`-Xarch_host -fsanitize=...` for HIP sources, one clang toolchain for all of
 it), and run here without a GPU. Any sanitizer report fails the test
@@ -14,6 +14,8 @@ import socket
 import subprocess
 
 import pytest
+
+from hddm_amd.build import SOURCES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLANG = "/opt/rocm/lib/llvm/bin/clang"
@@ -44,8 +46,7 @@ def driver(tmp_path_factory):
     hip_flags = ["-std=c++17", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950",
                  "-Xarch_host", "-O1", "-Xarch_host", "-g", "-Xarch_host", SAN, "-Xarch_host",
                  NOREC]
-    for src in ("wfpt_capi.cpp", "wfpt_rendezvous.cpp", "wfpt_kernels.hip",
-                "cdfdif_kernels.hip"):
+    for src in SOURCES:  # the library's own list: every kernel unit, every C ABI unit
         o = str(d / (os.path.splitext(src)[0] + ".o"))
         # no GPU runs here: the device code only has to exist (-O0 keeps the
         # build short); the host side is what is sanitized
