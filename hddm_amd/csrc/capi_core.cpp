@@ -338,6 +338,7 @@ static int run_sum_fast(wfpt_ctx* c, const wfpt_ds* d, const wfpt::Params& P, co
   const bool fast = c->fast_only && d->no_defer;
   if (!lean && !fast) return -1;
   const int lp = lean ? wfpt::kPassLean : 0;
+  double ntree0 = 0.0;  // chunks the first of two launches reported as refined in-wave
   if (!fast) {  // deferred trials expected: the whole sequence at once
     if (int rc = run_sum(c, d->x.p, n, P, K, c->mres.d, wfpt::kPassAll | lp | wfpt::kPassRedo, d))
       return rc;
@@ -346,12 +347,22 @@ static int run_sum_fast(wfpt_ctx* c, const wfpt_ds* d, const wfpt::Params& P, co
     if (int rc = wait_result(c, c->mres.h)) return rc;
     if (res_deferred(c->mres.h)) {
       if (int rc = check_status_value(c->mres.h[2])) return rc;
+      ntree0 = c->mres.h[6];
       if (int rc = run_sum(c, d->x.p, n, P, K, c->mres.d,
                            wfpt::kPassDeferred | (lean ? wfpt::kPassRedo : 0), d))
         return rc;
     }
   }
-  return finish_sum(c, d, P, K, out, lean);
+  const int rc = finish_sum(c, d, P, K, out, lean);
+  // an engine level-0 pass whose deferred trials took a second launch: its own
+  // finalize reported (and reset) the refinement count, so the second result
+  // holds the deferred pass's alone (0 without a redo pass) and would predict
+  // the lean pass for data that refines
+  if (rc == WFPT_OK && eng && ntree0 > 0.0) {
+    d->no_tree = false;
+    d->tree_frac += d->nw > 0 ? ntree0 / (double)d->nw : 0.0;
+  }
+  return rc;
 }
 
 // |a| < |b| with NaN RTs last: a strict weak order for any input (the

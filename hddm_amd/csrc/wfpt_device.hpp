@@ -52,8 +52,10 @@ enum Mode : int {
 };
 
 // Host+device: mode after full_pdf's st/sz < 1e-3 zeroing (pdf.pxi:122-146).
+// A NaN is not below the threshold: the reference leaves it and integrates
+// over a NaN interval (NaN), as trial_setup does, so its family integrates.
 __host__ __device__ inline int select_mode(double sz, double st, int use_adaptive) {
-  const bool zst = !(st >= 1e-3), zsz = !(sz >= 1e-3);
+  const bool zst = st < 1e-3, zsz = sz < 1e-3;
   if (zsz) {
     if (zst) return kDirect;
     return use_adaptive > 0 ? kAdaptT : kFixedT;
