@@ -107,6 +107,8 @@ wfpt_wiener_like_multi_ex = _sig("wfpt_wiener_like_multi_ex", _I,
 wfpt_wiener_like_multi_resident_ex = _sig("wfpt_wiener_like_multi_resident_ex", _I,
                                           [_VP, _VP, ctypes.POINTER(_PD), _PD, _PK, _D, _PD, _PD])
 wfpt_dmat_cdf_array = _sig("wfpt_dmat_cdf_array", _I, [_VP, _PD, _I64, _PP, _D, _PD])
+wfpt_dmat_cdf_rows = _sig("wfpt_dmat_cdf_rows", _I,
+                          [_VP, _PP, _PD, _PD, _PD, _I64, _I32, _D, _PD, _PD, _PD])
 wfpt_comm_unique_id = _sig("wfpt_comm_unique_id", _I, [ctypes.c_char_p])
 wfpt_comm_init = _sig("wfpt_comm_init", _I, [_VP, _I, _I, ctypes.c_char_p])
 wfpt_wiener_like_allreduce = _sig("wfpt_wiener_like_allreduce", _I, [_VP, _VP, _PP, _PK, _PD])
@@ -218,6 +220,7 @@ EXPORTED = [
     "wfpt_gen_rts_drift_nodes", "wfpt_gen_rts_drift_nodes_ex",
     "wfpt_reg_dataset_create", "wfpt_reg_dataset_destroy", "wfpt_wiener_like_reg",
     "wfpt_wiener_like_reg_ex", "wfpt_wiener_like_reg_groups", "wfpt_wiener_like_reg_groups_ex",
+    "wfpt_dmat_cdf_rows",
 ]
 
 # error encoding of a result triple (include/wfpt_amd.h: wfpt_decode_result)

@@ -11,7 +11,11 @@ outlier mixture: F(|x|, boundary) from cdfdif (src/cdfdif.c:59-221), folded as
 Callers: the stochastic's `cdf` (hddm/likelihoods.py:90-91) and the quantile /
 chi-square optimisers built on it (likelihoods.py:200-239, base.py:249-264).
 
-The series run in the HIP kernel of libwfpt_amd.so (cdfdif_kernels.hip);
+`dmat_cdf_rows` is not in the reference: the same CDF for many rows of
+(parameters, a few RTs, bin counts) in one launch, with each row's chi-square
+and G-square, for the quantile optimisers (hddm_amd/optimize.py).
+
+The series run in the HIP kernels of libwfpt_amd.so (cdfdif_kernels.hip);
 argument checks and their exceptions are the reference's.
 """
 import ctypes
@@ -21,7 +25,61 @@ import numpy as np
 from . import _lib
 from .wfpt import _check_x
 
-__all__ = ["dmat_cdf_array"]
+__all__ = ["dmat_cdf_array", "dmat_cdf_rows"]
+
+MAX_EDGES = 64    # include/wfpt_amd.h: wfpt_dmat_cdf_rows
+ROWS_GRID = 2048  # its launch grid (wfpt_internal.h: kCdfRowsGrid); more rows stride over it
+
+
+def dmat_cdf_rows(x, params, w_outlier, freq_obs=None, n_samples=None):
+    """dmat_cdf_array for R rows in one launch, each with its own parameters.
+
+    x (R, E): signed RTs of each row, ascending (the quantile edges of
+    hddm_amd.quantiles.quantile_stats); params (R, 8): v, sv, a, z, sz, t, st,
+    p_outlier per row. Returns cdf (R, E), row r bit for bit
+    dmat_cdf_array(x[r], *params[r], w_outlier).
+
+    With freq_obs (R, E + 1) and n_samples (R,) it returns (cdf, chisq, gsq),
+    the reference's quantile statistics (likelihoods.py:200-239) per row:
+    p = diff([0, cdf, 1]) with p <= 1e-6 replaced by 1e-6, chisq = the Pearson
+    sum of (freq_obs - p n)^2 / (p n), gsq = 2 sum(freq_obs log p).
+
+    A row outside the support (NaN included) does not raise: its chisq is
+    +inf, its gsq -inf and its cdf NaN, what the reference's `except
+    ValueError` branches return. The RT assertion and the zero w_outlier are
+    dmat_cdf_array's, raised before any device work."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    P = np.ascontiguousarray(params, dtype=np.float64)
+    if x.ndim != 2 or P.ndim != 2 or P.shape[1] != 8 or P.shape[0] != x.shape[0]:
+        raise ValueError("dmat_cdf_rows: x must be (R, E) and params (R, 8)")
+    R, E = x.shape
+    if R < 1 or not 1 <= E <= MAX_EDGES:
+        raise ValueError(f"dmat_cdf_rows: needs R >= 1 and 1 <= E <= {MAX_EDGES}, got R={R}, E={E}")
+    if (freq_obs is None) != (n_samples is None):
+        raise ValueError("dmat_cdf_rows: freq_obs and n_samples go together")
+    if float(w_outlier) == 0.0:  # add_outlier_cdf (cdfdif_wrapper.pyx:11-12)
+        raise ZeroDivisionError("float division")
+    if np.any(P[:, 7] > 0):  # cdfdif_wrapper.pyx:20-21
+        assert np.max(np.abs(x)) < (1. / (2 * w_outlier)), \
+            ValueError('1. / (2*w_outlier) must be smaller than RT')
+    if freq_obs is not None:
+        f = np.ascontiguousarray(freq_obs, dtype=np.float64)
+        n = np.ascontiguousarray(n_samples, dtype=np.float64)
+        if f.shape != (R, E + 1) or n.shape != (R,):
+            raise ValueError("dmat_cdf_rows: freq_obs must be (R, E + 1) and n_samples (R,)")
+    c = _lib.context()
+    cdf = np.empty((R, E), dtype=np.float64)
+    rows = P.ctypes.data_as(ctypes.POINTER(_lib.Params))
+    if freq_obs is None:
+        _lib.check(_lib.wfpt_dmat_cdf_rows(c.handle, rows, _lib.dptr(x), None, None, R, E,
+                                           float(w_outlier), _lib.dptr(cdf), None, None))
+        return cdf
+    chisq = np.empty(R, dtype=np.float64)
+    gsq = np.empty(R, dtype=np.float64)
+    _lib.check(_lib.wfpt_dmat_cdf_rows(c.handle, rows, _lib.dptr(x), _lib.dptr(f), _lib.dptr(n),
+                                       R, E, float(w_outlier), _lib.dptr(cdf), _lib.dptr(chisq),
+                                       _lib.dptr(gsq)))
+    return cdf, chisq, gsq
 
 
 def dmat_cdf_array(x, v, sv, a, z, sz, t, st, p_outlier, w_outlier):

@@ -1220,6 +1220,68 @@ int wfpt_dmat_cdf_array(wfpt_ctx* c, const double* x, int64_t n, const wfpt_para
   return WFPT_OK;
 }
 
+int wfpt_dmat_cdf_rows(wfpt_ctx* c, const wfpt_params* rows, const double* x,
+                       const double* freq_obs, const double* n_samples, int64_t R, int32_t E,
+                       double w_outlier, double* out_cdf, double* out_chisq, double* out_gsq) {
+  if (!c || !rows || !x) return fail(WFPT_ERR_ARG, "dmat_cdf_rows: null pointer");
+  if (R < 1) return fail(WFPT_ERR_ARG, "dmat_cdf_rows: R must be >= 1");
+  if (E < 1 || E > wfpt::kCdfRowsMaxEdges)
+    return fail(WFPT_ERR_ARG, "dmat_cdf_rows: E must be in 1.." +
+                                  std::to_string(wfpt::kCdfRowsMaxEdges));
+  if (R > ((int64_t)1 << 31) / (E + 1))
+    return fail(WFPT_ERR_ARG, "dmat_cdf_rows: R * (E + 1) must be <= 2^31");
+  const bool stats = freq_obs != nullptr;
+  if (stats != (n_samples != nullptr) || stats != (out_chisq != nullptr) ||
+      stats != (out_gsq != nullptr))
+    return fail(WFPT_ERR_ARG,
+                "dmat_cdf_rows: freq_obs, n_samples, out_chisq and out_gsq go together");
+  if (!stats && !out_cdf) return fail(WFPT_ERR_ARG, "dmat_cdf_rows: no output requested");
+  static_assert(sizeof(wfpt_params) == 8 * sizeof(double), "rows pack as doubles");
+  WFPT_RANGE("wfpt_dmat_cdf_rows");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  // in: rows | x | freq_obs | n_samples; out: cdf | chisq | gsq
+  const size_t o_x = (size_t)R * 8, o_f = o_x + (size_t)R * E;
+  const size_t o_n = o_f + (stats ? (size_t)R * (E + 1) : 0), n_in = o_n + (stats ? R : 0);
+  const size_t o_c = out_cdf ? (size_t)R * E : 0, n_out = o_c + (stats ? 2 * (size_t)R : 0);
+  std::vector<double>& h = c->rows_host;
+  h.resize(std::max(n_in, n_out));
+  std::memcpy(h.data(), rows, (size_t)R * sizeof(wfpt_params));
+  std::memcpy(h.data() + o_x, x, (size_t)R * E * sizeof(double));
+  if (stats) {
+    std::memcpy(h.data() + o_f, freq_obs, (size_t)R * (E + 1) * sizeof(double));
+    std::memcpy(h.data() + o_n, n_samples, (size_t)R * sizeof(double));
+  }
+  HIP_TRY(c->rows_in.reserve(n_in));
+  HIP_TRY(c->rows_out.reserve(n_out));
+  HIP_TRY(hipMemcpyAsync(c->rows_in.p, h.data(), n_in * sizeof(double), hipMemcpyHostToDevice,
+                         c->stream));
+  if (c->profile) HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  double* d = c->rows_in.p;
+  double* o = c->rows_out.p;
+  wfpt::launch_dmat_cdf_rows(reinterpret_cast<const wfpt_params*>(d), d + o_x,
+                             stats ? d + o_f : nullptr, stats ? d + o_n : nullptr, R, E, w_outlier,
+                             out_cdf ? o : nullptr, stats ? o + o_c : nullptr,
+                             stats ? o + o_c + R : nullptr, c->stream);
+  HIP_TRY(hipGetLastError());
+  if (c->profile) HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  // the upload is complete before the kernel runs (same stream), so h is free
+  HIP_TRY(hipMemcpyAsync(h.data(), o, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (out_cdf) std::memcpy(out_cdf, h.data(), o_c * sizeof(double));
+  if (stats) {
+    std::memcpy(out_chisq, h.data() + o_c, (size_t)R * sizeof(double));
+    std::memcpy(out_gsq, h.data() + o_c + R, (size_t)R * sizeof(double));
+  }
+  if (c->profile) {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->k_ms += ms;
+    c->launches += 1;
+  }
+  return WFPT_OK;
+}
+
 int wfpt_profile_enable(wfpt_ctx* c, int flags) {
   if (!c) return fail(WFPT_ERR_ARG, "null pointer");
   std::lock_guard<std::mutex> lk(c->mu);

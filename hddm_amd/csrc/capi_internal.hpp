@@ -225,6 +225,9 @@ struct wfpt_ctx {
   DevBuf<unsigned long long> phase;  // engine phase cycles (diagnostic builds)
   DevBuf<int> defer;         // dmat_cdf_array: deferred trial indices + count
   DevBuf<double> cdf_tab;    // dmat_cdf_array: the call's parameter-only tables
+  DevBuf<double> rows_in;    // dmat_cdf_rows: the call's rows | x | freq_obs | n_samples, packed
+  DevBuf<double> rows_out;   // ... and its cdf | chisq | gsq
+  std::vector<double> rows_host;  // host side of both (one copy each way)
   DevBuf<int64_t> nd_idx;    // wiener_like_nodes: deferred trial indices
   DevBuf<int64_t> rare_v;    // wiener_like_nodes: the rare trials (wfpt_kernels.hip: NodeRare)
   DevBuf<int32_t> rare_j;

@@ -16,6 +16,10 @@
 //   cdf_wave_kernel  one wave per deferred trial: the terms of 64 consecutive
 //                    v in parallel (sequential accumulation in v order), or
 //                    the 36 + 6 window-branch series one per lane.
+// dmat_cdf_rows (the quantile objectives, likelihoods.py:200-239) has a kernel
+// of its own, cdf_rows_kernel: one block per row of (parameters, a few RT
+// edges, bin counts), no per-call tables, the same helpers and so the same
+// values.
 //
 // Numerics: every basic operation follows the reference's expression order
 // (-ffp-contract=off), and the transcendental calls are the reference's
@@ -230,6 +234,31 @@ __device__ inline double beyond_F(double h2, const CdfTrial& T, const CdfPar& P)
   return ((T.p0 * (1 - T.x)) + (T.p1 * T.x)) - (((h2 * 4) * kCPi) / ((a2 * P.sZ) * P.st));  // :148
 }
 
+// One round of the series beyond the window: lane j holds term v0 + j. The 64
+// additions run without a test between them (lane j keeps the sum after term
+// j), then every lane tests its own step at once and the first converged step
+// ends the series: the same sums and the same stopping term as one test per
+// step (cdfdif.c:128-147). h1, h2: the last two partial sums, advanced to the
+// stopping term (or the round's last); true = converged.
+__device__ inline bool beyond_round(double term, int v0, int lane, double& h1, double& h2) {
+  const int m = (kVMax - v0 < 64) ? kVMax - v0 : 64;
+  double h = h2, hk = 0.0;
+#pragma unroll
+  for (int j = 0; j < 64; ++j) {
+    h = h + bcast_lane(term, j);
+    hk = lane == j ? h : hk;
+  }
+  const double up1 = __shfl(hk, (lane + 63) & 63, 64), up2 = __shfl(hk, (lane + 62) & 63, 64);
+  const double hm1 = lane >= 1 ? up1 : h2;
+  const double hm2 = lane >= 2 ? up2 : (lane == 1 ? h2 : h1);
+  const unsigned long long cb = __ballot(lane < m && converged(hm2, hm1, hk));
+  const int last = cb ? __ffsll((long long)cb) - 1 : m - 1;
+  const double n1 = __shfl(hk, last > 0 ? last - 1 : 0, 64);
+  h1 = last == 0 ? h2 : n1;
+  h2 = __shfl(hk, last, 64);
+  return cb != 0ull;
+}
+
 // Window branch, drift node m with |gk| > eps, start-point node i: the
 // increment of sum_z (cdfdif.c:161-182). Term v of its series is
 // (v sin(sifa zzz)) exp(-denom/2 (t - lower_t) - 2 log(denom)), where only
@@ -307,9 +336,12 @@ __device__ inline double window_vs(int v, double zzz, double a) {
   return v * sin(sifa * zzz);
 }
 
+// kTabled = false (cdf_rows_kernel: no per-call tables, W and WS null): every
+// term is computed, the same operations.
+template <bool kTabled>
 __device__ inline double window_mi(int m, int i, const CdfTrial& T, const CdfPar& P,
                                    const CdfShared& S, const CdfWinTable* __restrict__ W,
-                                   const CdfWinStage& WS) {
+                                   const CdfWinStage* WS) {
   const double a = P.a, a2 = a * a, st = P.st, t = T.t, lower_t = T.lower_t;
   const int x = T.x, sg = T.sg, sh = T.sh;
   const double g = S.gk[m];
@@ -326,13 +358,13 @@ __device__ inline double window_mi(int m, int i, const CdfTrial& T, const CdfPar
   bool done = false;
   for (int v0 = 0; v0 < kVMax && !done; v0 += kWinChunk) {
     double term[kWinChunk];
-    if (v0 < kWinStage) {
+    if (kTabled && v0 < kWinStage) {
 #pragma unroll
       for (int u = 0; u < kWinChunk; ++u) {
         const int v = v0 + u;
-        term[u] = WS.vs[v][x][i] * exp((WS.dh[v][m] * tl) - WS.l2[v][m]);
+        term[u] = WS->vs[v][x][i] * exp((WS->dh[v][m] * tl) - WS->l2[v][m]);
       }
-    } else if (v0 < kWinTerms) {
+    } else if (kTabled && v0 < kWinTerms) {
 #pragma unroll
       for (int u = 0; u < kWinChunk; ++u) {
         const int v = v0 + u;
@@ -392,6 +424,25 @@ __device__ inline double window_m0(const CdfTrial& T, const CdfPar& P) {
     }
   }
   return (((400 * a2) * a) * ((sl - su) - h2)) / (st * sZ);
+}
+
+// F inside the window from the wave's series: lane m*6+i holds window_mi of
+// (m, i), lane 36+m window_m0 of a drift node ~ 0; sum_z and sum_nu in the
+// reference's order (cdfdif.c:155-210).
+__device__ inline double window_F(double val, const CdfTrial& T, const CdfShared& S) {
+  double sum_nu = 0;
+#pragma unroll
+  for (int m = 0; m < 6; ++m) {
+    double sum_z = 0;
+    if (fabs(S.gk[m]) > kEps) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) sum_z += bcast_lane(val, m * 6 + i);
+    } else {
+      sum_z = bcast_lane(val, 36 + m);
+    }
+    sum_nu += sum_z * S.w_gh[m];
+  }
+  return ((T.p0 * (1 - T.x)) + (T.p1 * T.x)) - sum_nu;  // cdfdif.c:210
 }
 
 // cdfdif.c:218 (a NaN ends as 0 too), then the wrapper's fold and outlier mix
@@ -574,11 +625,7 @@ __global__ __launch_bounds__(64) void cdf_wave_kernel(const double* xs, CdfPar P
     const CdfTrial T = cdf_prepare(fabs(xi), xi > 0, P, S);
     double F;
     if (T.branch == 1) {
-      // h1, h2: the last two partial sums (the reference's sequential
-      // additions, cdfdif.c:128-147). Per round the 64 additions run without
-      // a test between them (lane j keeps the sum after term j), then every
-      // lane tests its own step at once and the first converged step ends the
-      // series: the same sums and the same stopping term as one test per step.
+      // h1, h2: the last two partial sums (beyond_round)
       double h1 = 0, h2 = 0;
       bool conv = false;
       // the table's factors of the next round are loaded one round ahead, so
@@ -618,22 +665,7 @@ __global__ __launch_bounds__(64) void cdf_wave_kernel(const double* xs, CdfPar P
         } else if (v < kVMax) {
           term = beyond_term(v, T, P, S);
         }
-        const int m = (kVMax - v0 < 64) ? kVMax - v0 : 64;
-        double h = h2, hk = 0.0;
-#pragma unroll
-        for (int j = 0; j < 64; ++j) {
-          h = h + bcast_lane(term, j);
-          hk = lane == j ? h : hk;
-        }
-        const double up1 = __shfl(hk, (lane + 63) & 63, 64), up2 = __shfl(hk, (lane + 62) & 63, 64);
-        const double hm1 = lane >= 1 ? up1 : h2;
-        const double hm2 = lane >= 2 ? up2 : (lane == 1 ? h2 : h1);
-        const unsigned long long cb = __ballot(lane < m && converged(hm2, hm1, hk));
-        const int last = cb ? __ffsll((long long)cb) - 1 : m - 1;
-        conv = cb != 0ull;
-        h1 = __shfl(hk, last > 0 ? last - 1 : 0, 64);
-        if (last == 0) h1 = h2;
-        h2 = __shfl(hk, last, 64);
+        conv = beyond_round(term, v0, lane, h1, h2);
       }
       F = beyond_F(h2, T, P);
     } else {
@@ -645,25 +677,145 @@ __global__ __launch_bounds__(64) void cdf_wave_kernel(const double* xs, CdfPar P
       double val = 0.0;
       if (lane < 36) {
         const int m = lane / 6, i = lane % 6;
-        if (fabs(S.gk[m]) > kEps) val = window_mi(m, i, T, P, S, W, WS);
+        if (fabs(S.gk[m]) > kEps) val = window_mi<true>(m, i, T, P, S, W, &WS);
       } else if (lane < 42) {
         if (!(fabs(S.gk[lane - 36]) > kEps)) val = window_m0(T, P);
       }
-      double sum_nu = 0;
-#pragma unroll
-      for (int m = 0; m < 6; ++m) {
-        double sum_z = 0;
-        if (fabs(S.gk[m]) > kEps) {
-#pragma unroll
-          for (int i = 0; i < 6; ++i) sum_z += bcast_lane(val, m * 6 + i);
-        } else {
-          sum_z = bcast_lane(val, 36 + m);
-        }
-        sum_nu += sum_z * S.w_gh[m];
-      }
-      F = ((T.p0 * (1 - T.x)) + (T.p1 * T.x)) - sum_nu;  // cdfdif.c:210
+      F = window_F(val, T, S);
     }
     if (lane == 0) out[idx] = cdf_output(F, xi, p_outlier, w_outlier, S);
+  }
+}
+
+// dmat_cdf_rows: R rows, each with its own parameters, E signed RT edges and
+// E + 1 observed bin counts (the quantile objectives of likelihoods.py:200-239).
+// One block per row, rows grid-strided. The block builds the row's CdfShared
+// and the beyond-window factors of v < 64 in LDS (what cdf_table_kernel
+// writes for the whole call, here for one round: a row has few edges and its
+// parameters change with every call, so the 26,000-double tables would be the
+// whole cost), then each wave takes edges in turn: the wave pass's rounds
+// beyond the window (LDS factors first, beyond_term past them), the 36 + 6
+// window series one per lane with computed terms. The helpers are those of the
+// kernels above, so cdf[r][e] is dmat_cdf_array's value bit for bit. The
+// statistics are summed by one lane in bin order; no atomics anywhere, so a
+// row's results depend on neither its position nor R.
+constexpr int kRowEdges = 64;  // E <= kRowEdges
+struct CdfRowTable {
+  double dh[6][64];       // -denom(v, m) / 2
+  double lx[6][64];       // log(1 - exp(dh * st_window))
+  double fact[2][6][64];  // fact(v, m) per boundary x
+};
+
+__global__ __launch_bounds__(kCdfBlock) void cdf_rows_kernel(
+    const wfpt_params* __restrict__ rows, const double* __restrict__ xs,
+    const double* __restrict__ freq, const double* __restrict__ nsamp, int64_t R, int E,
+    double w_outlier, double* __restrict__ cdf, double* __restrict__ chisq,
+    double* __restrict__ gsq) {
+  __shared__ CdfShared S;
+  __shared__ CdfRowTable L;
+  __shared__ double theo[kRowEdges], cterm[kRowEdges + 1], gterm[kRowEdges + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int64_t r = blockIdx.x; r < R; r += gridDim.x) {
+    __syncthreads();  // the previous row's LDS is read to its end
+    const wfpt_params Q = rows[r];
+    const double po = Q.p_outlier;
+    // cdfdif_wrapper.pyx:23-25 negated, so a NaN anywhere fails it too
+    const bool ok = (Q.sv >= 0) && (Q.a > 0) && (Q.z >= 0) && (Q.z <= 1) && (Q.sz >= 0) &&
+                    (Q.sz <= 1) && (Q.z + Q.sz / 2. <= 1) && (Q.z - Q.sz / 2. >= 0) &&
+                    (Q.t - Q.st / 2. >= 0) && (Q.t >= 0) && (Q.st >= 0) && (po >= 0) &&
+                    (po <= 1) && (Q.v == Q.v);
+    if (!ok) {  // block-uniform; likelihoods.py:220-223, 235-238
+      if (cdf && tid < E) cdf[r * E + tid] = __longlong_as_double(0x7ff8000000000000ll);
+      if (chisq && tid == 0) {
+        chisq[r] = __longlong_as_double(0x7ff0000000000000ll);
+        gsq[r] = __longlong_as_double((long long)0xfff0000000000000ull);
+      }
+      continue;
+    }
+    const double epsi = 1e-10;  // cdfdif_wrapper.pyx:35-42
+    CdfPar P;
+    P.a = Q.a / 10.;
+    P.Ter = Q.t;
+    P.eta = Q.sv / 10. + epsi;
+    P.z = Q.z * (Q.a / 10.);
+    P.sZ = Q.sz * (Q.a / 10.) + epsi;
+    P.st = Q.st + epsi;
+    P.nu = Q.v / 10.;
+    cdf_setup(P, S);
+    {
+      const double a2 = P.a * P.a;
+      const double width = (P.Ter + (P.st / 2)) - (P.Ter - (P.st / 2));  // upper_t - lower_t
+      for (int k = tid; k < 2 * 6 * 64; k += kCdfBlock) {
+        const int x = k / 384, m = (k % 384) / 64, v = k % 64;
+        const double denom = beyond_denom(v, S.gk[m], a2);
+        const double dh = -.5 * denom;
+        L.fact[x][m][v] = beyond_fact(v, m, x, denom, P, S);
+        if (x == 0) {
+          L.dh[m][v] = dh;
+          L.lx[m][v] = beyond_lx(dh, width);
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = wave; e < E; e += kCdfBlock / 64) {
+      const double xi = xs[r * E + e];
+      const CdfTrial T = cdf_prepare(fabs(xi), xi > 0, P, S);
+      double F = 0.0;
+      if (T.branch == 1) {
+        const double t_up = T.t - T.upper_t;
+        double h1 = 0, h2 = 0;
+        bool conv = false;
+        for (int v0 = 0; v0 < kVMax && !conv; v0 += 64) {
+          const int v = v0 + lane;
+          double term = 0.0;
+          if (v0 == 0) {
+            double sum_nu = 0;
+#pragma unroll
+            for (int m = 0; m < 6; ++m)
+              sum_nu += L.fact[T.x][m][v] * exp((L.dh[m][v] * t_up) + L.lx[m][v]);
+            term = v * sum_nu;
+          } else if (v < kVMax) {
+            term = beyond_term(v, T, P, S);
+          }
+          conv = beyond_round(term, v0, lane, h1, h2);
+        }
+        F = beyond_F(h2, T, P);
+      } else if (T.branch == 2) {
+        double val = 0.0;
+        if (lane < 36) {
+          const int m = lane / 6, i = lane % 6;
+          if (fabs(S.gk[m]) > kEps) val = window_mi<false>(m, i, T, P, S, nullptr, nullptr);
+        } else if (lane < 42) {
+          if (!(fabs(S.gk[lane - 36]) > kEps)) val = window_m0(T, P);
+        }
+        F = window_F(val, T, S);
+      }
+      if (lane == 0) {
+        const double y = cdf_output(F, xi, po, w_outlier, S);
+        theo[e] = y;
+        if (cdf) cdf[r * E + e] = y;
+      }
+    }
+    if (!chisq) continue;  // block-uniform
+    __syncthreads();
+    if (tid <= E) {  // bin k of theo = [0, cdf, 1] (likelihoods.py:205-213)
+      const double lo = tid > 0 ? theo[tid - 1] : 0.0, hi = tid < E ? theo[tid] : 1.0;
+      double p = hi - lo;
+      if (p <= 1e-6) p = 1e-6;
+      const double f = freq[r * (E + 1) + tid], ex = p * nsamp[r];
+      cterm[tid] = ((f - ex) * (f - ex)) / ex;
+      gterm[tid] = f * log(p);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double cs = 0, gs = 0;
+      for (int k = 0; k <= E; ++k) {
+        cs += cterm[k];
+        gs += gterm[k];
+      }
+      chisq[r] = cs;
+      gsq[r] = 2 * gs;  // likelihoods.py:239
+    }
   }
 }
 
@@ -712,6 +864,19 @@ void launch_dmat_cdf(const double* x, int64_t n, const double par[7], double p_o
   const int64_t gw = n < WFPT_CDF_WAVES ? n : WFPT_CDF_WAVES;
   hipLaunchKernelGGL(cdf_wave_kernel, dim3(gw), dim3(64), 0, s, x, P, T, W, B, p_outlier,
                      w_outlier, out, defer, n_defer);
+}
+
+// dmat_cdf_rows over device arrays: rows[R], x[R][E], freq[R][E + 1],
+// n_samples[R] -> cdf[R][E] (nullable), chisq[R], gsq[R] (null together with
+// freq and n_samples: CDF values only). 1 <= E <= kCdfRowsMaxEdges.
+void launch_dmat_cdf_rows(const wfpt_params* rows, const double* x, const double* freq,
+                          const double* n_samples, int64_t R, int E, double w_outlier,
+                          double* cdf, double* chisq, double* gsq, hipStream_t s) {
+  static_assert(kRowEdges == kCdfRowsMaxEdges, "kCdfRowsMaxEdges");
+  if (R <= 0) return;
+  const int64_t nb = R < kCdfRowsGrid ? R : kCdfRowsGrid;
+  hipLaunchKernelGGL(cdf_rows_kernel, dim3(nb), dim3(kCdfBlock), 0, s, rows, x, freq, n_samples,
+                     R, E, w_outlier, cdf, chisq, gsq);
 }
 
 }  // namespace wfpt

@@ -221,4 +221,11 @@ constexpr int kCdfTableDoubles = 1344 + 512 * 48;  // per-call tables of launch_
 void launch_dmat_cdf(const double* x, int64_t n, const double par[7], double p_outlier,
                      double w_outlier, double* out, double* tab, int* defer, int* n_defer,
                      hipStream_t s);
+// dmat_cdf_rows: one block per row (own parameters, E edges, E + 1 bin
+// counts), rows striding over a grid of at most kCdfRowsGrid blocks.
+constexpr int kCdfRowsMaxEdges = 64;
+constexpr int kCdfRowsGrid = 2048;
+void launch_dmat_cdf_rows(const wfpt_params* rows, const double* x, const double* freq,
+                          const double* n_samples, int64_t R, int E, double w_outlier,
+                          double* cdf, double* chisq, double* gsq, hipStream_t s);
 }  // namespace wfpt

@@ -244,6 +244,7 @@ class HDDM:
             self.node_unit[fam] = self.node_subj * n_lv + lv_codes
             self.n_units[fam] = self.n_subj * n_lv
         self.dataset = self._make_dataset(rt, node_codes, device)
+        self.signed_rt, self.node_codes = rt, node_codes  # optimize()'s quantile statistics
         self.n_trials = rt.size
         self.node_counts = np.bincount(node_codes, minlength=self.n_nodes).astype(np.int64)
         self.likelihood_calls = 0
@@ -485,6 +486,62 @@ class HDDM:
                       "2.5q": float(np.quantile(v, .025)), "97.5q": float(np.quantile(v, .975))}
         return out
 
+    # -- point fits --------------------------------------------------------------
+    def set_values(self, values):
+        """Set group-level values by gen_stats()' node names ('a', 'v(c1)',
+        'sv', ...). With one subject the subject-level value follows its group
+        node, so the next sample() -- or optimize() -- starts there."""
+        slots = {}
+        for fam in self.FAMILIES:
+            for k, lv in enumerate(self.levels[fam]):
+                slots[fam + (f"({','.join(map(str, lv))})" if lv else "")] = (fam, k)
+        for name, val in values.items():
+            if name in slots:
+                fam, k = slots[name]
+                self.group[fam][k] = float(val)
+                if self.n_subj == 1:
+                    self.subj[fam] = self.subj[fam].copy()
+                    self.subj[fam][k] = float(val)
+            elif name in ("sv", "sz", "st") and name in self.include:
+                self.inter[name] = float(val)
+            else:
+                raise KeyError(f"no group-level node named {name!r}")
+
+    def optimize(self, method, quantiles=(.1, .3, .5, .7, .9), n_runs=3, n_bootstraps=0,
+                 seed=None):
+        """Point fit of the flat model by 'ML', 'chisquare' or 'gsquare'
+        (hddm/models/base.py:114-308); returns {node name: value} in
+        gen_stats()' names: one value per (family, condition level) of a, v, t
+        and one per included sv, sz, st (z = 0.5).
+
+        'chisquare' / 'gsquare': the quantile statistics of each observed node
+        (several subjects: pooled per condition, the reference's average model)
+        against the DMAT CDF at the node's RT quantiles; every evaluation is one
+        `cdfdif_wrapper.dmat_cdf_rows` launch over the rows. 'ML': minus the
+        summed node likelihoods; one subject only (TypeError otherwise).
+        n_runs restarts of Powell's method from the current group-level values
+        (later ones perturbed), the best wins. After 'gsquare' `bic_info` holds
+        likelihood, penalty and bic. With one subject the result becomes the
+        model's values; a group model's values stay as they are.
+
+        n_bootstraps > 0 (quantile methods): that many resamples of the trials
+        are refitted in lockstep from the main fit, `bootstrap_stats` gets
+        describe() plus the 2.5% and 97.5% rows. seed: generator seed of the
+        restarts and the resampling (default: the model's rng)."""
+        from . import optimize as _opt
+        return _opt.optimize(self, method, quantiles=quantiles, n_runs=n_runs,
+                             n_bootstraps=n_bootstraps, seed=seed)
+
+    def quantile_objective(self, method, quantiles=(.1, .3, .5, .7, .9)):
+        """The 'chisquare' / 'gsquare' objective of optimize() at the current
+        group-level values."""
+        from . import optimize as _opt
+        if method not in ("chisquare", "gsquare"):
+            raise ValueError("quantile_objective: method must be 'chisquare' or 'gsquare'")
+        flat = _opt._FlatModel(self)
+        stats = flat.row_stats(self.signed_rt, self.node_codes, quantiles)
+        return float(_opt._quantile_scores(flat, method, flat.current()[None], *stats)[0])
+
     def post_pred_rows(self, samples=500):
         """The kept sweeps a posterior predictive draws from and their node
         parameters: (picked, table) with `picked` the indices of `samples`
@@ -652,6 +709,9 @@ class HDDMChains(HDDM):
 
     def node_table(self, over=None):
         raise NotImplementedError("HDDMChains: node_tables() holds one table per chain")
+
+    def optimize(self, *args, **kw):
+        raise NotImplementedError("HDDMChains: point fits take one chain (HDDM)")
 
     def post_pred_rows(self, samples=500):
         raise NotImplementedError("HDDMChains: posterior predictive draws take one chain (HDDM)")

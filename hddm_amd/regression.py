@@ -393,6 +393,9 @@ class HDDMRegressor(HDDM):
         self.sample_seconds = time.perf_counter() - t0
         return self.trace
 
+    def optimize(self, *args, **kw):
+        raise NotImplementedError("the regressor's point fits are not implemented")
+
     def post_pred_rows(self, samples=500):
         raise NotImplementedError("the regressor's posterior predictive is not implemented")
 

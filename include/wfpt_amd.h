@@ -345,6 +345,25 @@ int wfpt_wiener_like_reg_groups_ex(wfpt_ctx *ctx, const wfpt_reg_ds *ds,
  * (the reference raises ValueError, cdfdif_wrapper.pyx:23-25). */
 int wfpt_dmat_cdf_array(wfpt_ctx *ctx, const double *x, int64_t n, const wfpt_params *p,
                         double w_outlier, double *out);
+/* The quantile objectives (hddm/likelihoods.py:200-239) for R rows in one
+ * launch. Row r has its own parameters rows[r], E signed RT edges x[r * E ..]
+ * (ascending: lower-boundary edges negative), E + 1 observed bin counts
+ * freq_obs[r * (E + 1) ..] and n_samples[r]; one w_outlier for the call.
+ *   out_cdf[R * E] (nullable)  bit for bit wfpt_dmat_cdf_array of x[r][e] with
+ *                              rows[r]
+ *   out_chisq[R]  sum_k (f_k - p_k n)^2 / (p_k n), k = 0..E in order, with
+ *                 p = diff([0, cdf, 1]) and p_k <= 1e-6 replaced by 1e-6
+ *   out_gsq[R]    2 sum_k f_k log(p_k)
+ * freq_obs, n_samples, out_chisq and out_gsq are null together (CDF values
+ * only). A row outside the support (cdfdif_wrapper.pyx:23-25, or with a NaN
+ * parameter) does not fail the call: its chisq is +inf, its gsq -inf and its
+ * cdf NaN, as the reference's `except ValueError` branches give; no other row
+ * changes. Results depend on neither a row's position nor R.
+ * WFPT_ERR_ARG: null pointers, R < 1, E outside 1..64. The RT range check of
+ * the reference wrapper is the caller's (hddm_amd.cdfdif_wrapper). */
+int wfpt_dmat_cdf_rows(wfpt_ctx *ctx, const wfpt_params *rows, const double *x,
+                       const double *freq_obs, const double *n_samples, int64_t R, int32_t E,
+                       double w_outlier, double *out_cdf, double *out_chisq, double *out_gsq);
 
 /* ---- multi-GPU: trials sharded over GPUs, RCCL all-reduce over xGMI ----- */
 /* (The reference has no multi-device path; SURVEY.md §8(e). Every entry point
