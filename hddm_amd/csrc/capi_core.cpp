@@ -581,7 +581,7 @@ int wfpt_dataset_create_ex(wfpt_ctx* c, const double* rt, int64_t n, const int32
   } else if (!keep_order) {
     // boundary first (x > 0 is the upper boundary, pdf.pxi:116), then |rt|:
     // the lean pass keeps a wave's root z grid in scalar registers when the
-    // wave holds one boundary (wfpt_kernels.hip: lean_kernel)
+    // wave holds one boundary (wfpt_level0.hip: lean_kernel)
     // (NaN RTs last in their group: a strict weak order for any input)
     stable_order(idx, rt, true);
   }

@@ -229,7 +229,7 @@ struct wfpt_ctx {
   DevBuf<double> rows_out;   // ... and its cdf | chisq | gsq
   std::vector<double> rows_host;  // host side of both (one copy each way)
   DevBuf<int64_t> nd_idx;    // wiener_like_nodes: deferred trial indices
-  DevBuf<int64_t> rare_v;    // wiener_like_nodes: the rare trials (wfpt_kernels.hip: NodeRare)
+  DevBuf<int64_t> rare_v;    // wiener_like_nodes: the rare trials (wfpt_engine.hpp: NodeRare)
   DevBuf<int32_t> rare_j;
   DevBuf<wfpt::Params> nd_par;  // ... and their parameter rows
   DevBuf<int> nd_chunks;     // wiener_like_nodes: chunks the level-0 pass left to the chunk engine

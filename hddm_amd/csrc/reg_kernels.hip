@@ -7,7 +7,7 @@
 //                     non-regressed parameters, into per-trial arrays
 //
 // The densities are not computed here: the arrays go into the per-trial-
-// parameter pass (wfpt_kernels.hip: multi_fast_kernel / multi_kernel through
+// parameter pass (multi_fast_kernel / multi_kernel through
 // launch_multi_fast / launch_multi), the per-group sums come from
 // rl_kernels.hip's launch_rl_node_sum.
 #include <hip/hip_runtime.h>

@@ -9,28 +9,21 @@
 //   rl_node_sum_kernel  per-node sums in the single-node call's order
 //
 // The densities of the DDM variants are not computed here: the drift buffer
-// goes into the v slot of the per-trial-parameter pass (wfpt_kernels.hip:
-// multi_fast_kernel / multi_kernel through launch_multi_fast / launch_multi).
+// goes into the v slot of the per-trial-parameter pass (multi_fast_kernel /
+// multi_kernel through launch_multi_fast / launch_multi).
 #include <hip/hip_runtime.h>
 
 #include "rl_internal.h"
-#include "wfpt_device.hpp"
+#include "wfpt_kernel_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace wfpt {
 namespace {
 
-constexpr int kRlBlock = 256;    // lp_sum_kernel's block (wfpt_kernels.hip: kBlock)
 constexpr int kRlScanBlock = 64; // one wave: few segments still spread over the CUs
 constexpr int kRlSumBlock = 1024;  // finalize_kernel's block
 constexpr int kRlAhead = 8;        // steps whose inputs the scan loads ahead
-
-__device__ inline double rl_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // The Q recurrence. Bit-exact with the reference's arithmetic: the drift is one
 // subtraction and one multiplication, the update q + alfa * (f - q) three
@@ -90,13 +83,13 @@ __global__ __launch_bounds__(kRlScanBlock) void rl_scan_kernel(RlLayout L, RlRow
 // 2.718281828459**(.) - 1 terms (the reference's truncated base, not exp) or
 // one minus it by response; then the outlier mixture and the log. No a, no
 // integration knobs: the reference ignores them here.
-__global__ __launch_bounds__(kRlBlock) void rl_choice_kernel(const double* drift_c,
+__global__ __launch_bounds__(kBlock) void rl_choice_kernel(const double* drift_c,
                                                              const unsigned char* resp_c,
                                                              int64_t m, double z, double p_outlier,
                                                              double wp_outlier, double* lp,
                                                              double* part, int* zeros) {
-  __shared__ double ss[kRlBlock / 64];
-  const int64_t i = (int64_t)blockIdx.x * kRlBlock + threadIdx.x;
+  __shared__ double ss[kBlock / 64];
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double s = 0.0;
   if (i < m) {
     const double drift = drift_c[i];
@@ -112,8 +105,8 @@ __global__ __launch_bounds__(kRlBlock) void rl_choice_kernel(const double* drift
     s = log_val(p);  // p == 0: -inf, the whole sum's value (wfpt.pyx:224-225)
     lp[i] = s;
   }
-  // lp_sum_kernel's order (wfpt_kernels.hip: block_reduce)
-  s = rl_wave_sum(s);
+  // lp_sum_kernel's order (block_reduce)
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) ss[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -122,10 +115,10 @@ __global__ __launch_bounds__(kRlBlock) void rl_choice_kernel(const double* drift
   }
 }
 
-__global__ __launch_bounds__(kRlBlock) void rl_fill_kernel(const int32_t* node_c, int64_t m,
+__global__ __launch_bounds__(kBlock) void rl_fill_kernel(const int32_t* node_c, int64_t m,
                                                            const Params* P, int mask,
                                                            double* dst) {
-  const int64_t i = (int64_t)blockIdx.x * kRlBlock + threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= m) return;
   const double* row = reinterpret_cast<const double*>(P + node_c[i]);
   int slot = 0;
@@ -141,7 +134,7 @@ __global__ __launch_bounds__(kRlBlock) void rl_fill_kernel(const int32_t* node_c
 // first partial of node j in the scratch array: the nodes' ranges
 // ceil(m_j / 256) never overlap (floor(off[j + 1] / 256) - floor(off[j] / 256)
 // + 1 >= ceil((off[j + 1] - off[j]) / 256))
-__device__ inline int64_t rl_partial_base(int64_t off, int32_t j) { return off / kRlBlock + j; }
+__device__ inline int64_t rl_partial_base(int64_t off, int32_t j) { return off / kBlock + j; }
 
 // One block per node. First the node's 256-trial block sums exactly as
 // lp_sum_kernel forms them over the single-node call's compact array (block b
@@ -155,23 +148,23 @@ __global__ __launch_bounds__(kRlSumBlock) void rl_node_sum_kernel(const double* 
   __shared__ double sw[kRlSumBlock / 64];
   const int32_t j = blockIdx.x;
   const int64_t lo = off[j], hi = off[j + 1];
-  const int64_t nb = (hi - lo + kRlBlock - 1) / kRlBlock;
+  const int64_t nb = (hi - lo + kBlock - 1) / kBlock;
   double* part = scratch + rl_partial_base(lo, j);
   const int t = threadIdx.x, w = t >> 6, g = t >> 8;  // g: the 256-lane group of the thread
-  for (int64_t b0 = 0; b0 < nb; b0 += kRlSumBlock / kRlBlock) {
+  for (int64_t b0 = 0; b0 < nb; b0 += kRlSumBlock / kBlock) {
     const int64_t b = b0 + g;
-    const int64_t i = lo + b * kRlBlock + (t & (kRlBlock - 1));
+    const int64_t i = lo + b * kBlock + (t & (kBlock - 1));
     double v = (b < nb && i < hi) ? lp[i] : 0.0;
-    v = rl_wave_sum(v);
+    v = wave_sum(v);
     if ((t & 63) == 0) sw[w] = v;
     __syncthreads();
-    if ((t & (kRlBlock - 1)) == 0 && b < nb)
+    if ((t & (kBlock - 1)) == 0 && b < nb)
       part[b] = ((sw[4 * g] + sw[4 * g + 1]) + (sw[4 * g + 2] + sw[4 * g + 3]));
     __syncthreads();
   }
   double s = 0.0;
   for (int64_t b = t; b < nb; b += kRlSumBlock) s += part[b];
-  s = rl_wave_sum(s);
+  s = wave_sum(s);
   if ((t & 63) == 0) sw[w] = s;
   __syncthreads();
   if (t == 0) {
@@ -194,20 +187,20 @@ void launch_rl_scan(const RlLayout& L, const RlRow& one, const RlRow* rows, cons
 void launch_rl_choice(const double* drift_c, const unsigned char* resp_c, int64_t m, double z,
                       double p_outlier, double wp_outlier, double* lp, double* part, int* zeros,
                       hipStream_t s) {
-  const int64_t nb = (m + kRlBlock - 1) / kRlBlock;
+  const int64_t nb = (m + kBlock - 1) / kBlock;
   if (nb == 0) return;
-  hipLaunchKernelGGL(rl_choice_kernel, dim3(nb), dim3(kRlBlock), 0, s, drift_c, resp_c, m, z,
+  hipLaunchKernelGGL(rl_choice_kernel, dim3(nb), dim3(kBlock), 0, s, drift_c, resp_c, m, z,
                      p_outlier, wp_outlier, lp, part, zeros);
 }
 
 void launch_rl_fill(const int32_t* node_c, int64_t m, const Params* P, int mask, double* dst,
                     hipStream_t s) {
-  const int64_t nb = (m + kRlBlock - 1) / kRlBlock;
+  const int64_t nb = (m + kBlock - 1) / kBlock;
   if (nb == 0 || (mask & 0x7e) == 0) return;
-  hipLaunchKernelGGL(rl_fill_kernel, dim3(nb), dim3(kRlBlock), 0, s, node_c, m, P, mask, dst);
+  hipLaunchKernelGGL(rl_fill_kernel, dim3(nb), dim3(kBlock), 0, s, node_c, m, P, mask, dst);
 }
 
-static_assert(kRlBlock == 256, "rl_node_partials (rl_internal.h) counts 256-trial blocks");
+static_assert(kBlock == 256, "rl_node_partials (rl_internal.h) counts 256-trial blocks");
 
 void launch_rl_node_sum(const double* lp, const int64_t* off, int32_t n_nodes, double* scratch,
                         double* res, hipStream_t s) {

@@ -11,7 +11,7 @@
 //     branch and K, sqrt/log terms, sv normalisers) is hoisted out of the z
 //     integral: one `TNode` per t node serves all z nodes;
 //   * adaptive trees up to kTreeDepth levels per axis complete inside the
-//     wave that owns the trial (engine_kernel, wfpt_kernels.hip: tree_node /
+//     wave that owns the trial (engine_kernel, wfpt_engine.hip: tree_node /
 //     tree_value over the dyadic points); deeper trees continue on a
 //     per-lane walk with an explicit stack (adaptive_walk).
 // Compiled with -ffp-contract=off: no FMA contraction, like the x86-64 build
@@ -1341,7 +1341,7 @@ __device__ inline bool tnode_pdf_sv_grid5(const TNode& T, const ZGrid& G, double
 //
 // Node order used below: lb, d, c, e, ub of an interval (integrate.pxi:114-141
 // prologue nodes lb, c, ub + the root aux nodes d, e). The level-0 engine
-// (wfpt_kernels.hip: engine_kernel) completes trees of up to kTreeDepth
+// (wfpt_engine.hip: engine_kernel) completes trees of up to kTreeDepth
 // refinement levels per axis in-wave (HDDM's n_st = n_sz = 2 default); deeper
 // trees continue on the per-lane walk (kFlagFallback). A tree's values live at
 // the kTreePoints dyadic points P_0..P_kTreeW of its root interval.

@@ -1,5 +1,5 @@
 // wfpt_internal.h — launcher interface between the C ABI (capi_*.cpp) and
-// the kernels (wfpt_kernels.hip). Not part of the public ABI.
+// the kernel units (wfpt_kernel_common.hpp lists them). Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,7 +35,7 @@ struct Work {
 
 constexpr int kPhaseWaves = 16384;
 
-// Heavy chunks of a resident dataset (wfpt_kernels.hip: engine_kernel). The
+// Heavy chunks of a resident dataset (wfpt_engine.hip: engine_kernel). The
 // engine records the chunks whose level 0 leaves more than kHeavyZ z walks
 // (next_*); the following call splits those chunks into kSplit units of
 // kSplitTrials trials, one wave each. All pointers null / n = 0: no split, no
@@ -81,8 +81,9 @@ bool has_deferred_pass(const Params& P, const Knobs& K);
 int64_t partials_for(int64_t n, const Params& P, const Knobs& K);
 
 // out_kind: 0 = partial {sum, zeros}; 1 = per-trial density (logp => log);
-// 2 = per-trial log p; 3 = 0's partials + each trial's log term in trial[n]
-// (the per-trial check of the summing kernels). part: kPassFast (level-0 pass, or the whole fixed
+// 3 = 0's partials + each trial's log term in trial[n] (the per-trial check
+// of the summing kernels). evals (nullable) counts evaluations for out_kind
+// 0 only: kinds 1 and 3 are non-counting. part: kPassFast (level-0 pass, or the whole fixed
 // Simpson kernel) | kPassDeferred (the deferred trials + fold). Adaptive
 // families only: kPassLean makes the level-0 pass the lean kernel (level 0
 // without the in-wave refinement; a chunk that refines is flagged in W.redo

@@ -1,0 +1,157 @@
+// wfpt_level0.hip — the level-0 passes of a resident call on gfx950:
+//   direct_kernel        the simple DDM (one pdf_sv per trial)
+//   lean_kernel<MODE>    level 0 of every trial of the adaptive families, one
+//                        64-trial chunk per wave; a chunk that refines is
+//                        flagged for the engine's redo pass (wfpt_engine.hip)
+// (One-block calls run level 0 and the finalize in one launch: wfpt_sum.hip.)
+#include "wfpt_kernel_common.hpp"
+
+#pragma clang fp contract(off)
+
+namespace wfpt {
+
+// Direct family (sz = st = 0): one pdf_sv per trial, one chunk of 64 trials
+// per wave. The level-0 pass takes the call's per-boundary constants
+// (DirectArgs: v, w, sin / 2cos(pi w), (-v) a w, 1 / a^2 computed once on the
+// host) instead of per-lane flips, sincospi and a division: the same outputs
+// as fast_level0<kDirect> bit for bit (direct_level0). As in the lean pass, a
+// wave's trials are taken by boundary (datasets are ordered by boundary, then
+// |rt|), so the constants are wave-uniform; only the wave at the boundary
+// switch takes the second call site.
+template <bool COUNT, int OUT>
+__global__ __launch_bounds__(kFastBlock, FastWaves<kDirect>::value > 0 ? FastWaves<kDirect>::value : 1)
+void direct_kernel(TrialArgs A, Work W, DirectArgs D) {
+  const int64_t i = (int64_t)blockIdx.x * kFastBlock + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const int64_t c = i >> 6;
+  if (c * 64 >= A.n) return;  // a wave past the last chunk (wave-uniform)
+  const bool own = i < A.n;
+  const double x0 = own ? A.x[i] : 0.0;
+  double p = 0.0;
+  long long ne = 0;
+  int flags = 0, oc = kFinal;
+  const bool pos = x0 > 0;
+  const unsigned long long bo = __ballot(own), bp = __ballot(own && pos);
+  const int b = (bp == bo) ? 1 : 0;  // every trial upper: 1; otherwise lower first
+  if (own && pos == (b != 0)) oc = direct_level0(x0, A.P, A.K, D, b, p, ne, flags);
+  if (bp != 0ull && bp != bo) {  // mixed wave: its upper-boundary lanes
+    if (own && pos) oc = direct_level0(x0, A.P, A.K, D, 1, p, ne, flags);
+  }
+  double lp = 0.0;
+  int zero = 0;
+  if (own && oc == kFinal) emit<OUT>(A, i, p, lp, zero);
+  const bool anyd = defer_slots(W, c, lane, oc != kFinal, kFlagExact);
+  if (sum_out(OUT)) {
+    lp = wave_sum(lp);
+    const int zs = __popcll(__ballot(zero != 0));
+    if (lane == 0) {
+      A.out[c] = lp;
+      A.zeros[c] = zs | (anyd ? kZeroDefer : 0);
+    }
+  }
+  if (COUNT) {
+    const long long nf = wave_sum_ll(oc == kFinal ? ne : 0);
+    if (lane == 0) atomicAdd(A.evals, (unsigned long long)nf);
+  }
+}
+
+// The engine's level 0 alone (kPassLean), for resident datasets whose last
+// call refined no chunk in-wave (the usual MCMC case at HDDM's knobs): no LDS,
+// no refinement code, so the register allocation and occupancy are those of
+// level 0 (FastWaves) instead of the engine's. Each lane runs eng_level0 on
+// the table's root z grid, i.e. the same operations on the same inputs as the
+// engine's level 0, and a chunk without refining trials leaves the bits the
+// engine would (chunk_out). A chunk with a refining trial writes nothing but
+// its redo flag and a nonzero deferred count; the engine's redo pass
+// (kPassRedo) then processes it from scratch, as a full engine call would.
+// Block size of the lean pass (WFPT_LEAN_BLOCK; its waves are independent:
+// one chunk each, no block-level exchange). The launch bound's second
+// argument is waves per SIMD (amdgpu_waves_per_eu), independent of the block
+// size, so the register budget is the same for every block size.
+#ifndef WFPT_LEAN_BLOCK
+#define WFPT_LEAN_BLOCK 256
+#endif
+constexpr int kLeanBlock = WFPT_LEAN_BLOCK;
+static_assert(kLeanBlock % 64 == 0 && kLeanBlock <= kFastBlock, "kLeanBlock");
+template <int MODE, bool COUNT, int OUT>
+__global__ __launch_bounds__(kLeanBlock, FastWaves<MODE>::value > 0 ? FastWaves<MODE>::value : 1)
+void lean_kernel(TrialArgs A, Work W, RootGrids R) {
+#ifdef WFPT_PHASE_TIMING
+  const long long rt0 = __builtin_amdgcn_s_memrealtime();
+#endif
+  const int64_t i = (int64_t)blockIdx.x * kLeanBlock + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const int64_t c = i >> 6;
+  if (c * 64 >= A.n) return;  // a wave past the last chunk (wave-uniform)
+  const bool own = i < A.n;
+  const double x0 = own ? A.x[i] : 0.0;
+  double p = 0.0, f0[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  long long ne0 = 0;
+  unsigned pend0 = 0u;
+  int oc = kFinal;
+  // The wave's trials by boundary. Inside one boundary the root z grid and
+  // the flipped v, z (pdf.pxi:116-118) are wave-uniform: they stay in scalar
+  // registers (zgrid_uniform) instead of per-lane selects and copies.
+  // Datasets are ordered by boundary, then |rt| (wfpt_dataset_create), so
+  // only the wave at the boundary switch is mixed: its upper-boundary lanes
+  // take the second call site.
+  const bool pos = x0 > 0;
+  const unsigned long long bo = __ballot(own), bp = __ballot(own && pos);
+  const int b = (bp == bo) ? 1 : 0;  // every trial upper: 1; otherwise lower first
+  if (own && pos == (b != 0))
+    oc = eng_level0_t<MODE, false, true>(trial_setup_b(x0, A.P, b != 0), A.P, A.K,
+                                         zgrid_uniform(R, b), p, f0, ne0, pend0, &R.S[b][0][0]);
+  if (bp != 0ull && bp != bo) {  // mixed wave: its upper-boundary lanes
+    if (own && pos)
+      oc = eng_level0_t<MODE, false, true>(trial_setup_b(x0, A.P, true), A.P, A.K, R.G[1], p, f0,
+                                           ne0, pend0, &R.S[1][0][0]);
+  }
+  if (__ballot(oc == kTree) != 0ull) {
+    if (lane == 0) {
+      W.redo[c] = 1;
+      // finalize reports the call as deferred: the host runs the redo pass
+      if (sum_out(OUT)) A.zeros[c] = kZeroDefer;
+    }
+    return;
+  }
+  chunk_out<COUNT, OUT>(A, W, c, lane, p, oc == kExact, kFlagExact, ne0);
+#ifdef WFPT_PHASE_TIMING
+  // per-wave start / end (the lean pass has no split units: every record)
+  if (lane == 0 && c < kPhaseWaves) {
+    unsigned long long* rec = W.phase + c * 8;
+    rec[0] = rt0;
+    rec[1] = __builtin_amdgcn_s_memrealtime();
+    unsigned hw;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    rec[2] = hw;
+    unsigned xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    rec[3] = xcc;
+  }
+#endif
+}
+
+// ---------------------------------------------------------------------------
+// launchers
+
+void launch_direct(bool count, int out, const TrialArgs& A, const Work& W, hipStream_t s) {
+  DirectArgs D;
+  direct_args(A.P, D);
+  with_build<true>(count, out, [&](auto c, auto o) {
+    hipLaunchKernelGGL((direct_kernel<decltype(c)::value, decltype(o)::value>),
+                       dim3(fast_blocks(A.n)), dim3(kFastBlock), 0, s, A, W, D);
+  });
+}
+
+void launch_lean(int mode, bool count, int out, const TrialArgs& A, const Work& W, hipStream_t s) {
+  RootGrids R;
+  root_grids(A.P, R);
+  with_value<kAdaptT, kAdaptTZ>(mode, [&](auto m) {
+    with_build<false>(count, out, [&](auto c, auto o) {
+      hipLaunchKernelGGL((lean_kernel<decltype(m)::value, decltype(c)::value, decltype(o)::value>),
+                         dim3((A.n + kLeanBlock - 1) / kLeanBlock), dim3(kLeanBlock), 0, s, A, W, R);
+    });
+  });
+}
+
+}  // namespace wfpt

@@ -2,7 +2,7 @@
 
 The per-node sums of `Dataset.wiener_like_nodes` reach a mapped host slot
 that the host reads as soon as the call's completion word appears
-(wfpt_kernels.hip: segment_publish_kernel). If any sum could land after the
+(wfpt_node.hip: segment_publish_kernel). If any sum could land after the
 word, the host would read the previous call's value for that node. This
 alternates two parameter tables A, B over config 4's 200 x 500 dataset and
 counts calls whose sums differ from the table's own sums (computed once,

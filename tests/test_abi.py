@@ -182,6 +182,18 @@ def test_build_switch_inventory():
     assert named <= found, sorted(named - found)
 
 
+def test_build_lists_cover_csrc():
+    """Every file under hddm_amd/csrc is in build.DEPS (the stale-build check
+    and source_digest read that list) and every translation unit there is in
+    build.SOURCES: a forgotten entry silently drops the file from both."""
+    from hddm_amd import build as hb
+    files = set(os.listdir(hb.CSRC))
+    assert files == set(hb.DEPS), sorted(files ^ set(hb.DEPS))
+    units = {f for f in files if f.endswith((".hip", ".cpp"))}
+    assert units == set(hb.SOURCES), sorted(units ^ set(hb.SOURCES))
+    assert len(hb.DEPS) == len(set(hb.DEPS)) and len(hb.SOURCES) == len(set(hb.SOURCES))
+
+
 @pytest.mark.gpu
 def test_close_detaches_live_datasets_of_every_kind(gpu):
     """One context, one dataset of each kind (plain, RL, regression) at n = 65

@@ -132,13 +132,15 @@ STRESS = [(-1.2388, 1.3918, 1.4387, 0.4995, 0.2891, 0.277, 0.0698),
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("knobs", [(1e-4, 2, 2, 1, 1e-3), (1e-6, 3, 3, 1, 1e-5),
-                                   (1e-4, 4, 4, 1, 1e-4)])
+                                   (1e-4, 4, 4, 1, 1e-4), (1e-4, 2, 2, 0, 1e-3)])
 def test_evaluation_counts_equal_reference(gpu, oracle_lib, knobs):
     """The quadrature trees are the reference's: the number of pdf_sv
     evaluations the library performs (level-0 pass + breadth-first levels +
     inner refinements, or the exact / per-lane path from scratch) equals the
     reference's count on the same data, exactly. Knob sets cover trees within
-    the breadth-first levels (depth 2) and deeper ones (per-lane walk)."""
+    the breadth-first levels (depth 2) and deeper ones (per-lane walk), and
+    fixed Simpson (use_adaptive = 0: the counting trial_kernel of the three
+    fixed families; the direct set stays direct)."""
     from hddm_amd import _lib
     ctx = _lib.context()
     err, n_st, n_sz, ua, se = knobs

@@ -226,6 +226,31 @@ def test_stress_sets_per_trial_every_sequence(gpu, oracle_lib, k):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("family", ["fixed_tz", "fixed_t", "fixed_z"])
+def test_fixed_simpson_per_trial(gpu, oracle_lib, family):
+    """Fixed composite Simpson (use_adaptive = 0) at n = 257, one 256-thread
+    block plus one trial: the summing trial_kernel, its per-trial build
+    (wiener_like_trials) on the same path with the same block partials, and
+    pdf_array, each term against the reference at the suite's 1e-6 bar."""
+    from hddm_amd import _lib
+    ctx = _lib.context()
+    p = {"fixed_tz": PINNED, "fixed_t": ST_ONLY, "fixed_z": SZ_ONLY}[family]
+    kn = (1e-4, 2, 2, 0, 1e-3, 0.05, 0.1)
+    np.random.seed(257)
+    x = gpu.gen_rts_from_cdf(*p, samples=257, dt=1e-3)
+    ref = ref_terms(oracle_lib, x, p, kn)
+    ds = gpu.Dataset(x)
+    tot, terms, path = summing_vs_trials(ctx, ds, p, kn)
+    assert path_names(path) == {"fixed"}, path_names(path)
+    assert_terms(terms, ref, family)
+    want = math.fsum(ref[np.isfinite(ref)])
+    assert abs(tot - want) <= 1e-9 * abs(want), (tot, want)
+    arr = gpu.pdf_array(x, *p, kn[0], 1, kn[1], kn[2], kn[3], kn[4], kn[5], kn[6])
+    assert_terms(arr, ref, family + " pdf_array")
+    ds.close()
+
+
+@pytest.mark.gpu
 def test_dataset_outliving_its_context(gpu):
     """Closing a context detaches its datasets (their device memory is
     released with it); destroying one afterwards frees only its host part and

@@ -1,7 +1,8 @@
 """Static ISA statistics of one kernel (device assembly via hipcc -S).
 
     python tools/isa_stats.py [kernel-substring] [-D...]
-Prints VGPR/SGPR counts, occupancy and the instruction histogram.
+Compiles the .hip units of hddm_amd.build.SOURCES in turn, with its CFLAGS,
+and stops at the first one that holds the kernel. Prints VGPR/SGPR counts, occupancy and the instruction histogram.
 """
 import collections
 import os
@@ -10,17 +11,22 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from hddm_amd.build import CFLAGS, CSRC, HIPCC, SOURCES  # noqa: E402
 
 
 def main():
-    pat = sys.argv[1] if len(sys.argv) > 1 else "fast_kernelILi3ELb0ELi0E"
+    pat = sys.argv[1] if len(sys.argv) > 1 else "lean_kernelILi3ELb0ELi0E"
     defs = [a for a in sys.argv[2:] if a.startswith("-D")]
     out = "/tmp/wfpt_isa.s"
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off",
-                    "-fno-fast-math", "--offload-arch=gfx950", "--cuda-device-only", "-S", *defs,
-                    "-o", out, os.path.join(ROOT, "hddm_amd/csrc/wfpt_kernels.hip")], check=True,
-                   stderr=subprocess.DEVNULL)
-    s = open(out).read()
+    for src in (u for u in SOURCES if u.endswith(".hip")):
+        subprocess.run([HIPCC, *CFLAGS, "--cuda-device-only", "-S", *defs, "-o", out,
+                        os.path.join(CSRC, src)], check=True, stderr=subprocess.DEVNULL)
+        s = open(out).read()
+        if re.search(r"^_Z\w*" + re.escape(pat) + r"\w*:", s, re.M):
+            break
+    else:
+        sys.exit(f"no kernel matches {pat}")
     for m in re.finditer(r"^(_Z\w*" + re.escape(pat) + r"\w*):", s, re.M):
         name = m.group(1)
         end = s.index(".Lfunc_end", m.end())

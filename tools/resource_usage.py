@@ -2,6 +2,7 @@
 compiler's own resource-usage remarks (the numbers the code object carries).
 
     python tools/resource_usage.py [name-filter ...] [-D NAME=VAL ...] [--src sim_kernels.hip]
+Without --src: every .hip unit of hddm_amd.build.SOURCES.
 """
 import os
 import re
@@ -10,7 +11,10 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "hddm_amd", "csrc", "wfpt_kernels.hip")
+sys.path.insert(0, ROOT)
+from hddm_amd.build import CSRC, SOURCES  # noqa: E402
+
+UNITS = [os.path.join(CSRC, s) for s in SOURCES if s.endswith(".hip")]
 FIELDS = ("VGPRs", "AGPRs", "SGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]",
           "LDS Size [bytes/block]")
 
@@ -21,7 +25,7 @@ def demangle(names):
     return out if len(out) == len(names) else names
 
 
-def usage(defines=(), src=SRC):
+def usage(defines=(), src=UNITS[0]):
     with tempfile.TemporaryDirectory() as td:
         cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
                "-fPIC", "--offload-arch=gfx950", *[f"-D{d}" for d in defines], "-c", src, "-o",
@@ -46,16 +50,16 @@ def usage(defines=(), src=SRC):
 
 def main():
     args = sys.argv[1:]
-    defines, filt, src = [], [], SRC
+    defines, filt, srcs = [], [], UNITS
     while args:
         a = args.pop(0)
         if a == "-D":
             defines.append(args.pop(0))
         elif a == "--src":  # another unit of hddm_amd/csrc
-            src = os.path.join(os.path.dirname(SRC), args.pop(0))
+            srcs = [os.path.join(CSRC, args.pop(0))]
         else:
             filt.append(a)
-    for r in usage(defines, src):
+    for r in (r for src in srcs for r in usage(defines, src)):
         if filt and not any(f in r["name"] for f in filt):
             continue
         print(f"{r['name'][:70]:70s} " + " ".join(f"{k.split()[0]}={r.get(k, '-')}" for k in FIELDS))
