@@ -7,7 +7,8 @@ i.e. thousands of tiny CPU likelihood calls per sweep. Neither kabuki nor
 PyMC is available here, so this module restates the model and its step
 methods around the batched GPU likelihood:
 
-* model (informative HDDM, hddm_info.py:121-140; families base.py:578-690):
+* model (informative HDDM, hddm_info.py:121-140; families base.py:578-690; as
+  data in MODEL / INTER below, which every sampler reads):
     a_subj ~ Gamma(mean=a, sd=a_std),  a ~ Gamma(mean 1.5, sd 0.75), a_std ~ HalfNormal(sd 2)
     v_subj ~ Normal(v, v_std),         v ~ Normal(2, sd 3),          v_std ~ HalfNormal(sd 2)
     t_subj ~ Gamma(mean=t, sd=t_std),  t ~ Gamma(mean .4, sd .2),    t_std ~ HalfNormal(sd 1)
@@ -31,16 +32,53 @@ tests/test_hierarchical.py.
 """
 import math
 import time
+from collections import namedtuple
 
 import numpy as np
 from scipy import special
 
 from . import wfpt as _wfpt
 
-SLICE_WIDTHS = {"a": 1, "t": 0.01, "a_std": 1, "t_std": 0.15, "sz": 1.1, "v": 1.5, "st": 0.1,
-                "sv": 3, "v_std": 1}  # hddm_info.py:103-105
 WIENER_PARAMS = {"err": 1e-4, "n_st": 2, "n_sz": 2, "use_adaptive": 1, "simps_err": 1e-3,
                  "w_outlier": 0.1}  # base.py:712-716
+
+# the columns of a parameter table (the likelihood's argument order)
+_COL = {"v": 0, "sv": 1, "a": 2, "z": 3, "sz": 4, "t": 5, "st": 6, "p_outlier": 7}
+
+# The model of the header as data: the ONE place to change a prior, a starting
+# value, a lower bound or a slice width. HDDM, HDDMChains, HDDMRegressor
+# (regression.py) and the flat model of optimize.py all read it. A density is
+# (kind, *parameters) for logpdf() below; its parameters stay Python numbers,
+# so the scalar fast paths of the densities see what they always saw.
+# group_prior: of the group mean; subject: density kind of the subject nodes
+# around it (gamma by mean and sd); std_sd: sd of the HalfNormal prior of the
+# std node; start: (group, subject, std); widths: slice width (value, std)
+Family = namedtuple("Family", "group_prior subject std_sd start lower widths")
+Inter = namedtuple("Inter", "prior start width")  # start: when included, else 0
+MODEL = {  # priors and starting values hddm_info.py:121-140, widths hddm_info.py:103-105
+    "a": Family(("gamma", 1.5, 0.75), "gamma", 2.0, (1.5, 1.0, 0.1), 0.0, (1, 1)),
+    "v": Family(("normal", 2.0, 3.0), "normal", 2.0, (2.0, 2.0, 0.1), None, (1.5, 1)),
+    "t": Family(("gamma", 0.4, 0.2), "gamma", 1.0, (0.4, 0.001, 0.2), 0.0, (0.01, 0.15)),
+}
+INTER = {
+    "sv": Inter(("halfnormal", 2.0), 1.0, 3),
+    "sz": Inter(("beta", 1, 3), 0.01, 1.1),
+    "st": Inter(("halfnormal", 0.3), 0.001, 0.1),
+}
+SLICE_WIDTHS = {**{f: s.widths[0] for f, s in MODEL.items()},
+                **{f + "_std": s.widths[1] for f, s in MODEL.items()},
+                **{n: s.width for n, s in INTER.items()}}
+
+
+def param_table(shape, cols, p_outlier):
+    """(*shape, 8) parameter table v, sv, a, z, sz, t, st, p_outlier with
+    shape = (..., n_nodes). cols: v, a, t already gathered per node and sv, sz,
+    st, each anything that broadcasts against `shape`. z = 0.5 (base.py:687-752)."""
+    P = np.empty(shape + (8,))
+    cols = dict(cols, z=0.5, p_outlier=p_outlier)
+    for name, col in _COL.items():
+        P[..., col] = cols[name]
+    return P
 
 
 # ---------------------------------------------------------------- log densities
@@ -78,6 +116,15 @@ def beta_logpdf(x, a, b):
     with np.errstate(divide="ignore", invalid="ignore"):
         out = (a - 1) * np.log(x) + (b - 1) * np.log1p(-x) - special.betaln(a, b)
     return np.where((x > 0) & (x < 1), out, -np.inf)
+
+
+LOGPDF = {"gamma": gamma_logpdf_mean_sd, "normal": normal_logpdf, "halfnormal": halfnormal_logpdf,
+          "beta": beta_logpdf}
+
+
+def logpdf(density, x):
+    """Log density at x of a (kind, *parameters) entry of MODEL / INTER."""
+    return LOGPDF[density[0]](x, *density[1:])
 
 
 # ---------------------------------------------------------------- slice sampler
@@ -184,6 +231,13 @@ def slice_step(x0, logp, w, rng, lower=None, max_steps=50, max_shrink=200, logp_
 
 # ---------------------------------------------------------------- the model
 
+def _refuses(reason):
+    """A method of a subclass that does not support what its parent offers."""
+    def method(self, *args, **kw):
+        raise NotImplementedError(reason)
+    return method
+
+
 class HDDM:
     """HDDM(data, depends_on={'v': 'cond'}).sample(n) on one MI355X.
 
@@ -193,6 +247,8 @@ class HDDM:
     """
 
     FAMILIES = ("a", "v", "t")
+    _COL = _COL
+    _trace_shape, _progress_note = (-1,), ""  # HDDMChains: (-1, C), " (C chains)"
 
     def __init__(self, data, depends_on=None, include=(), p_outlier=0.05, wiener_params=None,
                  seed=None, device=None, paired_probes=True):
@@ -204,12 +260,13 @@ class HDDM:
         self.depends = {k: ([v] if isinstance(v, str) else list(v))
                         for k, v in (depends_on or {}).items()}
         for k in self.depends:
-            if k not in self.FAMILIES + ("sv", "sz", "st"):
+            if k not in self.FAMILIES + tuple(INTER):
                 raise NotImplementedError(f"depends_on for '{k}' is not supported")
-        self.include = set(include) | {"a", "v", "t"}
-        unsupported = self.include - {"a", "v", "t", "sv", "sz", "st"}
+        self.include = set(include) | set(MODEL)
+        unsupported = self.include - set(MODEL) - set(INTER)
         if unsupported:
             raise NotImplementedError(f"include {sorted(unsupported)} is not supported")
+        self.inter_names = [name for name in INTER if name in self.include]
         self.p_outlier = float(p_outlier)
         self.wp = dict(WIENER_PARAMS if wiener_params is None else wiener_params)
         self.rng = np.random.default_rng(seed)
@@ -250,6 +307,8 @@ class HDDM:
         self.likelihood_calls = 0
         self.likelihood_seconds = 0.0
         self.call_stats = {}  # updated parameter -> [calls, seconds]
+        self.device_call_seconds = 0.0  # HDDMChains: inside the binding's calls
+        self.tables_evaluated = 0       # HDDMChains: tables over all launches
         self._init_values()
 
     def _make_dataset(self, rt, node_codes, device):
@@ -260,17 +319,30 @@ class HDDM:
     # -- state ---------------------------------------------------------------
     def _init_values(self):
         """Starting values of hddm_info.py:121-140."""
-        nl = {f: len(self.levels[f]) for f in self.FAMILIES}
-        self.group = {"a": np.full(nl["a"], 1.5), "v": np.full(nl["v"], 2.0),
-                      "t": np.full(nl["t"], 0.4)}
-        self.std = {"a": 0.1, "v": 0.1, "t": 0.2}
-        self.subj = {"a": np.full(self.n_units["a"], 1.0), "v": np.full(self.n_units["v"], 2.0),
-                     "t": np.full(self.n_units["t"], 0.001)}
-        self.inter = {"sv": 1.0 if "sv" in self.include else 0.0,
-                      "sz": 0.01 if "sz" in self.include else 0.0,
-                      "st": 0.001 if "st" in self.include else 0.0}
+        fams = self.FAMILIES
+        self.group = {f: np.full(len(self.levels[f]), MODEL[f].start[0]) for f in fams}
+        self.subj = {f: np.full(self.n_units[f], MODEL[f].start[1]) for f in fams}
+        self.std = {f: MODEL[f].start[2] for f in fams}
+        self.inter = {n: s.start if n in self.include else 0.0 for n, s in INTER.items()}
 
-    _COL = {"v": 0, "sv": 1, "a": 2, "sz": 4, "t": 5, "st": 6}
+    def group_nodes(self):
+        """(name, family, level index) of every group mean node in trace
+        order: 'a', 'v(c1)', ... -- the names of gen_stats(), set_values() and
+        optimize()."""
+        for fam in self.FAMILIES:
+            for k, lv in enumerate(self.levels[fam]):
+                yield fam + (f"({','.join(map(str, lv))})" if lv else ""), fam, k
+
+    def _table_of(self, lead, subj, inter):
+        """param_table (*lead, n_nodes, 8) of subject values subj[f] (*lead,
+        units) and sv / sz / st values inter[n], scalars or (*lead, 1). A
+        family the model does not have (a regressed outcome) is unused by the
+        likelihood: 0."""
+        cols = dict.fromkeys(MODEL, 0.0)
+        cols.update(inter)
+        for fam in self.FAMILIES:
+            cols[fam] = subj[fam].take(self.node_unit[fam], axis=-1)
+        return param_table(lead + (self.n_nodes,), cols, self.p_outlier)
 
     def node_table(self, over=None):
         """(n_nodes, 8) parameter table v, sv, a, z, sz, t, st, p_outlier. The
@@ -279,16 +351,7 @@ class HDDM:
         key = (self.subj["v"].tobytes(), self.subj["a"].tobytes(), self.subj["t"].tobytes(),
                self.inter["sv"], self.inter["sz"], self.inter["st"])
         if getattr(self, "_table_key", None) != key:
-            P = np.empty((self.n_nodes, 8))
-            P[:, 0] = self.subj["v"][self.node_unit["v"]]
-            P[:, 1] = self.inter["sv"]
-            P[:, 2] = self.subj["a"][self.node_unit["a"]]
-            P[:, 3] = 0.5
-            P[:, 4] = self.inter["sz"]
-            P[:, 5] = self.subj["t"][self.node_unit["t"]]
-            P[:, 6] = self.inter["st"]
-            P[:, 7] = self.p_outlier
-            self._table, self._table_key = P, key
+            self._table, self._table_key = self._table_of((), self.subj, self.inter), key
         if not over:
             return self._table
         P = self._table.copy()
@@ -297,16 +360,18 @@ class HDDM:
             P[:, col] = val[self.node_unit[name]] if name in self.FAMILIES else val
         return P
 
-    def node_logp(self, over=None):
-        t0 = time.perf_counter()
-        out = self.dataset.wiener_like_nodes(self.node_table(over), **self.wp)
-        dt = time.perf_counter() - t0
+    def _count_call(self, dt, key):
+        """Book one likelihood call of dt seconds under call_stats[key]."""
         self.likelihood_seconds += dt
         self.likelihood_calls += 1
-        key = ",".join(sorted(over)) if over else "-"
         st = self.call_stats.setdefault(key, [0, 0.0])
         st[0] += 1
         st[1] += dt
+
+    def node_logp(self, over=None):
+        t0 = time.perf_counter()
+        out = self.dataset.wiener_like_nodes(self.node_table(over), **self.wp)
+        self._count_call(time.perf_counter() - t0, ",".join(sorted(over)) if over else "-")
         return out
 
     def node_logp_multi(self, overs):
@@ -316,13 +381,7 @@ class HDDM:
         t0 = time.perf_counter()
         out = self.dataset.wiener_like_nodes_multi(np.stack([self.node_table(o) for o in overs]),
                                                    **self.wp)
-        dt = time.perf_counter() - t0
-        self.likelihood_seconds += dt
-        self.likelihood_calls += 1
-        key = ",".join(sorted(overs[0])) + f" x{len(overs)}"
-        st = self.call_stats.setdefault(key, [0, 0.0])
-        st[0] += 1
-        st[1] += dt
+        self._count_call(time.perf_counter() - t0, ",".join(sorted(overs[0])) + f" x{len(overs)}")
         return out
 
     def _unit_group(self, fam):
@@ -333,26 +392,24 @@ class HDDM:
         return self.group[fam][np.arange(self.n_units[fam]) % len(self.levels[fam])]
 
     def subj_prior(self, fam, x):
-        g = self._unit_group(fam)
-        if fam == "v":
-            return normal_logpdf(x, g, self.std["v"])
-        return gamma_logpdf_mean_sd(x, g, self.std[fam])
+        return LOGPDF[MODEL[fam].subject](x, self._unit_group(fam), self.std[fam])
 
     def logp(self):
         """Joint log density of the model at the current values."""
         lp = float(np.sum(self.node_logp()))
         for fam in self.FAMILIES:
             lp += float(np.sum(self.subj_prior(fam, self.subj[fam])))
-        lp += float(np.sum(self._group_prior("a", self.group["a"])))
-        lp += float(np.sum(self._group_prior("t", self.group["t"])))
-        lp += float(np.sum(normal_logpdf(self.group["v"], 2.0, 3.0)))
-        lp += float(np.sum([halfnormal_logpdf(self.std[f], s)
-                            for f, s in (("a", 2.0), ("v", 2.0), ("t", 1.0))]))
+        for fam in ("a", "t", "v"):  # the order these terms have always been summed in
+            lp += float(np.sum(self._group_prior(fam, self.group[fam])))
+        lp += float(np.sum([halfnormal_logpdf(self.std[f], MODEL[f].std_sd)
+                            for f in self.FAMILIES]))
+        for name in self.inter_names:
+            lp += float(logpdf(INTER[name].prior, self.inter[name]))
         return lp
 
     @staticmethod
     def _group_prior(fam, x):
-        return gamma_logpdf_mean_sd(x, 1.5, 0.75) if fam == "a" else gamma_logpdf_mean_sd(x, .4, .2)
+        return logpdf(MODEL[fam].group_prior, x)
 
     # -- updates ---------------------------------------------------------------
     def _update_subject(self, fam):
@@ -368,22 +425,23 @@ class HDDM:
             return (np.bincount(unit, weights=r[0], minlength=nu) + self.subj_prior(fam, xl),
                     np.bincount(unit, weights=r[1], minlength=nu) + self.subj_prior(fam, xr))
 
-        lower = 0.0 if fam in ("a", "t") else None
         self.subj[fam], _ = slice_step(self.subj[fam], logp, SLICE_WIDTHS[fam], self.rng,
-                                       lower=lower,
+                                       lower=MODEL[fam].lower,
                                        logp_pair=logp_pair if self.paired_probes else None)
 
     def _update_group(self, fam):
         nl = len(self.levels[fam])
         lv = np.arange(self.n_units[fam]) % nl
-        if fam == "v":  # kNormalNormal: conjugate Normal mean (hddm_info.py:167-168)
-            tau0, mu0 = 3.0 ** -2, 2.0
-            tau = self.std["v"] ** -2
+        spec = MODEL[fam]
+        if spec.subject == "normal":  # kNormalNormal: conjugate Normal mean (hddm_info.py:167-168)
+            _, mu0, sd0 = spec.group_prior
+            tau0 = sd0 ** -2
+            tau = self.std[fam] ** -2
             for k in range(nl):
-                xs = self.subj["v"][lv == k]
+                xs = self.subj[fam][lv == k]
                 prec = tau0 + tau * xs.size
                 mean = (tau0 * mu0 + tau * xs.sum()) / prec
-                self.group["v"][k] = self.rng.normal(mean, prec ** -0.5)
+                self.group[fam][k] = self.rng.normal(mean, prec ** -0.5)
         else:
             def logp(g):
                 out = self._group_prior(fam, g)
@@ -392,25 +450,26 @@ class HDDM:
                                                           self.std[fam]))
                 return out
             self.group[fam], _ = slice_step(self.group[fam], logp, SLICE_WIDTHS[fam], self.rng,
-                                            lower=0.0)
-        std_sd = {"a": 2.0, "v": 2.0, "t": 1.0}[fam]
+                                            lower=spec.lower)
+        subject = LOGPDF[spec.subject]
 
         def logp_std(s):
             s = float(s[0])
             if s <= 0:
                 return np.array([-np.inf])
-            g = self._unit_group(fam)
-            x = self.subj[fam]
-            ll = normal_logpdf(x, g, s) if fam == "v" else gamma_logpdf_mean_sd(x, g, s)
-            return np.array([float(halfnormal_logpdf(s, std_sd)) + float(np.sum(ll))])
+            ll = subject(self.subj[fam], self._unit_group(fam), s)
+            return np.array([float(halfnormal_logpdf(s, spec.std_sd)) + float(np.sum(ll))])
 
         new, _ = slice_step(np.array([self.std[fam]]), logp_std, SLICE_WIDTHS[fam + "_std"],
                             self.rng, lower=0.0)
         self.std[fam] = float(new[0])
 
     def _update_inter(self, name):
-        prior = {"sv": lambda x: halfnormal_logpdf(x, 2.0), "sz": lambda x: beta_logpdf(x, 1, 3),
-                 "st": lambda x: halfnormal_logpdf(x, 0.3)}[name]
+        kind, *args = INTER[name].prior
+        density = LOGPDF[kind]
+
+        def prior(x):
+            return density(x, *args)
 
         def logp(x):
             val = float(x[0])
@@ -438,44 +497,39 @@ class HDDM:
         for fam in self.FAMILIES:
             self._update_group(fam)
             self._update_subject(fam)
-        for name in ("sv", "sz", "st"):
-            if name in self.include:
-                self._update_inter(name)
+        for name in self.inter_names:
+            self._update_inter(name)
+
+    def _record(self, nodes):
+        """The current state as sample() keeps it: ({trace name: value} in
+        trace order -- the group nodes (nodes: group_nodes() as a list),
+        `{family}_std`, the included sv / sz / st --, {trace_subj name: a copy
+        of the subject array})."""
+        group = {name: self.group[fam][k] for name, fam, k in nodes}
+        group.update((f"{fam}_std", self.std[fam]) for fam in self.FAMILIES)
+        group.update((name, self.inter[name]) for name in self.inter_names)
+        return group, {fam: self.subj[fam].copy() for fam in self.FAMILIES}
 
     def sample(self, iter, burn=0, thin=1, progress=None):
         """Run `iter` sweeps; keep every `thin`-th after `burn`. Returns traces
         of the group-level nodes (dict name -> array)."""
-        trace = {}
-        names = []
-        for fam in self.FAMILIES:
-            for k, lv in enumerate(self.levels[fam]):
-                names.append((f"{fam}" + (f"({','.join(map(str, lv))})" if lv else ""), fam, k))
-        self.trace_subj = {f: [] for f in self.FAMILIES}
-        for name, _, _ in names:
-            trace[name] = []
-        for fam in self.FAMILIES:
-            trace[f"{fam}_std"] = []
-        for name in ("sv", "sz", "st"):
-            if name in self.include:
-                trace[name] = []
+        nodes = list(self.group_nodes())
+        names, subj_names = (list(d) for d in self._record(nodes))
+        kept, kept_subj = [], []
         t0 = time.perf_counter()
         for it in range(iter):
             self.sweep()
             if it >= burn and (it - burn) % thin == 0:
-                for name, fam, k in names:
-                    trace[name].append(self.group[fam][k])
-                for fam in self.FAMILIES:
-                    trace[f"{fam}_std"].append(self.std[fam])
-                    self.trace_subj[fam].append(self.subj[fam].copy())
-                for name in ("sv", "sz", "st"):
-                    if name in self.include:
-                        trace[name].append(self.inter[name])
+                group, subj = self._record(nodes)
+                kept.append(group)
+                kept_subj.append(subj)
             if progress and (it + 1) % progress == 0:
                 el = time.perf_counter() - t0
                 print(f"  [{it + 1}/{iter}] {el:.1f}s, {self.likelihood_calls} batched "
-                      f"likelihood calls", flush=True)
-        self.trace = {k: np.asarray(v) for k, v in trace.items()}
-        self.trace_subj = {k: np.asarray(v) for k, v in self.trace_subj.items()}
+                      f"likelihood calls{self._progress_note}", flush=True)
+        self.trace = {k: np.asarray([g[k] for g in kept]).reshape(self._trace_shape)
+                      for k in names}
+        self.trace_subj = {k: np.asarray([s[k] for s in kept_subj]) for k in subj_names}
         self.sample_seconds = time.perf_counter() - t0
         return self.trace
 
@@ -491,10 +545,7 @@ class HDDM:
         """Set group-level values by gen_stats()' node names ('a', 'v(c1)',
         'sv', ...). With one subject the subject-level value follows its group
         node, so the next sample() -- or optimize() -- starts there."""
-        slots = {}
-        for fam in self.FAMILIES:
-            for k, lv in enumerate(self.levels[fam]):
-                slots[fam + (f"({','.join(map(str, lv))})" if lv else "")] = (fam, k)
+        slots = {name: (fam, k) for name, fam, k in self.group_nodes()}
         for name, val in values.items():
             if name in slots:
                 fam, k = slots[name]
@@ -502,7 +553,7 @@ class HDDM:
                 if self.n_subj == 1:
                     self.subj[fam] = self.subj[fam].copy()
                     self.subj[fam][k] = float(val)
-            elif name in ("sv", "sz", "st") and name in self.include:
+            elif name in self.inter_names:
                 self.inter[name] = float(val)
             else:
                 raise KeyError(f"no group-level node named {name!r}")
@@ -557,16 +608,10 @@ class HDDM:
         if samples < 1:
             raise ValueError("samples must be >= 1")
         picked = np.unique(np.linspace(0, kept - 1, min(samples, kept)).round().astype(np.int64))
-        P = np.empty((picked.size, self.n_nodes, 8))
-        P[:, :, 0] = self.trace_subj["v"][picked][:, self.node_unit["v"]]
-        P[:, :, 2] = self.trace_subj["a"][picked][:, self.node_unit["a"]]
-        P[:, :, 3] = 0.5
-        P[:, :, 5] = self.trace_subj["t"][picked][:, self.node_unit["t"]]
-        for name in ("sv", "sz", "st"):
-            P[:, :, self._COL[name]] = (self.trace[name][picked][:, None] if name in self.include
-                                        else self.inter[name])
-        P[:, :, 7] = self.p_outlier
-        return picked, P
+        subj = {fam: self.trace_subj[fam][picked] for fam in self.FAMILIES}
+        inter = {name: self.trace[name][picked][:, None] if name in self.include
+                 else self.inter[name] for name in INTER}
+        return picked, self._table_of((picked.size,), subj, inter)
 
     def post_pred_gen(self, samples=500, seed=None, cdf_range=(-5, 5), dt=1e-4, method="cdf"):
         """Posterior predictive data (kabuki.analyze.post_pred_gen over the
@@ -625,6 +670,7 @@ class HDDMChains(HDDM):
         self.C = int(chains)
         if self.C < 1:
             raise ValueError("chains must be >= 1")
+        self._trace_shape, self._progress_note = (-1, self.C), f" ({self.C} chains)"
         super().__init__(data, **kw)
 
     def _init_values(self):
@@ -642,16 +688,8 @@ class HDDMChains(HDDM):
         key = tuple(self.subj[f].tobytes() for f in self.FAMILIES) + tuple(
             self.inter[k].tobytes() for k in ("sv", "sz", "st"))
         if getattr(self, "_tables_key", None) != key:
-            P = np.empty((self.C, self.n_nodes, 8))
-            P[:, :, 0] = self.subj["v"][:, self.node_unit["v"]]
-            P[:, :, 1] = self.inter["sv"][:, None]
-            P[:, :, 2] = self.subj["a"][:, self.node_unit["a"]]
-            P[:, :, 3] = 0.5
-            P[:, :, 4] = self.inter["sz"][:, None]
-            P[:, :, 5] = self.subj["t"][:, self.node_unit["t"]]
-            P[:, :, 6] = self.inter["st"][:, None]
-            P[:, :, 7] = self.p_outlier
-            self._tables, self._tables_key = P, key
+            inter = {name: val[:, None] for name, val in self.inter.items()}
+            self._tables, self._tables_key = self._table_of((self.C,), self.subj, inter), key
         if idx is None and not over:
             return self._tables
         P = self._tables.copy() if idx is None else self._tables[idx]
@@ -693,31 +731,20 @@ class HDDMChains(HDDM):
             out = r.reshape(len(overs), C, m)
         else:
             out[:, idx] = r.reshape(len(overs), idx.size, m)
-        dt = time.perf_counter() - t0
-        self.likelihood_seconds += dt
-        self.device_call_seconds = getattr(self, "device_call_seconds", 0.0) + (t2 - t1)
-        self.likelihood_calls += 1
-        self.tables_evaluated = getattr(self, "tables_evaluated", 0) + tabs.shape[0]
-        key = ",".join(sorted(overs[0])) + f" x{len(overs)}"
-        st = self.call_stats.setdefault(key, [0, 0.0])
-        st[0] += 1
-        st[1] += dt
+        self._count_call(time.perf_counter() - t0, ",".join(sorted(overs[0])) + f" x{len(overs)}")
+        self.device_call_seconds += t2 - t1
+        self.tables_evaluated += tabs.shape[0]
         return out
 
     def node_logp(self, over=None):
         return self.node_logp_chains([over or {}])[0]
 
-    def node_table(self, over=None):
-        raise NotImplementedError("HDDMChains: node_tables() holds one table per chain")
-
-    def optimize(self, *args, **kw):
-        raise NotImplementedError("HDDMChains: point fits take one chain (HDDM)")
-
-    def post_pred_rows(self, samples=500):
-        raise NotImplementedError("HDDMChains: posterior predictive draws take one chain (HDDM)")
-
-    def post_pred_gen(self, samples=500, seed=None, cdf_range=(-5, 5), dt=1e-4):
-        raise NotImplementedError("HDDMChains: posterior predictive draws take one chain (HDDM)")
+    node_table = _refuses("HDDMChains: node_tables() holds one table per chain")
+    node_logp_multi = _refuses("HDDMChains: node_logp_chains() scores every chain's tables")
+    set_values = _refuses("HDDMChains: group[f][chain, level] holds one value per chain")
+    optimize = quantile_objective = _refuses("HDDMChains: point fits take one chain (HDDM)")
+    post_pred_rows = post_pred_gen = _refuses(
+        "HDDMChains: posterior predictive draws take one chain (HDDM)")
 
     def _unit_group_c(self, fam):
         """(C, units) group mean of each unit's level, per chain."""
@@ -725,22 +752,19 @@ class HDDMChains(HDDM):
         return self.group[fam][:, np.arange(self.n_units[fam]) % nl]
 
     def subj_prior_c(self, fam, x):
-        g = self._unit_group_c(fam)
-        sd = self.std[fam][:, None]
-        if fam == "v":
-            return normal_logpdf(x, g, sd)
-        return gamma_logpdf_mean_sd(x, g, sd)
+        return LOGPDF[MODEL[fam].subject](x, self._unit_group_c(fam), self.std[fam][:, None])
 
     def logp(self):
         """Joint log density of the model at each chain's values: (C,)."""
         lp = np.sum(self.node_logp(), axis=1)
         for fam in self.FAMILIES:
             lp = lp + np.sum(self.subj_prior_c(fam, self.subj[fam]), axis=1)
-        lp = lp + np.sum(self._group_prior("a", self.group["a"]), axis=1)
-        lp = lp + np.sum(self._group_prior("t", self.group["t"]), axis=1)
-        lp = lp + np.sum(normal_logpdf(self.group["v"], 2.0, 3.0), axis=1)
-        for f, s in (("a", 2.0), ("v", 2.0), ("t", 1.0)):
-            lp = lp + halfnormal_logpdf(self.std[f], s)
+        for fam in ("a", "t", "v"):  # HDDM.logp's order
+            lp = lp + np.sum(self._group_prior(fam, self.group[fam]), axis=1)
+        for fam in self.FAMILIES:
+            lp = lp + halfnormal_logpdf(self.std[fam], MODEL[fam].std_sd)
+        for name in self.inter_names:
+            lp = lp + logpdf(INTER[name].prior, self.inter[name])
         return lp
 
     def _update_subject(self, fam):
@@ -767,23 +791,24 @@ class HDDMChains(HDDM):
             r = self.node_logp_chains([{fam: xl.reshape(C, nu)}, {fam: xr.reshape(C, nu)}], ch)
             return ll(r[0]) + prior(xl), ll(r[1]) + prior(xr)
 
-        lower = 0.0 if fam in ("a", "t") else None
         new, _ = slice_step(self.subj[fam].ravel(), logp, SLICE_WIDTHS[fam], self.rng,
-                            lower=lower, logp_pair=logp_pair if self.paired_probes else None,
-                            masked=True)
+                            lower=MODEL[fam].lower,
+                            logp_pair=logp_pair if self.paired_probes else None, masked=True)
         self.subj[fam] = new.reshape(C, nu)
 
     def _update_group(self, fam):
         C, nl = self.C, len(self.levels[fam])
         lv = np.arange(self.n_units[fam]) % nl
-        if fam == "v":  # kNormalNormal per chain and level (hddm_info.py:167-168)
-            tau0, mu0 = 3.0 ** -2, 2.0
-            tau = self.std["v"] ** -2
+        spec = MODEL[fam]
+        if spec.subject == "normal":  # kNormalNormal per chain and level (hddm_info.py:167-168)
+            _, mu0, sd0 = spec.group_prior
+            tau0 = sd0 ** -2
+            tau = self.std[fam] ** -2
             for k in range(nl):
-                xs = self.subj["v"][:, lv == k]
+                xs = self.subj[fam][:, lv == k]
                 prec = tau0 + tau * xs.shape[1]
                 mean = (tau0 * mu0 + tau * xs.sum(axis=1)) / prec
-                self.group["v"][:, k] = self.rng.normal(mean, prec ** -0.5)
+                self.group[fam][:, k] = self.rng.normal(mean, prec ** -0.5)
         else:
             def logp(g):
                 g = g.reshape(C, nl)
@@ -794,29 +819,27 @@ class HDDMChains(HDDM):
                         gamma_logpdf_mean_sd(xs, g[:, k:k + 1], self.std[fam][:, None]), axis=1)
                 return out.ravel()
             new, _ = slice_step(self.group[fam].ravel(), logp, SLICE_WIDTHS[fam], self.rng,
-                                lower=0.0)
+                                lower=spec.lower)
             self.group[fam] = new.reshape(C, nl)
-        std_sd = {"a": 2.0, "v": 2.0, "t": 1.0}[fam]
+        subject = LOGPDF[spec.subject]
 
         def logp_std(s):
             ok = s > 0
             ss = np.where(ok, s, 1.0)[:, None]
-            g = self._unit_group_c(fam)
-            x = self.subj[fam]
-            ll = normal_logpdf(x, g, ss) if fam == "v" else gamma_logpdf_mean_sd(x, g, ss)
-            val = halfnormal_logpdf(np.where(ok, s, 1.0), std_sd) + np.sum(ll, axis=1)
+            ll = subject(self.subj[fam], self._unit_group_c(fam), ss)
+            val = halfnormal_logpdf(np.where(ok, s, 1.0), spec.std_sd) + np.sum(ll, axis=1)
             return np.where(ok, val, -np.inf)
 
         self.std[fam], _ = slice_step(self.std[fam].copy(), logp_std, SLICE_WIDTHS[fam + "_std"],
                                       self.rng, lower=0.0)
 
     def _update_inter(self, name):
-        prior = {"sv": lambda x: halfnormal_logpdf(x, 2.0), "sz": lambda x: beta_logpdf(x, 1, 3),
-                 "st": lambda x: halfnormal_logpdf(x, 0.3)}[name]
         cur = self.inter[name]
+        kind, *args = INTER[name].prior
+        density = LOGPDF[kind]
 
         def masked(x):
-            pr = prior(x)
+            pr = density(x, *args)
             ok = np.isfinite(pr)
             # a probe outside the prior's support is not evaluated: the table
             # keeps the chain's current value there and the result is -inf
@@ -840,39 +863,14 @@ class HDDMChains(HDDM):
                                          logp_pair=logp_pair if self.paired_probes else None,
                                          masked=True)
 
-    def sample(self, iter, burn=0, thin=1, progress=None):
-        """Run `iter` lockstep sweeps of every chain; keep every `thin`-th
-        after `burn`. Returns traces (dict name -> (kept, C))."""
-        names = []
-        for fam in self.FAMILIES:
-            for k, lv in enumerate(self.levels[fam]):
-                names.append((f"{fam}" + (f"({','.join(map(str, lv))})" if lv else ""), fam, k))
-        trace = {nm: [] for nm, _, _ in names}
-        for fam in self.FAMILIES:
-            trace[f"{fam}_std"] = []
-        inter = [nm for nm in ("sv", "sz", "st") if nm in self.include]
-        for nm in inter:
-            trace[nm] = []
-        self.trace_subj = {f: [] for f in self.FAMILIES}
-        t0 = time.perf_counter()
-        for it in range(iter):
-            self.sweep()
-            if it >= burn and (it - burn) % thin == 0:
-                for nm, fam, k in names:
-                    trace[nm].append(self.group[fam][:, k].copy())
-                for fam in self.FAMILIES:
-                    trace[f"{fam}_std"].append(self.std[fam].copy())
-                    self.trace_subj[fam].append(self.subj[fam].copy())
-                for nm in inter:
-                    trace[nm].append(self.inter[nm].copy())
-            if progress and (it + 1) % progress == 0:
-                el = time.perf_counter() - t0
-                print(f"  [{it + 1}/{iter}] {el:.1f}s, {self.likelihood_calls} batched "
-                      f"likelihood calls ({self.C} chains)", flush=True)
-        self.trace = {k: np.asarray(v).reshape(-1, self.C) for k, v in trace.items()}
-        self.trace_subj = {k: np.asarray(v) for k, v in self.trace_subj.items()}
-        self.sample_seconds = time.perf_counter() - t0
-        return self.trace
+    def _record(self, nodes):
+        """HDDM._record with a (C,) value per trace name: sample() runs `iter`
+        lockstep sweeps of every chain, keeps every `thin`-th after `burn` and
+        returns traces (dict name -> (kept, C))."""
+        group = {name: self.group[fam][:, k].copy() for name, fam, k in nodes}
+        group.update((f"{fam}_std", self.std[fam].copy()) for fam in self.FAMILIES)
+        group.update((name, self.inter[name].copy()) for name in self.inter_names)
+        return group, {fam: self.subj[fam].copy() for fam in self.FAMILIES}
 
     def gen_stats(self):
         """Posterior summaries pooled over the chains, with the Gelman-Rubin

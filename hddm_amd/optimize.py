@@ -16,6 +16,7 @@ of all replicates that need it.
 import numpy as np
 
 from . import cdfdif_wrapper
+from .hierarchical import INTER, param_table
 from .quantiles import DEFAULT_QUANTILES, pool_stats, quantile_stats
 
 METHODS = ("ML", "chisquare", "gsquare")
@@ -129,15 +130,9 @@ class _FlatModel:
 
     def __init__(self, m):
         self.m = m
-        self.names, self.slots = [], []
-        for fam in m.FAMILIES:
-            for k, lv in enumerate(m.levels[fam]):
-                self.names.append(fam + (f"({','.join(map(str, lv))})" if lv else ""))
-                self.slots.append((fam, k))
-        for name in ("sv", "sz", "st"):
-            if name in m.include:
-                self.names.append(name)
-                self.slots.append((name, None))
+        nodes = list(m.group_nodes()) + [(name, name, None) for name in m.inter_names]
+        self.names = [name for name, _, _ in nodes]
+        self.slots = [(s, k) for _, s, k in nodes]
         self.d = len(self.names)
         # rows: the nodes, or one per condition tag (its first node gives the levels)
         tags = [key[1:] for key in m.node_keys]
@@ -154,7 +149,7 @@ class _FlatModel:
                         for fam in m.FAMILIES}
         self.node_col = {fam: np.array([col[(fam, int(k))] for k in m.node_level[fam]])
                          for fam in m.FAMILIES}
-        self.inter_col = {n: col.get((n, None)) for n in ("sv", "sz", "st")}
+        self.inter_col = {n: col.get((n, None)) for n in INTER}
 
     def current(self):
         m = self.m
@@ -165,16 +160,10 @@ class _FlatModel:
         """(n, rows, 8) parameter rows of the value vectors X (n, d); cols:
         row_col (quantile rows) or node_col (the observed nodes)."""
         X = np.asarray(X, dtype=np.float64)
-        P = np.empty((X.shape[0], cols["a"].size, 8))
-        P[:, :, 0] = X[:, cols["v"]]
-        P[:, :, 2] = X[:, cols["a"]]
-        P[:, :, 3] = 0.5
-        P[:, :, 5] = X[:, cols["t"]]
-        for name, c in ((("sv", 1), ("sz", 4), ("st", 6))):
-            i = self.inter_col[name]
-            P[:, :, c] = self.m.inter[name] if i is None else X[:, i:i + 1]
-        P[:, :, 7] = self.m.p_outlier
-        return P
+        vals = {fam: X[:, c] for fam, c in cols.items()}
+        for name, i in self.inter_col.items():
+            vals[name] = self.m.inter[name] if i is None else X[:, i:i + 1]
+        return param_table((X.shape[0], cols["a"].size), vals, self.m.p_outlier)
 
     def row_stats(self, rt, node, quantiles):
         """(emp_rt, freq_obs, n_samples) arrays over the rows for signed RTs

@@ -27,8 +27,8 @@ import time
 import numpy as np
 
 from . import wfpt as _wfpt
-from .hierarchical import (HDDM, SLICE_WIDTHS, beta_logpdf, gamma_logpdf_mean_sd,
-                           halfnormal_logpdf, normal_logpdf, slice_step)
+from .hierarchical import (HDDM, INTER, LOGPDF, MODEL, SLICE_WIDTHS, _refuses, halfnormal_logpdf,
+                           logpdf, normal_logpdf, slice_step)
 
 LINKS = ("identity", "exp", "invlogit")
 COEF_SLICE_WIDTH = 0.05  # hddm_regression.py:284
@@ -126,12 +126,6 @@ class HDDMRegressor(HDDM):
     `{outcome}_{design column}`. The non-regressed families stay as in HDDM.
     """
 
-    _GROUP_PRIOR = {"a": lambda x: gamma_logpdf_mean_sd(x, 1.5, 0.75),
-                    "v": lambda x: normal_logpdf(x, 2.0, 3.0),
-                    "t": lambda x: gamma_logpdf_mean_sd(x, 0.4, 0.2)}
-    _STD_SD = {"a": 2.0, "v": 2.0, "t": 1.0}
-    _START = {"a": (1.5, 1.0), "v": (2.0, 2.0), "t": (0.4, 0.001)}  # group, subject
-
     def __init__(self, data, models, group_only_regressors=True, include=(), p_outlier=0.05,
                  wiener_params=None, seed=None, device=None, depends_on=None):
         import pandas as pd
@@ -175,16 +169,10 @@ class HDDMRegressor(HDDM):
         """HDDM's starting values (hddm_info.py:121-140) for the non-regressed
         families; an intercept starts where its outcome would, every other
         coefficient at 0."""
-        fams = self.FAMILIES
-        self.group = {f: np.full(len(self.levels[f]), self._START[f][0]) for f in fams}
-        self.std = {f: {"a": 0.1, "v": 0.1, "t": 0.2}[f] for f in fams}
-        self.subj = {f: np.full(self.n_units[f], self._START[f][1]) for f in fams}
-        self.inter = {"sv": 1.0 if "sv" in self.include else 0.0,
-                      "sz": 0.01 if "sz" in self.include else 0.0,
-                      "st": 0.001 if "st" in self.include else 0.0}
+        super()._init_values()
         self.coef, self.coef_std, self.coef_subj = {}, {}, {}
         for nm, out, inter in zip(self.coef_names, self.coef_outcome, self.coef_intercept):
-            g0, s0 = self._START[out] if inter else (0.0, 0.0)
+            g0, s0 = MODEL[out].start[:2] if inter else (0.0, 0.0)
             if self.group_only_regressors:
                 # the group node feeds the likelihood directly: start where a
                 # subject node would (t below every RT)
@@ -208,16 +196,9 @@ class HDDMRegressor(HDDM):
     def node_table(self, over=None):
         """(n_nodes, 8) parameter table as HDDM.node_table; a regressed
         outcome's column is unused by the likelihood (0)."""
-        P = np.zeros((self.n_nodes, 8))
         over = over or {}
-        for fam in self.FAMILIES:
-            x = over.get(fam, self.subj[fam])
-            P[:, self._COL[fam]] = x[self.node_unit[fam]]
-        P[:, 3] = 0.5
-        for name in ("sv", "sz", "st"):
-            P[:, self._COL[name]] = over.get(name, self.inter[name])
-        P[:, 7] = self.p_outlier
-        return P
+        return self._table_of((), {fam: over.get(fam, self.subj[fam]) for fam in self.FAMILIES},
+                              {name: over.get(name, self.inter[name]) for name in INTER})
 
     def node_logp(self, over=None):
         """One wiener_like_reg_groups call: the (n_nodes,) sums. Keys of `over`
@@ -227,60 +208,47 @@ class HDDMRegressor(HDDM):
         t0 = time.perf_counter()
         out = self.dataset.wiener_like_reg_groups(self.reg_model, self.coef_table(over),
                                                   self.node_table(over), **self.wp)
-        dt = time.perf_counter() - t0
-        self.likelihood_seconds += dt
-        self.likelihood_calls += 1
-        st = self.call_stats.setdefault(",".join(sorted(over)) if over else "-", [0, 0.0])
-        st[0] += 1
-        st[1] += dt
+        self._count_call(time.perf_counter() - t0, ",".join(sorted(over)) if over else "-")
         return out
-
-    def node_logp_multi(self, overs):
-        raise NotImplementedError("HDDMRegressor scores one table per call")
 
     # -- priors --------------------------------------------------------------
     def _coef_group_prior(self, nm, x):
         j = self.coef_names.index(nm)
         if self.coef_intercept[j]:
-            return self._GROUP_PRIOR[self.coef_outcome[j]](x)
+            return self._group_prior(self.coef_outcome[j], x)
         return normal_logpdf(x, 0.0, 15.0)
 
     def _coef_subj_prior(self, nm, x, g=None, std=None):
         j = self.coef_names.index(nm)
         g = float(self.coef[nm] if g is None else g)
         std = float(self.coef_std[nm] if std is None else std)
-        if self.coef_intercept[j] and self.coef_outcome[j] != "v":
-            return gamma_logpdf_mean_sd(x, g, std)
-        return normal_logpdf(x, g, std)
+        kind = MODEL[self.coef_outcome[j]].subject if self.coef_intercept[j] else "normal"
+        return LOGPDF[kind](x, g, std)
 
     def _coef_std_prior(self, nm, s):
         j = self.coef_names.index(nm)
         if self.coef_intercept[j]:
-            return float(halfnormal_logpdf(s, self._STD_SD[self.coef_outcome[j]]))
+            return float(halfnormal_logpdf(s, MODEL[self.coef_outcome[j]].std_sd))
         return -np.log(100.0 - 1e-10) if 1e-10 <= s <= 100.0 else -np.inf
 
     def _coef_lower(self, nm):
         j = self.coef_names.index(nm)
-        return 0.0 if self.coef_intercept[j] and self.coef_outcome[j] in ("a", "t") else None
+        return MODEL[self.coef_outcome[j]].lower if self.coef_intercept[j] else None
 
     def logp(self):
         """Joint log density of the model at the current values."""
         lp = float(np.sum(self.node_logp()))
         for fam in self.FAMILIES:
             lp += float(np.sum(self.subj_prior(fam, self.subj[fam])))
-            lp += float(np.sum(self._GROUP_PRIOR[fam](self.group[fam])))
-            lp += float(halfnormal_logpdf(self.std[fam], self._STD_SD[fam]))
+            lp += float(np.sum(self._group_prior(fam, self.group[fam])))
+            lp += float(halfnormal_logpdf(self.std[fam], MODEL[fam].std_sd))
         for nm in self.coef_names:
             lp += float(self._coef_group_prior(nm, self.coef[nm]))
             if not self.group_only_regressors:
                 lp += float(np.sum(self._coef_subj_prior(nm, self.coef_subj[nm])))
                 lp += self._coef_std_prior(nm, self.coef_std[nm])
-        inter_prior = {"sv": lambda x: halfnormal_logpdf(x, 2.0),
-                       "sz": lambda x: beta_logpdf(x, 1, 3),
-                       "st": lambda x: halfnormal_logpdf(x, 0.3)}
-        for name in ("sv", "sz", "st"):
-            if name in self.include:
-                lp += float(inter_prior[name](self.inter[name]))
+        for name in self.inter_names:
+            lp += float(logpdf(INTER[name].prior, self.inter[name]))
         return lp
 
     # -- updates -------------------------------------------------------------
@@ -343,61 +311,25 @@ class HDDMRegressor(HDDM):
             else:
                 self._update_coef_group(nm)
                 self._update_coef_subject(nm)
-        for name in ("sv", "sz", "st"):
-            if name in self.include:
-                self._update_inter(name)
+        for name in self.inter_names:
+            self._update_inter(name)
 
-    def sample(self, iter, burn=0, thin=1, progress=None):
-        """Run `iter` sweeps; keep every `thin`-th after `burn`. Returns traces
-        of the group-level nodes (dict name -> array): HDDM's names for the
-        non-regressed families, the coefficient names, `{coefficient}_std`
-        with subject-level coefficients."""
-        names = []
-        for fam in self.FAMILIES:
-            for k, lv in enumerate(self.levels[fam]):
-                names.append((f"{fam}" + (f"({','.join(map(str, lv))})" if lv else ""), fam, k))
-        trace = {name: [] for name, _, _ in names}
-        for fam in self.FAMILIES:
-            trace[f"{fam}_std"] = []
+    def _record(self, nodes):
+        """HDDM._record, so that sample() returns traces of the group-level
+        nodes (dict name -> array): HDDM's names for the non-regressed
+        families, then the coefficient names, each followed by its
+        `{coefficient}_std` with subject-level coefficients, then sv / sz / st."""
+        group, subj = super()._record(nodes)
+        inter = {name: group.pop(name) for name in self.inter_names}
         for nm in self.coef_names:
-            trace[nm] = []
+            group[nm] = self.coef[nm]
             if not self.group_only_regressors:
-                trace[f"{nm}_std"] = []
-        inter = [name for name in ("sv", "sz", "st") if name in self.include]
-        for name in inter:
-            trace[name] = []
-        subj_keys = list(self.FAMILIES) + ([] if self.group_only_regressors else self.coef_names)
-        trace_subj = {k: [] for k in subj_keys}
-        t0 = time.perf_counter()
-        for it in range(iter):
-            self.sweep()
-            if it >= burn and (it - burn) % thin == 0:
-                for name, fam, k in names:
-                    trace[name].append(self.group[fam][k])
-                for fam in self.FAMILIES:
-                    trace[f"{fam}_std"].append(self.std[fam])
-                    trace_subj[fam].append(self.subj[fam].copy())
-                for nm in self.coef_names:
-                    trace[nm].append(self.coef[nm])
-                    if not self.group_only_regressors:
-                        trace[f"{nm}_std"].append(self.coef_std[nm])
-                        trace_subj[nm].append(self.coef_subj[nm].copy())
-                for name in inter:
-                    trace[name].append(self.inter[name])
-            if progress and (it + 1) % progress == 0:
-                el = time.perf_counter() - t0
-                print(f"  [{it + 1}/{iter}] {el:.1f}s, {self.likelihood_calls} batched "
-                      f"likelihood calls", flush=True)
-        self.trace = {k: np.asarray(v) for k, v in trace.items()}
-        self.trace_subj = {k: np.asarray(v) for k, v in trace_subj.items()}
-        self.sample_seconds = time.perf_counter() - t0
-        return self.trace
+                group[f"{nm}_std"] = self.coef_std[nm]
+                subj[nm] = self.coef_subj[nm].copy()
+        group.update(inter)
+        return group, subj
 
-    def optimize(self, *args, **kw):
-        raise NotImplementedError("the regressor's point fits are not implemented")
-
-    def post_pred_rows(self, samples=500):
-        raise NotImplementedError("the regressor's posterior predictive is not implemented")
-
-    def post_pred_gen(self, samples=500, seed=None, cdf_range=(-5, 5), dt=1e-4):
-        raise NotImplementedError("the regressor's posterior predictive is not implemented")
+    node_logp_multi = _refuses("HDDMRegressor scores one table per call")
+    optimize = quantile_objective = _refuses("the regressor's point fits are not implemented")
+    post_pred_rows = post_pred_gen = _refuses(
+        "the regressor's posterior predictive is not implemented")
