@@ -198,6 +198,16 @@ wfpt_gen_rts_drift_nodes_ex = _sig("wfpt_gen_rts_drift_nodes_ex", _I,
                                    [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64, _I64, _I32,
                                     _PD, _PI64, _PD, _PD, _PD, _PD, _PI64, _PI64])
 wfpt_profile_stages = _sig("wfpt_profile_stages", _I, [_VP, _PD, _I])
+# per-row RT statistics (include/wfpt_amd.h)
+wfpt_rt_stats_rows = _sig("wfpt_rt_stats_rows", _I, [_VP, _PD, _PI64, _I64, _PD, _I32, _PD])
+wfpt_rt_stats_rows_ex = _sig("wfpt_rt_stats_rows_ex", _I,
+                             [_VP, _PD, _PI64, _I64, _PD, _I32, _I32, _PD])
+wfpt_gen_rts_nodes_stats = _sig("wfpt_gen_rts_nodes_stats", _I,
+                                [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD,
+                                 _PD, _I32, _PD])
+wfpt_gen_rts_drift_nodes_stats = _sig("wfpt_gen_rts_drift_nodes_stats", _I,
+                                      [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64, _PD, _PI64,
+                                       _PD, _I32, _PD])
 
 EXPORTED = [
     "wfpt_device_count", "wfpt_open", "wfpt_close", "wfpt_last_error", "wfpt_dataset_create",
@@ -221,6 +231,8 @@ EXPORTED = [
     "wfpt_reg_dataset_create", "wfpt_reg_dataset_destroy", "wfpt_wiener_like_reg",
     "wfpt_wiener_like_reg_ex", "wfpt_wiener_like_reg_groups", "wfpt_wiener_like_reg_groups_ex",
     "wfpt_dmat_cdf_rows",
+    "wfpt_rt_stats_rows", "wfpt_rt_stats_rows_ex", "wfpt_gen_rts_nodes_stats",
+    "wfpt_gen_rts_drift_nodes_stats",
 ]
 
 # error encoding of a result triple (include/wfpt_amd.h: wfpt_decode_result)

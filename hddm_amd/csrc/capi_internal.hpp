@@ -190,6 +190,14 @@ struct SimWork {
   }
 };
 
+// ... of the per-row RT statistics (stats_kernels.hip)
+struct StatsWork {
+  DevBuf<double> out;    // [R x K] the rows' statistics
+  DevBuf<int32_t> list;  // the rows of each tier and block-tier LDS size, one group after the other
+  DevBuf<double> ws;     // global tier: the padded row being sorted
+  DevBuf<unsigned long long> count;  // NaN draws of a drift call whose draws stay on the device
+};
+
 }  // namespace capi
 }  // namespace wfpt
 
@@ -285,6 +293,7 @@ struct wfpt_ctx {
   wfpt::capi::RlWork rl;
   wfpt::capi::RegWork reg;
   wfpt::capi::SimWork sim;
+  wfpt::capi::StatsWork stats;
 };
 
 struct wfpt_ds : wfpt::capi::DsBase {

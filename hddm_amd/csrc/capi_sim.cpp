@@ -1,20 +1,147 @@
 // capi_sim.cpp — the samplers of the C ABI (include/wfpt_amd.h): the batched
-// inverse-CDF RT sampler and the diffusion-path simulator (sim_kernels.hip).
+// inverse-CDF RT sampler and the diffusion-path simulator (sim_kernels.hip),
+// and the per-row RT statistics (stats_kernels.hip) alone or fused onto either.
 #include "capi_internal.hpp"
 #include "sim_internal.h"
+#include "stats_internal.h"
 
 using namespace wfpt::capi;
 
-extern "C" {
+namespace {
+
+// The statistics a sampler call is asked for on top of its draws.
+struct StatsReq {
+  const double* q;
+  int32_t nq;
+  double* out;  // [R x (8 + 2 nq)]
+};
+
+// Which kernel scores which row, decided on the host before any device work:
+// `list` holds the wave tier's rows, then the block tier's by LDS size, then
+// the global tier's. A call whose rows all take the wave tier uploads no list.
+struct StatsPlan {
+  wfpt::StatsQ Q;
+  std::vector<int32_t> list;
+  int64_t n_wave = 0, n_global = 0;
+  struct Group {
+    int64_t P, first, count;
+  };
+  std::vector<Group> block;
+  int64_t global_first = 0, global_P = 0;
+  bool identity = false;
+};
+
+int stats_check_q(const char* name, const double* q, int32_t nq, const double* out) {
+  if (nq < 0 || nq > wfpt::kStatsMaxQ)
+    return fail(WFPT_ERR_ARG, std::string(name) + ": nq outside 0..16");
+  if ((nq > 0 && !q) || !out)
+    return fail(WFPT_ERR_ARG, std::string(name) + ": null pointer (q / stats_out)");
+  for (int32_t k = 0; k < nq; ++k)
+    if (!(q[k] >= 0 && q[k] <= 100))
+      return fail(WFPT_ERR_ARG, std::string(name) + ": percentile " + std::to_string(k) +
+                                    " outside [0, 100]");
+  return WFPT_OK;
+}
+
+// off: R + 1 rising offsets. tier 0: by row length; 1 / 2 / 3 force the wave /
+// block / global tier, and a row the forced tier cannot hold is WFPT_ERR_ARG.
+int stats_plan(const char* name, const int64_t* off, int64_t R, const double* q, int32_t nq,
+               int32_t tier, StatsPlan* S) {
+  if (tier < 0 || tier > 3) return fail(WFPT_ERR_ARG, std::string(name) + ": tier outside 0..3");
+  S->Q.nq = nq;
+  for (int k = 0; k < wfpt::kStatsMaxQ; ++k) S->Q.q[k] = k < nq ? q[k] : 0.0;
+  std::vector<int32_t> wave, global;
+  std::vector<std::vector<int32_t>> block(16);  // by log2 of the padded length
+  for (int64_t r = 0; r < R; ++r) {
+    const int64_t n = off[r + 1] - off[r];
+    const int t = tier ? tier : (n <= wfpt::kStatsWaveMax ? 1 : n <= wfpt::kStatsBlockMax ? 2 : 3);
+    if ((t == 1 && n > wfpt::kStatsWaveMax) || (t == 2 && n > wfpt::kStatsBlockMax))
+      return fail(WFPT_ERR_ARG, std::string(name) + ": row " + std::to_string(r) + " has " +
+                                    std::to_string(n) + " draws, more than the forced tier " +
+                                    std::to_string(t) + " holds");
+    if (n >= (int64_t)1 << 36)
+      return fail(WFPT_ERR_ARG, std::string(name) + ": a row of 2^36 draws or more");
+    if (t == 1) wave.push_back((int32_t)r);
+    else if (t == 3) global.push_back((int32_t)r);
+    else {
+      int lg = 1;
+      while (((int64_t)1 << lg) < n) ++lg;
+      block[lg].push_back((int32_t)r);
+    }
+    if (t == 3) S->global_P = std::max(S->global_P, wfpt::stats_pow2(n));
+  }
+  S->identity = (int64_t)wave.size() == R;
+  S->n_wave = (int64_t)wave.size();
+  S->list = std::move(wave);
+  for (int lg = 1; lg < 16; ++lg) {
+    if (block[lg].empty()) continue;
+    S->block.push_back({(int64_t)1 << lg, (int64_t)S->list.size(), (int64_t)block[lg].size()});
+    S->list.insert(S->list.end(), block[lg].begin(), block[lg].end());
+  }
+  S->global_first = (int64_t)S->list.size();
+  S->n_global = (int64_t)global.size();
+  S->list.insert(S->list.end(), global.begin(), global.end());
+  return WFPT_OK;
+}
+
+// The statistics of rows [0, R) of the device draws d_rts (offsets on the
+// device and on the host) into c->stats.out, then host_out, on the context's
+// stream; returns after the stream has drained. The context is locked.
+int stats_run(wfpt_ctx* c, const StatsPlan& S, const double* d_rts, const int64_t* d_off,
+              const int64_t* off, int64_t R, double* host_out) {
+  const int K = wfpt::stats_cols(S.Q.nq);
+  HIP_TRY(c->stats.out.reserve((size_t)R * K));
+  if (!S.identity) {
+    HIP_TRY(c->stats.list.reserve(S.list.size()));
+    HIP_TRY(hipMemcpyAsync(c->stats.list.p, S.list.data(), S.list.size() * sizeof(int32_t),
+                           hipMemcpyHostToDevice, c->stream));
+  }
+  if (S.n_global > 0) HIP_TRY(c->stats.ws.reserve((size_t)S.global_P));
+  if (c->profile)
+    for (int k = 0; k < 2; ++k)
+      if (!c->sim.ev[k]) HIP_TRY(hipEventCreate(&c->sim.ev[k]));
+  wfpt::StatsCall C;
+  C.rts = d_rts;
+  C.off = d_off;
+  C.out = c->stats.out.p;
+  C.Q = S.Q;
+  if (c->profile) HIP_TRY(hipEventRecord(c->sim.ev[0], c->stream));
+  wfpt::launch_stats_wave(C, S.identity ? nullptr : c->stats.list.p, S.n_wave, c->stream);
+  HIP_TRY(hipGetLastError());
+  for (const StatsPlan::Group& g : S.block) {
+    wfpt::launch_stats_block(C, c->stats.list.p + g.first, g.count, g.P, c->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  for (int64_t k = 0; k < S.n_global; ++k) {
+    const int64_t r = S.list[S.global_first + k];
+    wfpt::launch_stats_global(C, r, off[r], off[r + 1] - off[r], c->stats.ws.p, c->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  if (c->profile) {
+    HIP_TRY(hipEventRecord(c->sim.ev[1], c->stream));
+    HIP_TRY(hipEventSynchronize(c->sim.ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->sim.ev[0], c->sim.ev[1]));
+    c->k_ms += ms;
+    c->launches += 1;
+  }
+  HIP_TRY(hipMemcpyAsync(host_out, c->stats.out.p, (size_t)R * K * sizeof(double),
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // a global-tier workspace grown past 256 MiB is not kept between calls
+  if (c->stats.ws.cap * sizeof(double) > ((size_t)256 << 20)) c->stats.ws.release();
+  return WFPT_OK;
+}
 
 // ---------------------------------------------------------------------------
 // RT sampler (sim_kernels.hip; wfpt.pyx:323-354 for R parameter rows)
 
-int wfpt_gen_rts_nodes_ex(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_params* rows,
-                          int64_t R, const int64_t* counts, const double* u_choice,
-                          const double* u_delay, uint64_t seed, int64_t workspace_bytes,
-                          double* out, double* out_pdf, double* out_cdf, int64_t* out_idx,
-                          double* out_u_choice, double* out_u_delay) {
+int gen_rts_nodes_impl(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_params* rows,
+                       int64_t R, const int64_t* counts, const double* u_choice,
+                       const double* u_delay, uint64_t seed, int64_t workspace_bytes, double* out,
+                       double* out_pdf, double* out_cdf, int64_t* out_idx, double* out_u_choice,
+                       double* out_u_delay, const StatsReq* sr) {
+
   if (!grid || !rows || !counts) return fail(WFPT_ERR_ARG, "null pointer (grid / rows / counts)");
   if (G < 2) return fail(WFPT_ERR_ARG, "gen_rts_nodes: G < 2 (the grid needs two points)");
   if (R < 1) return fail(WFPT_ERR_ARG, "gen_rts_nodes: R < 1");
@@ -28,7 +155,13 @@ int wfpt_gen_rts_nodes_ex(wfpt_ctx* c, const double* grid, int64_t G, const wfpt
   if ((u_delay && !u_choice) || (u_choice && !u_delay && any_st))
     return fail(WFPT_ERR_ARG,
                 "gen_rts_nodes: u_choice and u_delay go together when a row has st != 0");
-  if (!out && total > 0) return fail(WFPT_ERR_ARG, "null pointer (out)");
+  if (!out && total > 0 && !sr) return fail(WFPT_ERR_ARG, "null pointer (out)");
+  StatsPlan plan;
+  if (sr) {
+    if (int rc = stats_check_q("gen_rts_nodes_stats", sr->q, sr->nq, sr->out)) return rc;
+    if (int rc = stats_plan("gen_rts_nodes_stats", off.data(), R, sr->q, sr->nq, 0, &plan))
+      return rc;
+  }
   if (!c) return fail(WFPT_ERR_ARG, "null pointer (context)");
   const int64_t m = G - 1;
   const int64_t ws = workspace_bytes > 0 ? workspace_bytes : (int64_t)1 << 30;
@@ -135,8 +268,10 @@ int wfpt_gen_rts_nodes_ex(wfpt_ctx* c, const double* grid, int64_t G, const wfpt
       return fail(WFPT_ERR_UNSUPPORTED, "gen_rts_nodes: row " + std::to_string(r) +
                                     " has no CDF (the sum of its grid densities is " +
                                     std::to_string(tot[r]) + "); no draws are returned");
+  if (sr)
+    if (int rc = stats_run(c, plan, c->sim.out.p, c->sim.off.p, off.data(), R, sr->out)) return rc;
   if (total > 0) {
-    HIP_TRY(hipMemcpy(out, c->sim.out.p, total * sizeof(double), hipMemcpyDeviceToHost));
+    if (out) HIP_TRY(hipMemcpy(out, c->sim.out.p, total * sizeof(double), hipMemcpyDeviceToHost));
     if (out_idx)
       HIP_TRY(hipMemcpy(out_idx, c->sim.idx.p, total * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (out_u_choice) {
@@ -154,24 +289,15 @@ int wfpt_gen_rts_nodes_ex(wfpt_ctx* c, const double* grid, int64_t G, const wfpt
   return WFPT_OK;
 }
 
-int wfpt_gen_rts_nodes(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_params* rows,
-                       int64_t R, const int64_t* counts, const double* u_choice,
-                       const double* u_delay, uint64_t seed, int64_t workspace_bytes,
-                       double* out) {
-  return wfpt_gen_rts_nodes_ex(c, grid, G, rows, R, counts, u_choice, u_delay, seed,
-                               workspace_bytes, out, nullptr, nullptr, nullptr, nullptr, nullptr);
-}
-
 // ---------------------------------------------------------------------------
 // Diffusion-path simulator (sim_drift_kernel; hddm/generate.py:208-319)
 
-int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx* c, const wfpt_params* rows, int64_t R,
-                                const double* sw, const int64_t* counts, double dt,
-                                double intra_sv, int64_t max_steps, uint64_t seed, int64_t row0,
-                                int32_t wave_draws, double* out, int64_t* n_unfinished,
-                                double* out_y0, double* out_delay, double* out_drift,
-                                double* out_drift_switch, int64_t* out_n_steps,
-                                int64_t* out_wave_steps) {
+int gen_rts_drift_nodes_impl(wfpt_ctx* c, const wfpt_params* rows, int64_t R, const double* sw,
+                             const int64_t* counts, double dt, double intra_sv,
+                             int64_t max_steps, uint64_t seed, int64_t row0, int32_t wave_draws,
+                             double* out, int64_t* n_unfinished, double* out_y0,
+                             double* out_delay, double* out_drift, double* out_drift_switch,
+                             int64_t* out_n_steps, int64_t* out_wave_steps, const StatsReq* sr) {
   if (!rows || !counts || !n_unfinished)
     return fail(WFPT_ERR_ARG, "null pointer (rows / counts / n_unfinished)");
   if (R < 1) return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: R < 1");
@@ -194,7 +320,13 @@ int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx* c, const wfpt_params* rows, int64_t R,
   std::vector<int64_t> off;
   if (int rc = counts_to_offsets("gen_rts_drift_nodes", counts, R, &off)) return rc;
   const int64_t total = off[R];
-  if (!out && total > 0) return fail(WFPT_ERR_ARG, "null pointer (out)");
+  if (!out && total > 0 && !sr) return fail(WFPT_ERR_ARG, "null pointer (out)");
+  StatsPlan plan;
+  if (sr) {
+    if (int rc = stats_check_q("gen_rts_drift_nodes_stats", sr->q, sr->nq, sr->out)) return rc;
+    if (int rc = stats_plan("gen_rts_drift_nodes_stats", off.data(), R, sr->q, sr->nq, 0, &plan))
+      return rc;
+  }
   std::vector<wfpt::DriftRow> tab((size_t)R);
   for (int64_t r = 0; r < R; ++r) {
     const wfpt_params& P = rows[r];
@@ -233,7 +365,7 @@ int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx* c, const wfpt_params* rows, int64_t R,
   if (waves >= (int64_t)1 << 31)
     return fail(WFPT_ERR_ARG, "gen_rts_drift_nodes: too many draws for one call");
   *n_unfinished = 0;
-  if (total == 0) return WFPT_OK;
+  if (total == 0 && !sr) return WFPT_OK;
   WFPT_RANGE("wfpt_gen_rts_drift_nodes");
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
@@ -280,8 +412,9 @@ int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx* c, const wfpt_params* rows, int64_t R,
     c->k_ms += ms;
     c->launches += 1;
   }
-  HIP_TRY(hipMemcpyAsync(out, c->sim.out.p, total * sizeof(double), hipMemcpyDeviceToHost,
-                         c->stream));
+  if (out && total > 0)
+    HIP_TRY(hipMemcpyAsync(out, c->sim.out.p, total * sizeof(double), hipMemcpyDeviceToHost,
+                           c->stream));
   const std::pair<double*, const double*> copies[] = {
       {out_y0, C.y0}, {out_delay, C.delay}, {out_drift, C.drift},
       {out_drift_switch, C.drift_switch}};
@@ -295,11 +428,115 @@ int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx* c, const wfpt_params* rows, int64_t R,
   if (out_wave_steps)
     HIP_TRY(hipMemcpyAsync(out_wave_steps, C.wave_steps, waves * sizeof(int64_t),
                            hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  int64_t nan = 0;  // only a draw that ran out of steps is NaN
-  for (int64_t i = 0; i < total; ++i) nan += std::isnan(out[i]) ? 1 : 0;
+  if (sr) {
+    if (int rc = stats_run(c, plan, c->sim.out.p, c->sim.off.p, off.data(), R, sr->out)) return rc;
+  } else {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  unsigned long long nan_dev = 0;
+  if (!out && total > 0) {  // the draws stay on the device: their NaNs are counted there
+    HIP_TRY(c->stats.count.reserve(1));
+    HIP_TRY(hipMemsetAsync(c->stats.count.p, 0, sizeof(unsigned long long), c->stream));
+    wfpt::launch_stats_count_nan(c->sim.out.p, total, c->stats.count.p, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&nan_dev, c->stats.count.p, sizeof(unsigned long long),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  int64_t nan = (int64_t)nan_dev;  // only a draw that ran out of steps is NaN
+  if (out)
+    for (int64_t i = 0; i < total; ++i) nan += std::isnan(out[i]) ? 1 : 0;
   *n_unfinished = nan;
   return WFPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wfpt_gen_rts_nodes_ex(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_params* rows,
+                          int64_t R, const int64_t* counts, const double* u_choice,
+                          const double* u_delay, uint64_t seed, int64_t workspace_bytes,
+                          double* out, double* out_pdf, double* out_cdf, int64_t* out_idx,
+                          double* out_u_choice, double* out_u_delay) {
+  return gen_rts_nodes_impl(c, grid, G, rows, R, counts, u_choice, u_delay, seed, workspace_bytes,
+                            out, out_pdf, out_cdf, out_idx, out_u_choice, out_u_delay, nullptr);
+}
+
+int wfpt_gen_rts_nodes(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_params* rows,
+                       int64_t R, const int64_t* counts, const double* u_choice,
+                       const double* u_delay, uint64_t seed, int64_t workspace_bytes,
+                       double* out) {
+  return gen_rts_nodes_impl(c, grid, G, rows, R, counts, u_choice, u_delay, seed, workspace_bytes,
+                            out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int wfpt_gen_rts_nodes_stats(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_params* rows,
+                             int64_t R, const int64_t* counts, const double* u_choice,
+                             const double* u_delay, uint64_t seed, int64_t workspace_bytes,
+                             double* out, const double* q, int32_t nq, double* stats_out) {
+  const StatsReq sr{q, nq, stats_out};
+  return gen_rts_nodes_impl(c, grid, G, rows, R, counts, u_choice, u_delay, seed, workspace_bytes,
+                            out, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
+}
+
+int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx* c, const wfpt_params* rows, int64_t R,
+                                const double* sw, const int64_t* counts, double dt,
+                                double intra_sv, int64_t max_steps, uint64_t seed, int64_t row0,
+                                int32_t wave_draws, double* out, int64_t* n_unfinished,
+                                double* out_y0, double* out_delay, double* out_drift,
+                                double* out_drift_switch, int64_t* out_n_steps,
+                                int64_t* out_wave_steps) {
+  return gen_rts_drift_nodes_impl(c, rows, R, sw, counts, dt, intra_sv, max_steps, seed, row0,
+                                  wave_draws, out, n_unfinished, out_y0, out_delay, out_drift,
+                                  out_drift_switch, out_n_steps, out_wave_steps, nullptr);
+}
+
+int wfpt_gen_rts_drift_nodes_stats(wfpt_ctx* c, const wfpt_params* rows, int64_t R,
+                                   const double* sw, const int64_t* counts, double dt,
+                                   double intra_sv, int64_t max_steps, uint64_t seed, double* out,
+                                   int64_t* n_unfinished, const double* q, int32_t nq,
+                                   double* stats_out) {
+  const StatsReq sr{q, nq, stats_out};
+  return gen_rts_drift_nodes_impl(c, rows, R, sw, counts, dt, intra_sv, max_steps, seed, 0, 0,
+                                  out, n_unfinished, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, &sr);
+}
+
+// ---------------------------------------------------------------------------
+// Per-row RT statistics of host draws (stats_kernels.hip; hddm/utils.py:241-265)
+
+int wfpt_rt_stats_rows_ex(wfpt_ctx* c, const double* rts, const int64_t* off, int64_t R,
+                          const double* q, int32_t nq, int32_t tier, double* out) {
+  if (!off) return fail(WFPT_ERR_ARG, "null pointer (off)");
+  if (R < 1) return fail(WFPT_ERR_ARG, "rt_stats_rows: R < 1");
+  if (R >= (int64_t)1 << 31) return fail(WFPT_ERR_ARG, "rt_stats_rows: R must be < 2^31");
+  if (int rc = stats_check_q("rt_stats_rows", q, nq, out)) return rc;
+  if (off[0] != 0) return fail(WFPT_ERR_ARG, "rt_stats_rows: off[0] != 0");
+  for (int64_t r = 0; r < R; ++r)
+    if (off[r + 1] < off[r])
+      return fail(WFPT_ERR_ARG, "rt_stats_rows: off falls at row " + std::to_string(r));
+  const int64_t total = off[R];
+  if (!rts && total > 0) return fail(WFPT_ERR_ARG, "null pointer (rts)");
+  StatsPlan plan;
+  if (int rc = stats_plan("rt_stats_rows", off, R, q, nq, tier, &plan)) return rc;
+  if (!c) return fail(WFPT_ERR_ARG, "null pointer (context)");
+  WFPT_RANGE("wfpt_rt_stats_rows");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  HIP_TRY(c->sim.off.reserve(R + 1));
+  HIP_TRY(c->sim.out.reserve(std::max<int64_t>(total, 1)));
+  HIP_TRY(hipMemcpyAsync(c->sim.off.p, off, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
+                         c->stream));
+  if (total > 0)
+    HIP_TRY(hipMemcpyAsync(c->sim.out.p, rts, total * sizeof(double), hipMemcpyHostToDevice,
+                           c->stream));
+  return stats_run(c, plan, c->sim.out.p, c->sim.off.p, off, R, out);
+}
+
+int wfpt_rt_stats_rows(wfpt_ctx* c, const double* rts, const int64_t* off, int64_t R,
+                       const double* q, int32_t nq, double* out) {
+  return wfpt_rt_stats_rows_ex(c, rts, off, R, q, nq, 0, out);
 }
 
 int wfpt_gen_rts_drift_nodes(wfpt_ctx* c, const wfpt_params* rows, int64_t R, const double* sw,

@@ -646,6 +646,39 @@ class HDDM:
                              "node": np.repeat(np.tile(np.arange(self.n_nodes), S), per),
                              "rt": rts, "response": (rts > 0).astype(np.int64)})
 
+    def post_pred_stats(self, samples=500, seed=None, cdf_range=(-5, 5), dt=1e-4, method="cdf",
+                        quantiles=(10, 30, 50, 70, 90), return_sampled=False):
+        """The posterior predictive check (hddm.utils.post_pred_stats over
+        post_pred_gen's data sets, utils.py:241-299) without the data sets:
+        post_pred_gen's draws (same arguments, same seed: the same draws) are
+        reduced to gen_ppc_stats' statistics per (sweep, node) on the device by
+        ONE fused call (wfpt.gen_rts_stats_nodes; no draw is copied to the
+        host), the observed nodes by one wfpt.rt_stats_rows call, and
+        ppc.summarize compares the two.
+
+        Returns ppc.summarize's DataFrame indexed by (node, stat), node an index
+        into node_keys; with return_sampled=True also the sampled statistics
+        (len(picked), n_nodes, K) in wfpt.rt_stats_names' order."""
+        from . import ppc
+        picked, P = self.post_pred_rows(samples)
+        S = picked.size
+        if seed is None:
+            seed = int(self.rng.integers(0, 2 ** 63))
+        if method not in ("cdf", "drift"):
+            raise ValueError("method must be 'cdf' or 'drift'")
+        kw = {"dt": dt} if method == "drift" else \
+            {"cdf_lb": cdf_range[0], "cdf_ub": cdf_range[1], "dt": dt}
+        sampled, _ = _wfpt.gen_rts_stats_nodes(P.reshape(S * self.n_nodes, 8),
+                                               np.tile(self.node_counts, S), method=method,
+                                               quantiles=quantiles, seed=seed, **kw)
+        sampled = sampled.reshape(S, self.n_nodes, -1)
+        order = np.argsort(self.node_codes, kind="stable")
+        offsets = np.zeros(self.n_nodes + 1, dtype=np.int64)
+        np.cumsum(self.node_counts, out=offsets[1:])
+        observed = _wfpt.rt_stats_rows(self.signed_rt[order], offsets, quantiles)
+        table = ppc.summarize(observed, sampled, _wfpt.rt_stats_names(quantiles))
+        return (table, sampled) if return_sampled else table
+
 
 class HDDMChains(HDDM):
     """`chains` independent chains of HDDM(...) sampled in lockstep on one GPU.
@@ -743,7 +776,7 @@ class HDDMChains(HDDM):
     node_logp_multi = _refuses("HDDMChains: node_logp_chains() scores every chain's tables")
     set_values = _refuses("HDDMChains: group[f][chain, level] holds one value per chain")
     optimize = quantile_objective = _refuses("HDDMChains: point fits take one chain (HDDM)")
-    post_pred_rows = post_pred_gen = _refuses(
+    post_pred_rows = post_pred_gen = post_pred_stats = _refuses(
         "HDDMChains: posterior predictive draws take one chain (HDDM)")
 
     def _unit_group_c(self, fam):

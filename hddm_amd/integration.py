@@ -84,7 +84,7 @@ def _simulated_drift(params, samples=1000, dt=1e-4, intra_sv=1.):
 
 
 def install(wfpt_module=None, cdfdif_module=None, likelihoods_module=None, rl=False,
-            drift=False, generate_module=None):
+            drift=False, generate_module=None, utils_module=None):
     """Route HDDM's likelihood and CDF calls to libwfpt_amd.so.
 
     `rl=True` also rebinds the reinforcement-learning likelihoods (RL_PATH)
@@ -96,6 +96,11 @@ def install(wfpt_module=None, cdfdif_module=None, likelihoods_module=None, rl=Fa
     device's diffusion-path simulator, which `gen_rts(method='drift')` then
     calls (generate.py:188-189). It returns the RTs without the paths, which is
     why it is opt-in; by default `generate` is left alone.
+
+    If `hddm.utils` is given as `utils_module` or already imported, its
+    `post_pred_stats` (utils.py:270-299) is rebound to `ppc.post_pred_stats`,
+    which reduces every simulated data set on the device; when the module is
+    absent nothing happens.
 
     `wfpt_module` / `cdfdif_module` default to the already-imported (or
     importable) reference extensions `wfpt` and `cdfdif_wrapper`; when one is
@@ -125,6 +130,10 @@ def install(wfpt_module=None, cdfdif_module=None, likelihoods_module=None, rl=Fa
         if hasattr(lk, "Wfpt"):
             inst._attrs.append((lk, "Wfpt", lk.Wfpt))
             lk.Wfpt = amd_lk.generate_wfpt_stochastic_class()
+    utils = utils_module if utils_module is not None else sys.modules.get("hddm.utils")
+    if utils is not None:
+        from . import ppc
+        _patch(inst, "hddm.utils", utils, ppc, ("post_pred_stats",))
     if drift:
         gen = generate_module if generate_module is not None else sys.modules.get("hddm.generate")
         if gen is not None:

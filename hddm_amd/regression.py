@@ -331,5 +331,5 @@ class HDDMRegressor(HDDM):
 
     node_logp_multi = _refuses("HDDMRegressor scores one table per call")
     optimize = quantile_objective = _refuses("the regressor's point fits are not implemented")
-    post_pred_rows = post_pred_gen = _refuses(
+    post_pred_rows = post_pred_gen = post_pred_stats = _refuses(
         "the regressor's posterior predictive is not implemented")

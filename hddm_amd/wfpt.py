@@ -24,7 +24,10 @@ parameter rows in one call, grid, CDF and search on the device (posterior
 predictive data sets: HDDM.post_pred_gen). `gen_rts_from_drift_nodes` /
 `gen_rts_from_drift` are the reference's 'drift' sampling method
 (hddm/generate.py:208-319: every RT a simulated diffusion path, with the
-in-trial drift switch) on the device. `RegDataset(rt, design)` keeps a
+in-trial drift switch) on the device. `rt_stats_rows` reduces many rows of
+signed RTs to the posterior predictive check's statistics (gen_ppc_stats,
+hddm/utils.py:241-265) on the device, and `gen_rts_stats_nodes` does so for
+the draws of either sampler without copying them out. `RegDataset(rt, design)` keeps a
 design matrix resident and forms HDDMRegressor's trial-wise parameters
 link(design . coefficients) on the device (hddm_regression.py:26-36).
 """
@@ -35,8 +38,9 @@ import numpy as np
 from . import _lib
 
 __all__ = ["pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "gen_rts_from_cdf",
-           "gen_rts_from_cdf_nodes", "gen_rts_from_drift_nodes", "gen_rts_from_drift", "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl",
-           "wiener_like_multi_rlddm", "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_terms",
+           "gen_rts_from_cdf_nodes", "gen_rts_from_drift_nodes", "gen_rts_from_drift",
+           "rt_stats_rows", "rt_stats_names", "gen_rts_stats_nodes", "Dataset", "prob_ub",
+           "wiener_like_rlddm", "wiener_like_rl", "wiener_like_multi_rlddm", "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_terms",
            "wiener_like_rl_terms", "wiener_like_multi_rlddm_terms", "RegDataset"]
 
 
@@ -388,6 +392,189 @@ def gen_rts_from_drift(v, sv, a, z, sz, t, st, samples=1000, dt=1e-4, intra_sv=1
         sw = [[switch["v_switch"], switch.get("V_switch", 0.0), switch["t_switch"]]]
     return gen_rts_from_drift_nodes([[v, sv, a, z, sz, t, st]], int(samples), dt, intra_sv, seed,
                                     switch=sw)[0]
+
+
+PPC_QUANTILES = (10, 30, 50, 70, 90)  # gen_ppc_stats' default (hddm/utils.py:241)
+
+
+def _check_quantiles(quantiles):
+    q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+    if q.size > 16:
+        raise ValueError("at most 16 quantiles")
+    if not np.all((q >= 0) & (q <= 100)):  # NaN fails both comparisons
+        raise ValueError("quantiles must lie in [0, 100]")
+    return q
+
+
+def rt_stats_names(quantiles=PPC_QUANTILES):
+    """The columns of rt_stats_rows: n, n_ub, n_lb, then gen_ppc_stats' own
+    names in its order (hddm/utils.py:250-265): accuracy, mean_ub, std_ub,
+    '10q_ub', ..., mean_lb, std_lb, '10q_lb', ..."""
+    keys = [str(q) + "q" for q in quantiles]
+    return (["n", "n_ub", "n_lb", "accuracy", "mean_ub", "std_ub"] + [k + "_ub" for k in keys]
+            + ["mean_lb", "std_lb"] + [k + "_lb" for k in keys])
+
+
+def rt_stats_rows(rts, offsets, quantiles=PPC_QUANTILES, tier=0):
+    """gen_ppc_stats (hddm/utils.py:241-265) for R rows of signed RTs in one
+    call on the GPU (wfpt_rt_stats_rows): row r is rts[offsets[r]:offsets[r + 1]].
+
+    Returns an (R, 8 + 2 len(quantiles)) array with rt_stats_names' columns.
+    The upper boundary's draws are those > 0, the lower boundary's those < 0
+    (mean_lb is the mean of the signed values, the lower quantiles are taken
+    over |x|); a draw that is 0 or NaN counts in n only. std is np.std
+    (ddof=0); each quantile equals scipy.stats.scoreatpercentile bit for bit;
+    an empty boundary gives NaN. tier: 0 picks the kernel by row length, 1 / 2 /
+    3 force the wave / block / global one (ValueError when a row does not fit).
+    """
+    q = _check_quantiles(quantiles)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    if off.ndim != 1 or off.size < 2:
+        raise ValueError("offsets must hold R + 1 >= 2 entries")
+    if off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError("offsets must rise from 0")
+    x = np.ascontiguousarray(rts, dtype=np.float64)
+    if x.ndim != 1 or x.size != off[-1]:
+        raise ValueError(f"rts must hold offsets[-1] = {int(off[-1])} values")
+    if tier not in (0, 1, 2, 3):
+        raise ValueError("tier must be 0, 1, 2 or 3")
+    R = off.size - 1
+    out = np.empty((R, 8 + 2 * q.size))
+    c = _lib.context()
+    _lib.check(_lib.wfpt_rt_stats_rows_ex(c.handle, _lib.dptr(x), _i64ptr(off), R, _lib.dptr(q),
+                                          q.size, int(tier), _lib.dptr(out)))
+    return out
+
+
+def _sampler_table(params, samples):
+    """The samplers' (R, 8) table, per-row counts and offsets."""
+    pm = np.asarray(params, dtype=np.float64)
+    if pm.ndim != 2 or pm.shape[1] not in (7, 8) or pm.shape[0] < 1:
+        raise ValueError("params must have shape (R, 7) or (R, 8), R >= 1")
+    R = pm.shape[0]
+    table = np.zeros((R, 8))
+    table[:, :pm.shape[1]] = pm
+    cnt = np.asarray(samples)
+    if cnt.ndim == 0:
+        cnt = np.full(R, int(cnt))
+    if cnt.shape != (R,) or not np.issubdtype(cnt.dtype, np.integer):
+        raise ValueError(f"samples must be an int or {R} ints")
+    cnt = np.ascontiguousarray(cnt, dtype=np.int64)
+    if np.any(cnt < 0):
+        raise ValueError("samples must be non-negative")
+    offsets = np.zeros(R + 1, dtype=np.int64)
+    np.cumsum(cnt, out=offsets[1:])
+    return table, cnt, offsets
+
+
+def _stats_from_cdf(table, cnt, offsets, q, out, stats, cdf_lb=-6, cdf_ub=6, dt=1e-2, u=None,
+                    u_delay=None, seed=None, max_workspace=None):
+    R, total = table.shape[0], int(offsets[-1])
+    has_st = table[:, 6] != 0
+    if u is None and u_delay is not None:
+        raise ValueError("u_delay needs u")
+    if u is not None:
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.shape != (total,):
+            raise ValueError(f"u must hold sum(samples) = {total} uniforms")
+        if has_st.any() and u_delay is None:
+            raise ValueError("u_delay is needed: a row has st != 0")
+        if u_delay is not None:
+            u_delay = np.ascontiguousarray(u_delay, dtype=np.float64)
+            if u_delay.shape != (total,):
+                raise ValueError(f"u_delay must hold sum(samples) = {total} uniforms")
+        for nm, arr in (("u", u), ("u_delay", u_delay)):
+            if arr is not None and arr.size and not (arr.min() >= 0 and arr.max() < 1):
+                raise ValueError(f"{nm} must lie in [0, 1)")
+    elif seed is None:
+        # the reference's order of draws from the global RNG (wfpt.pyx:340-345)
+        u = np.empty(total)
+        u_delay = np.zeros(total) if has_st.any() else None
+        for r in range(R):
+            lo, hi = offsets[r], offsets[r + 1]
+            u[lo:hi] = np.random.rand(int(cnt[r]))
+            if has_st[r]:
+                u_delay[lo:hi] = np.random.rand(int(cnt[r]))
+    x = np.arange(cdf_lb, cdf_ub, dt)
+    if x.shape[0] < 2:
+        raise ValueError("the grid np.arange(cdf_lb, cdf_ub, dt) needs at least two points")
+    ws = 0 if max_workspace is None else int(max_workspace)
+    if ws < 0:
+        raise ValueError("max_workspace must be positive")
+    seed = 0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+    rc = _lib.wfpt_gen_rts_nodes_stats(
+        _lib.context().handle, _lib.dptr(x), x.shape[0], table.ctypes.data_as(_lib._PP), R,
+        _i64ptr(cnt), _lib.dptr(u) if u is not None else None,
+        _lib.dptr(u_delay) if u_delay is not None else None, seed, ws,
+        _lib.dptr(out) if out is not None else None, _lib.dptr(q), q.size, _lib.dptr(stats))
+    if rc == 4 and b"has no CDF" in _lib.wfpt_last_error():
+        raise RuntimeError("wfpt_amd: " + _lib.wfpt_last_error().decode(errors="replace"))
+    _lib.check(rc)
+
+
+def _stats_from_drift(table, cnt, offsets, q, out, stats, dt=1e-4, intra_sv=1., seed=None,
+                      switch=None, max_t=20., unfinished="raise"):
+    R, total = table.shape[0], int(offsets[-1])
+    dt, intra_sv = float(dt), float(intra_sv)
+    if not (dt > 0 and np.isfinite(dt)):
+        raise ValueError("dt must be positive")
+    if not (intra_sv > 0 and np.isfinite(intra_sv)):
+        raise ValueError("intra_sv must be positive")
+    if not max_t > 0:
+        raise ValueError("max_t must be positive")
+    max_steps = int(np.ceil(float(max_t) / dt))
+    if not 1 <= max_steps <= 2 ** 31:
+        raise ValueError("ceil(max_t / dt) must lie in [1, 2^31]")
+    if unfinished not in ("raise", "nan"):
+        raise ValueError("unfinished must be 'raise' or 'nan'")
+    sw = None
+    if switch is not None:
+        sw = np.ascontiguousarray(switch, dtype=np.float64)
+        if sw.shape != (R, 3):
+            raise ValueError(f"switch must have shape ({R}, 3): v_switch, V_switch, t_switch")
+        if not np.all(np.round(sw[:, 2] / dt) >= 1):  # generate.py:237-239
+            raise ValueError("t_switch / dt must round to at least one step")
+    if seed is None:
+        lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
+        seed = int(lo) | (int(hi) << 32)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    nun = ctypes.c_int64()
+    rc = _lib.wfpt_gen_rts_drift_nodes_stats(
+        _lib.context().handle, table.ctypes.data_as(_lib._PP), R,
+        _lib.dptr(sw) if sw is not None else None, _i64ptr(cnt), dt, intra_sv, max_steps, seed,
+        _lib.dptr(out) if out is not None else None, ctypes.byref(nun), _lib.dptr(q), q.size,
+        _lib.dptr(stats))
+    if rc == 4 and b"cannot be simulated" in _lib.wfpt_last_error():
+        raise RuntimeError("wfpt_amd: " + _lib.wfpt_last_error().decode(errors="replace"))
+    _lib.check(rc)
+    if nun.value and unfinished == "raise":
+        raise RuntimeError(f"wfpt_amd: {nun.value} of {total} draws had not crossed a boundary "
+                           f"after {max_steps} steps (max_t = {max_t})")
+
+
+def gen_rts_stats_nodes(params, samples, method="cdf", quantiles=PPC_QUANTILES, seed=None,
+                        return_draws=False, **sampler_kw):
+    """The draws of gen_rts_from_cdf_nodes (method='cdf') or
+    gen_rts_from_drift_nodes (method='drift') for R parameter rows, reduced to
+    rt_stats_rows' statistics while they are still in device memory
+    (wfpt_gen_rts_nodes_stats / wfpt_gen_rts_drift_nodes_stats): with
+    return_draws=False no draw is copied to the host.
+
+    params, samples, seed and sampler_kw (cdf: cdf_lb, cdf_ub, dt, u, u_delay,
+    max_workspace; drift: dt, intra_sv, switch, max_t, unfinished) are the
+    sampler's own, with its seed, uniform and RNG rules: the draws are the ones
+    that sampler returns for the same arguments. Returns (stats, offsets), and
+    the draws as a third element with return_draws=True; stats is (R, 8 + 2
+    len(quantiles)) in rt_stats_names' order."""
+    if method not in ("cdf", "drift"):
+        raise ValueError("method must be 'cdf' or 'drift'")
+    q = _check_quantiles(quantiles)
+    table, cnt, offsets = _sampler_table(params, samples)
+    stats = np.empty((table.shape[0], 8 + 2 * q.size))
+    out = np.empty(int(offsets[-1])) if return_draws else None
+    run = _stats_from_cdf if method == "cdf" else _stats_from_drift
+    run(table, cnt, offsets, q, out, stats, seed=seed, **sampler_kw)
+    return (stats, offsets, out) if return_draws else (stats, offsets)
 
 
 class Dataset:

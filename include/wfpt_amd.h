@@ -23,6 +23,8 @@
  *                             src/wfpt.pyx:323-354
  *   wfpt_gen_rts_drift_nodes <- generate._gen_rts_from_simulated_drift, many rows
  *                             hddm/generate.py:208-319
+ *   wfpt_rt_stats_rows     <- utils.gen_ppc_stats applied to many rows of RTs
+ *                             hddm/utils.py:241-265
  * The Python binding that keeps the reference signatures is
  * hddm_amd/wfpt.py (ctypes); INTEGRATION.md shows the drop-in.
  */
@@ -536,6 +538,54 @@ int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx *ctx, const wfpt_params *rows, int64_t 
                                 double *out_y0, double *out_delay, double *out_drift,
                                 double *out_drift_switch, int64_t *out_n_steps,
                                 int64_t *out_wave_steps);
+
+/* ---- per-row RT statistics ----------------------------------------------- */
+/* gen_ppc_stats (hddm/utils.py:241-265), the posterior predictive check's
+ * summary statistics, for R rows of signed RTs in one call. Row r's draws are
+ * rts[off[r] .. off[r + 1]) (off: R + 1 rising offsets from 0); ub is the set
+ * of draws x > 0, lb the set x < 0; a draw that is 0 or NaN is in neither but
+ * counts in n. Per row, K = 8 + 2 nq doubles go to out[r K ..):
+ *   n, n_ub, n_lb, accuracy = n_ub / n,
+ *   mean_ub, std_ub, q_ub[0 .. nq),  mean_lb (signed: negative), std_lb, q_lb[0 .. nq)
+ * std is the population standard deviation (np.std, ddof = 0), two-pass. q_ub[k]
+ * / q_lb[k] is scipy.stats.scoreatpercentile(x[x > 0] / abs(x[x < 0]), q[k]) bit
+ * for bit: on the m sorted values s, idx = q / 100. * (m - 1), i = (int)idx, s[i]
+ * when i == idx, else (s[i] w0 + s[i + 1] w1) / (w0 + w1) with w0 = (i + 1) - idx,
+ * w1 = idx - i. An empty set gives NaN for its mean, std and percentiles, n == 0 a
+ * NaN accuracy. The counts, the accuracy and the percentiles do not depend on
+ * the kernel that scored the row; the means and standard deviations are summed
+ * in an order that depends on the row's values alone.
+ *   q         nq percentiles in [0, 100], 0 <= nq <= 16 (NULL when nq == 0)
+ * WFPT_ERR_ARG before any device work: null pointers, R < 1, nq outside
+ * 0..16, a q outside [0, 100] or NaN, off[0] != 0 or a falling off. */
+int wfpt_rt_stats_rows(wfpt_ctx *ctx, const double *rts, const int64_t *off, int64_t R,
+                       const double *q, int32_t nq, double *out);
+/* As wfpt_rt_stats_rows (utils.py:241-265), for tests: tier 0 is the library's
+ * choice by row length, 1 / 2 / 3 force the wave (rows of at most 256 draws) /
+ * block (at most 4096) / global tier for every row. WFPT_ERR_ARG: a row the
+ * forced tier cannot hold, tier outside 0..3. */
+int wfpt_rt_stats_rows_ex(wfpt_ctx *ctx, const double *rts, const int64_t *off, int64_t R,
+                          const double *q, int32_t nq, int32_t tier, double *out);
+/* wfpt_gen_rts_nodes followed by the statistics of its draws (utils.py:241-265)
+ * while they are still in device memory: the draws are those of
+ * wfpt_gen_rts_nodes for the same arguments bit for bit, stats_out [R x (8 + 2
+ * nq)] is what wfpt_rt_stats_rows gives for them. out may be NULL: no draw is
+ * copied to the host. A call that fails (an argument error, a row without a
+ * CDF) writes neither out nor stats_out. */
+int wfpt_gen_rts_nodes_stats(wfpt_ctx *ctx, const double *grid, int64_t G,
+                             const wfpt_params *rows, int64_t R, const int64_t *counts,
+                             const double *u_choice, const double *u_delay, uint64_t seed,
+                             int64_t workspace_bytes, double *out, const double *q, int32_t nq,
+                             double *stats_out);
+/* wfpt_gen_rts_drift_nodes followed by the statistics of its draws
+ * (utils.py:241-265), as wfpt_gen_rts_nodes_stats: the same draws bit for bit,
+ * out may be NULL, *n_unfinished is counted either way. An unfinished walk's
+ * NaN counts in its row's n and in neither boundary. */
+int wfpt_gen_rts_drift_nodes_stats(wfpt_ctx *ctx, const wfpt_params *rows, int64_t R,
+                                   const double *sw, const int64_t *counts, double dt,
+                                   double intra_sv, int64_t max_steps, uint64_t seed,
+                                   double *out, int64_t *n_unfinished, const double *q,
+                                   int32_t nq, double *stats_out);
 
 /* ---- measurement -------------------------------------------------------- */
 /* Under WFPT_PROF_EVENTS: device milliseconds of the RT sampler's stages
