@@ -30,13 +30,21 @@ _lib = ctypes.CDLL(LIB_PATH)
 
 WFPT_OK = 0
 WFPT_MAX_DEPTH = 24
+WFPT_DS_INPUT_ORDER = 1
+# WFPT_PATH_* (include/wfpt_amd.h): kernels the last likelihood call launched
+PATH_LEAN, PATH_ENGINE, PATH_SMALL, PATH_REDO = 1, 2, 4, 8
+PATH_FOLD, PATH_DIRECT, PATH_FIXED, PATH_SPLIT = 16, 32, 64, 128
+PATH_SMALL_SPLIT, PATH_NODE_SPLIT, PATH_NODE_RARE = 256, 512, 1024
+# regression links (include/wfpt_amd.h)
+LINK_IDENTITY, LINK_EXP, LINK_INVLOGIT = 0, 1, 2
 
 _D = ctypes.c_double
 _I = ctypes.c_int
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
-_PD = ctypes.POINTER(ctypes.c_double)
+_U64 = ctypes.c_uint64
 _VP = ctypes.c_void_p
+_CP = ctypes.c_char_p
 
 
 class Params(ctypes.Structure):
@@ -48,192 +56,136 @@ class Knobs(ctypes.Structure):
                 ("simps_err", _D), ("w_outlier", _D)]
 
 
-_PP = ctypes.POINTER(Params)
-_PK = ctypes.POINTER(Knobs)
-
-
-def _sig(name, res, args):
-    f = getattr(_lib, name)
-    f.restype = res
-    f.argtypes = args
-    return f
-
-
-wfpt_last_error = _sig("wfpt_last_error", ctypes.c_char_p, [])
-wfpt_device_count = _sig("wfpt_device_count", _I, [ctypes.POINTER(_I)])
-wfpt_open = _sig("wfpt_open", _I, [_I, ctypes.POINTER(_VP)])
-wfpt_close = _sig("wfpt_close", None, [_VP])
-wfpt_dataset_create = _sig("wfpt_dataset_create", _I,
-                           [_VP, _PD, _I64, ctypes.POINTER(_I32), _I32, ctypes.POINTER(_VP)])
-wfpt_dataset_create_ex = _sig("wfpt_dataset_create_ex", _I,
-                              [_VP, _PD, _I64, ctypes.POINTER(_I32), _I32, _I,
-                               ctypes.POINTER(_VP)])
-WFPT_DS_INPUT_ORDER = 1
-wfpt_dataset_destroy = _sig("wfpt_dataset_destroy", None, [_VP])
-wfpt_dataset_size = _sig("wfpt_dataset_size", _I64, [_VP])
-wfpt_shard_range = _sig("wfpt_shard_range", None,
-                        [_I64, _I, _I, ctypes.POINTER(_I64), ctypes.POINTER(_I64)])
-wfpt_wiener_like = _sig("wfpt_wiener_like", _I, [_VP, _VP, _PP, _PK, _PD])
-wfpt_wiener_like_host = _sig("wfpt_wiener_like_host", _I, [_VP, _PD, _I64, _PP, _PK, _PD])
-wfpt_wiener_like_nodes = _sig("wfpt_wiener_like_nodes", _I, [_VP, _VP, _PP, _PK, _PD])
-
-
-def _raw(name, nargs):
-    """The same entry point through a prototype of plain addresses (ints): the
-    per-call paths (one likelihood per MCMC step) skip the per-argument ctypes
-    object conversions (~1 us per call through byref / data_as)."""
-    proto = ctypes.CFUNCTYPE(_I, *([ctypes.c_void_p] * nargs))
-    return proto(ctypes.cast(getattr(_lib, name), ctypes.c_void_p).value)
-
-
-raw_wiener_like = _raw("wfpt_wiener_like", 5)
-raw_wiener_like_nodes = _raw("wfpt_wiener_like_nodes", 5)
-wfpt_wiener_like_nodes_multi = _sig("wfpt_wiener_like_nodes_multi", _I,
-                                    [_VP, _VP, _PP, _I32, _PK, _PD])
-wfpt_wiener_like_nodes_multi_ex = _sig("wfpt_wiener_like_nodes_multi_ex", _I,
-                                       [_VP, _VP, _PP, _I32, _PK, _PD, _PD])
-_raw_multi_proto = ctypes.CFUNCTYPE(_I, _VP, _VP, _VP, _I32, _VP, _VP)
-raw_wiener_like_nodes_multi = _raw_multi_proto(
-    ctypes.cast(_lib.wfpt_wiener_like_nodes_multi, ctypes.c_void_p).value)
-wfpt_pdf_array = _sig("wfpt_pdf_array", _I, [_VP, _PD, _I64, _PP, _PK, _I, _PD])
-wfpt_full_pdf = _sig("wfpt_full_pdf", _I, [_VP, _D, _PP, _PK, _PD])
-wfpt_wiener_like_multi = _sig("wfpt_wiener_like_multi", _I,
-                              [_VP, _PD, _I64, ctypes.POINTER(_PD), _PD, _PK, _D, _PD])
-wfpt_wiener_like_multi_resident = _sig("wfpt_wiener_like_multi_resident", _I,
-                                       [_VP, _VP, ctypes.POINTER(_PD), _PD, _PK, _D, _PD])
-wfpt_wiener_like_nodes_ex = _sig("wfpt_wiener_like_nodes_ex", _I, [_VP, _VP, _PP, _PK, _PD, _PD])
-wfpt_wiener_like_multi_ex = _sig("wfpt_wiener_like_multi_ex", _I,
-                                 [_VP, _PD, _I64, ctypes.POINTER(_PD), _PD, _PK, _D, _PD, _PD])
-wfpt_wiener_like_multi_resident_ex = _sig("wfpt_wiener_like_multi_resident_ex", _I,
-                                          [_VP, _VP, ctypes.POINTER(_PD), _PD, _PK, _D, _PD, _PD])
-wfpt_dmat_cdf_array = _sig("wfpt_dmat_cdf_array", _I, [_VP, _PD, _I64, _PP, _D, _PD])
-wfpt_dmat_cdf_rows = _sig("wfpt_dmat_cdf_rows", _I,
-                          [_VP, _PP, _PD, _PD, _PD, _I64, _I32, _D, _PD, _PD, _PD])
-wfpt_comm_unique_id = _sig("wfpt_comm_unique_id", _I, [ctypes.c_char_p])
-wfpt_comm_init = _sig("wfpt_comm_init", _I, [_VP, _I, _I, ctypes.c_char_p])
-wfpt_wiener_like_allreduce = _sig("wfpt_wiener_like_allreduce", _I, [_VP, _VP, _PP, _PK, _PD])
-wfpt_comm_exchange_id = _sig("wfpt_comm_exchange_id", _I,
-                             [_I, _I, ctypes.c_char_p, _I, _I, ctypes.c_char_p])
-wfpt_comm_init_tcp = _sig("wfpt_comm_init_tcp", _I, [_VP, _I, _I, ctypes.c_char_p, _I, _I])
-wfpt_comm_init_all = _sig("wfpt_comm_init_all", _I, [ctypes.POINTER(_VP), _I])
-wfpt_wiener_like_allreduce_group = _sig("wfpt_wiener_like_allreduce_group", _I,
-                                        [ctypes.POINTER(_VP), ctypes.POINTER(_VP), _I, _PP, _PK,
-                                         _PD])
-wfpt_result_poison = _sig("wfpt_result_poison", _I, [_PD])
-wfpt_profile_enable = _sig("wfpt_profile_enable", _I, [_VP, _I])
-wfpt_profile_read = _sig("wfpt_profile_read", _I,
-                         [_VP, _PD, ctypes.POINTER(_I64), ctypes.POINTER(_I64), _I])
-try:  # diagnostics only: A/B runs may load an older library build without it
-    wfpt_profile_lists = _sig("wfpt_profile_lists", _I, [_VP, ctypes.POINTER(_I64), _I])
-    wfpt_debug_waves = _sig("wfpt_debug_waves", _I, [_VP, ctypes.POINTER(ctypes.c_uint64), _I64])
-except AttributeError:
-    wfpt_profile_lists = wfpt_debug_waves = None
-wfpt_synchronize = _sig("wfpt_synchronize", _I, [_VP])
-wfpt_wiener_like_trials = _sig("wfpt_wiener_like_trials", _I, [_VP, _VP, _PP, _PK, _PD, _PD])
-wfpt_dataset_order = _sig("wfpt_dataset_order", _I, [_VP, ctypes.POINTER(_I64)])
-wfpt_debug_partials = _sig("wfpt_debug_partials", _I,
-                           [_VP, _PD, ctypes.POINTER(ctypes.c_int32), _I64])
-wfpt_last_path = _sig("wfpt_last_path", _I, [_VP, ctypes.POINTER(_I)])
-wfpt_wiener_like_local = _sig("wfpt_wiener_like_local", _I, [_VP, _VP, _PP, _PK, _PD])
-wfpt_wiener_like_nodes_local = _sig("wfpt_wiener_like_nodes_local", _I, [_VP, _VP, _PP, _PK, _PD])
-wfpt_wiener_like_nodes_allreduce = _sig("wfpt_wiener_like_nodes_allreduce", _I,
-                                        [_VP, _VP, _PP, _I32, _PK, _PD])
-# WFPT_PATH_* (include/wfpt_amd.h): kernels the last likelihood call launched
-PATH_LEAN, PATH_ENGINE, PATH_SMALL, PATH_REDO = 1, 2, 4, 8
-PATH_FOLD, PATH_DIRECT, PATH_FIXED, PATH_SPLIT = 16, 32, 64, 128
-PATH_SMALL_SPLIT, PATH_NODE_SPLIT, PATH_NODE_RARE = 256, 512, 1024
-wfpt_decode_result = _sig("wfpt_decode_result", _I, [_PD, _PD])
-# reinforcement-learning family (include/wfpt_amd.h)
-_PI64 = ctypes.POINTER(_I64)
-wfpt_rl_dataset_create = _sig("wfpt_rl_dataset_create", _I,
-                              [_VP, _PD, _PI64, _PD, _PI64, _I64, ctypes.POINTER(_I32), _I32,
-                               ctypes.POINTER(_VP)])
-wfpt_rl_dataset_destroy = _sig("wfpt_rl_dataset_destroy", None, [_VP])
-wfpt_wiener_like_rlddm = _sig("wfpt_wiener_like_rlddm", _I, [_VP, _VP, _D, _D, _D, _PP, _PK, _PD])
-wfpt_wiener_like_rlddm_ex = _sig("wfpt_wiener_like_rlddm_ex", _I,
-                                 [_VP, _VP, _D, _D, _D, _PP, _PK, _PD, _PD, _PD])
-wfpt_wiener_like_rl = _sig("wfpt_wiener_like_rl", _I, [_VP, _VP, _D, _D, _D, _D, _D, _D, _D, _PD])
-wfpt_wiener_like_rl_ex = _sig("wfpt_wiener_like_rl_ex", _I,
-                              [_VP, _VP, _D, _D, _D, _D, _D, _D, _D, _PD, _PD, _PD])
-wfpt_wiener_like_multi_rlddm = _sig("wfpt_wiener_like_multi_rlddm", _I,
-                                    [_VP, _PD, _PI64, _PD, _PI64, _I64, _D, ctypes.POINTER(_PD),
-                                     _PD, _PK, _D, _PD])
-wfpt_wiener_like_multi_rlddm_ex = _sig("wfpt_wiener_like_multi_rlddm_ex", _I,
-                                       [_VP, _PD, _PI64, _PD, _PI64, _I64, _D,
-                                        ctypes.POINTER(_PD), _PD, _PK, _D, _PD, _PD, _PD])
-wfpt_wiener_like_rlddm_nodes = _sig("wfpt_wiener_like_rlddm_nodes", _I,
-                                    [_VP, _VP, _PD, _PP, _PK, _PD])
-wfpt_wiener_like_rlddm_nodes_ex = _sig("wfpt_wiener_like_rlddm_nodes_ex", _I,
-                                       [_VP, _VP, _PD, _PP, _PK, _PD, _PD, _PD])
-# regression likelihoods (include/wfpt_amd.h)
-LINK_IDENTITY, LINK_EXP, LINK_INVLOGIT = 0, 1, 2
-
-
 class RegTerm(ctypes.Structure):
     _fields_ = [(n, _I32) for n in ("param", "link", "col0", "ncol")]
 
 
+_PD = ctypes.POINTER(_D)
+_PPD = ctypes.POINTER(_PD)
+_PI = ctypes.POINTER(_I)
+_PI32 = ctypes.POINTER(_I32)
+_PI64 = ctypes.POINTER(_I64)
+_PU64 = ctypes.POINTER(_U64)
+_PVP = ctypes.POINTER(_VP)
+_PP = ctypes.POINTER(Params)
+_PK = ctypes.POINTER(Knobs)
 _PT = ctypes.POINTER(RegTerm)
-wfpt_reg_dataset_create = _sig("wfpt_reg_dataset_create", _I,
-                               [_VP, _PD, _I64, _PD, _I32, ctypes.POINTER(_I32), _I32,
-                                ctypes.POINTER(_VP)])
-wfpt_reg_dataset_destroy = _sig("wfpt_reg_dataset_destroy", None, [_VP])
-wfpt_wiener_like_reg = _sig("wfpt_wiener_like_reg", _I, [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD])
-wfpt_wiener_like_reg_ex = _sig("wfpt_wiener_like_reg_ex", _I,
-                               [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD, _PD, _PD])
-wfpt_wiener_like_reg_groups = _sig("wfpt_wiener_like_reg_groups", _I,
-                                   [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD])
-wfpt_wiener_like_reg_groups_ex = _sig("wfpt_wiener_like_reg_groups_ex", _I,
-                                      [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD, _PD, _PD])
-# RT sampler (include/wfpt_amd.h)
-_U64 = ctypes.c_uint64
-wfpt_gen_rts_nodes = _sig("wfpt_gen_rts_nodes", _I,
-                          [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD])
-wfpt_gen_rts_nodes_ex = _sig("wfpt_gen_rts_nodes_ex", _I,
-                             [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD, _PD,
-                              _PD, _PI64, _PD, _PD])
-wfpt_gen_rts_drift_nodes = _sig("wfpt_gen_rts_drift_nodes", _I,
-                                [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64, _PD, _PI64])
-wfpt_gen_rts_drift_nodes_ex = _sig("wfpt_gen_rts_drift_nodes_ex", _I,
-                                   [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64, _I64, _I32,
-                                    _PD, _PI64, _PD, _PD, _PD, _PD, _PI64, _PI64])
-wfpt_profile_stages = _sig("wfpt_profile_stages", _I, [_VP, _PD, _I])
-# per-row RT statistics (include/wfpt_amd.h)
-wfpt_rt_stats_rows = _sig("wfpt_rt_stats_rows", _I, [_VP, _PD, _PI64, _I64, _PD, _I32, _PD])
-wfpt_rt_stats_rows_ex = _sig("wfpt_rt_stats_rows_ex", _I,
-                             [_VP, _PD, _PI64, _I64, _PD, _I32, _I32, _PD])
-wfpt_gen_rts_nodes_stats = _sig("wfpt_gen_rts_nodes_stats", _I,
-                                [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD,
-                                 _PD, _I32, _PD])
-wfpt_gen_rts_drift_nodes_stats = _sig("wfpt_gen_rts_drift_nodes_stats", _I,
-                                      [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64, _PD, _PI64,
-                                       _PD, _I32, _PD])
 
-EXPORTED = [
-    "wfpt_device_count", "wfpt_open", "wfpt_close", "wfpt_last_error", "wfpt_dataset_create",
-    "wfpt_dataset_destroy", "wfpt_dataset_size", "wfpt_shard_range", "wfpt_wiener_like",
-    "wfpt_wiener_like_host", "wfpt_wiener_like_nodes", "wfpt_pdf_array", "wfpt_full_pdf",
-    "wfpt_wiener_like_multi", "wfpt_dmat_cdf_array", "wfpt_comm_unique_id", "wfpt_comm_init",
-    "wfpt_wiener_like_allreduce", "wfpt_profile_enable", "wfpt_profile_read", "wfpt_synchronize",
-    "wfpt_decode_result", "wfpt_profile_lists", "wfpt_debug_waves", "wfpt_dataset_create_ex",
-    "wfpt_wiener_like_multi_resident", "wfpt_comm_exchange_id", "wfpt_comm_init_tcp",
-    "wfpt_comm_init_all", "wfpt_wiener_like_allreduce_group", "wfpt_result_poison",
-    "wfpt_wiener_like_nodes_ex", "wfpt_wiener_like_multi_ex", "wfpt_wiener_like_multi_resident_ex",
-    "wfpt_wiener_like_trials", "wfpt_dataset_order", "wfpt_debug_partials", "wfpt_last_path",
-    "wfpt_wiener_like_local", "wfpt_wiener_like_nodes_local", "wfpt_wiener_like_nodes_allreduce",
-    "wfpt_wiener_like_nodes_multi", "wfpt_wiener_like_nodes_multi_ex",
-    "wfpt_rl_dataset_create", "wfpt_rl_dataset_destroy", "wfpt_wiener_like_rlddm",
-    "wfpt_wiener_like_rlddm_ex", "wfpt_wiener_like_rl", "wfpt_wiener_like_rl_ex",
-    "wfpt_wiener_like_multi_rlddm", "wfpt_wiener_like_multi_rlddm_ex",
-    "wfpt_wiener_like_rlddm_nodes", "wfpt_wiener_like_rlddm_nodes_ex",
-    "wfpt_gen_rts_nodes", "wfpt_gen_rts_nodes_ex", "wfpt_profile_stages",
-    "wfpt_gen_rts_drift_nodes", "wfpt_gen_rts_drift_nodes_ex",
-    "wfpt_reg_dataset_create", "wfpt_reg_dataset_destroy", "wfpt_wiener_like_reg",
-    "wfpt_wiener_like_reg_ex", "wfpt_wiener_like_reg_groups", "wfpt_wiener_like_reg_groups_ex",
-    "wfpt_dmat_cdf_rows",
-    "wfpt_rt_stats_rows", "wfpt_rt_stats_rows_ex", "wfpt_gen_rts_nodes_stats",
-    "wfpt_gen_rts_drift_nodes_stats",
-]
+# Every entry point of include/wfpt_amd.h: name -> (restype, argtypes). Each
+# becomes a module attribute below, and EXPORTED is this table's names.
+_LIKE = [_VP, _VP, _PP, _PK, _PD]  # ctx, dataset, params | table, knobs, out
+_MULTI = [_PPD, _PD, _PK, _D, _PD]  # per-trial arrays, scalars, knobs, p_outlier, out
+_RL_HOST = [_VP, _PD, _PI64, _PD, _PI64, _I64, _D]  # ctx, rt, response, feedback, split_by, n, q
+_REG = [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD]  # ctx, ds, terms, n_terms, coef, params, ...
+_GEN_CDF = [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD]
+_GEN_DRIFT = [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64]
+_SIGNATURES = {
+    "wfpt_last_error": (_CP, []),
+    "wfpt_device_count": (_I, [_PI]),
+    "wfpt_open": (_I, [_I, _PVP]),
+    "wfpt_close": (None, [_VP]),
+    "wfpt_synchronize": (_I, [_VP]),
+    "wfpt_shard_range": (None, [_I64, _I, _I, _PI64, _PI64]),
+    # resident data sets and their likelihoods
+    "wfpt_dataset_create": (_I, [_VP, _PD, _I64, _PI32, _I32, _PVP]),
+    "wfpt_dataset_create_ex": (_I, [_VP, _PD, _I64, _PI32, _I32, _I, _PVP]),
+    "wfpt_dataset_destroy": (None, [_VP]),
+    "wfpt_dataset_size": (_I64, [_VP]),
+    "wfpt_dataset_order": (_I, [_VP, _PI64]),
+    "wfpt_wiener_like": (_I, _LIKE),
+    "wfpt_wiener_like_trials": (_I, _LIKE + [_PD]),
+    "wfpt_wiener_like_local": (_I, _LIKE),
+    "wfpt_wiener_like_nodes": (_I, _LIKE),
+    "wfpt_wiener_like_nodes_ex": (_I, _LIKE + [_PD]),
+    "wfpt_wiener_like_nodes_local": (_I, _LIKE),
+    "wfpt_wiener_like_nodes_multi": (_I, [_VP, _VP, _PP, _I32, _PK, _PD]),
+    "wfpt_wiener_like_nodes_multi_ex": (_I, [_VP, _VP, _PP, _I32, _PK, _PD, _PD]),
+    "wfpt_wiener_like_multi_resident": (_I, [_VP, _VP] + _MULTI),
+    "wfpt_wiener_like_multi_resident_ex": (_I, [_VP, _VP] + _MULTI + [_PD]),
+    # host arrays
+    "wfpt_wiener_like_host": (_I, [_VP, _PD, _I64, _PP, _PK, _PD]),
+    "wfpt_pdf_array": (_I, [_VP, _PD, _I64, _PP, _PK, _I, _PD]),
+    "wfpt_full_pdf": (_I, [_VP, _D, _PP, _PK, _PD]),
+    "wfpt_wiener_like_multi": (_I, [_VP, _PD, _I64] + _MULTI),
+    "wfpt_wiener_like_multi_ex": (_I, [_VP, _PD, _I64] + _MULTI + [_PD]),
+    "wfpt_dmat_cdf_array": (_I, [_VP, _PD, _I64, _PP, _D, _PD]),
+    "wfpt_dmat_cdf_rows": (_I, [_VP, _PP, _PD, _PD, _PD, _I64, _I32, _D, _PD, _PD, _PD]),
+    # multi-GPU
+    "wfpt_comm_unique_id": (_I, [_CP]),
+    "wfpt_comm_init": (_I, [_VP, _I, _I, _CP]),
+    "wfpt_comm_exchange_id": (_I, [_I, _I, _CP, _I, _I, _CP]),
+    "wfpt_comm_init_tcp": (_I, [_VP, _I, _I, _CP, _I, _I]),
+    "wfpt_comm_init_all": (_I, [_PVP, _I]),
+    "wfpt_wiener_like_allreduce": (_I, _LIKE),
+    "wfpt_wiener_like_allreduce_group": (_I, [_PVP, _PVP, _I, _PP, _PK, _PD]),
+    "wfpt_wiener_like_nodes_allreduce": (_I, [_VP, _VP, _PP, _I32, _PK, _PD]),
+    "wfpt_result_poison": (_I, [_PD]),
+    "wfpt_decode_result": (_I, [_PD, _PD]),
+    # diagnostics
+    "wfpt_profile_enable": (_I, [_VP, _I]),
+    "wfpt_profile_read": (_I, [_VP, _PD, _PI64, _PI64, _I]),
+    "wfpt_profile_stages": (_I, [_VP, _PD, _I]),
+    "wfpt_profile_lists": (_I, [_VP, _PI64, _I]),
+    "wfpt_debug_waves": (_I, [_VP, _PU64, _I64]),
+    "wfpt_debug_partials": (_I, [_VP, _PD, _PI32, _I64]),
+    "wfpt_last_path": (_I, [_VP, _PI]),
+    # reinforcement-learning family
+    "wfpt_rl_dataset_create": (_I, [_VP, _PD, _PI64, _PD, _PI64, _I64, _PI32, _I32, _PVP]),
+    "wfpt_rl_dataset_destroy": (None, [_VP]),
+    "wfpt_wiener_like_rlddm": (_I, [_VP, _VP, _D, _D, _D, _PP, _PK, _PD]),
+    "wfpt_wiener_like_rlddm_ex": (_I, [_VP, _VP, _D, _D, _D, _PP, _PK, _PD, _PD, _PD]),
+    "wfpt_wiener_like_rl": (_I, [_VP, _VP] + [_D] * 7 + [_PD]),
+    "wfpt_wiener_like_rl_ex": (_I, [_VP, _VP] + [_D] * 7 + [_PD, _PD, _PD]),
+    "wfpt_wiener_like_multi_rlddm": (_I, _RL_HOST + _MULTI),
+    "wfpt_wiener_like_multi_rlddm_ex": (_I, _RL_HOST + _MULTI + [_PD, _PD]),
+    "wfpt_wiener_like_rlddm_nodes": (_I, [_VP, _VP, _PD, _PP, _PK, _PD]),
+    "wfpt_wiener_like_rlddm_nodes_ex": (_I, [_VP, _VP, _PD, _PP, _PK, _PD, _PD, _PD]),
+    # regression likelihoods
+    "wfpt_reg_dataset_create": (_I, [_VP, _PD, _I64, _PD, _I32, _PI32, _I32, _PVP]),
+    "wfpt_reg_dataset_destroy": (None, [_VP]),
+    "wfpt_wiener_like_reg": (_I, _REG),
+    "wfpt_wiener_like_reg_ex": (_I, _REG + [_PD, _PD]),
+    "wfpt_wiener_like_reg_groups": (_I, _REG),
+    "wfpt_wiener_like_reg_groups_ex": (_I, _REG + [_PD, _PD]),
+    # RT samplers and per-row RT statistics
+    "wfpt_gen_rts_nodes": (_I, _GEN_CDF),
+    "wfpt_gen_rts_nodes_ex": (_I, _GEN_CDF + [_PD, _PD, _PI64, _PD, _PD]),
+    "wfpt_gen_rts_nodes_stats": (_I, _GEN_CDF + [_PD, _I32, _PD]),
+    "wfpt_gen_rts_drift_nodes": (_I, _GEN_DRIFT + [_PD, _PI64]),
+    "wfpt_gen_rts_drift_nodes_ex": (_I, _GEN_DRIFT + [_I64, _I32, _PD, _PI64, _PD, _PD, _PD, _PD,
+                                                      _PI64, _PI64]),
+    "wfpt_gen_rts_drift_nodes_stats": (_I, _GEN_DRIFT + [_PD, _PI64, _PD, _I32, _PD]),
+    "wfpt_rt_stats_rows": (_I, [_VP, _PD, _PI64, _I64, _PD, _I32, _PD]),
+    "wfpt_rt_stats_rows_ex": (_I, [_VP, _PD, _PI64, _I64, _PD, _I32, _I32, _PD]),
+}
+# diagnostics only: A/B runs may load an older library build without them
+_OPTIONAL = ("wfpt_profile_lists", "wfpt_debug_waves")
+EXPORTED = list(_SIGNATURES)
+
+
+def _sig(name, res, args):
+    f = getattr(_lib, name, None) if name in _OPTIONAL else getattr(_lib, name)
+    if f is not None:
+        f.restype = res
+        f.argtypes = args
+    return f
+
+
+globals().update({name: _sig(name, *sig) for name, sig in _SIGNATURES.items()})
+
+
+def _raw(name, nargs, i32=()):
+    """The same entry point through a prototype of plain addresses (ints): the
+    per-call paths (one likelihood per MCMC step) skip the per-argument ctypes
+    object conversions (~1 us per call through byref / data_as). The argument
+    positions in `i32` are int32 values, not addresses."""
+    proto = ctypes.CFUNCTYPE(_I, *[_I32 if j in i32 else _VP for j in range(nargs)])
+    return proto(ctypes.cast(getattr(_lib, name), _VP).value)
+
+
+raw_wiener_like = _raw("wfpt_wiener_like", 5)
+raw_wiener_like_nodes = _raw("wfpt_wiener_like_nodes", 5)
+raw_wiener_like_nodes_multi = _raw("wfpt_wiener_like_nodes_multi", 6, i32=(3,))
 
 # error encoding of a result triple (include/wfpt_amd.h: wfpt_decode_result)
 DEPTH_ERROR = 1.0
@@ -333,7 +285,7 @@ class Context:
     def debug_waves(self, n):
         """Per-wave engine records of diagnostic builds (wfpt_debug_waves): (n, 8) uint64."""
         out = np.zeros((n, 8), dtype=np.uint64)
-        check(wfpt_debug_waves(self.handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n))
+        check(wfpt_debug_waves(self.handle, out.ctypes.data_as(_PU64), n))
         return out
 
     def synchronize(self):
@@ -349,8 +301,7 @@ class Context:
         """The first n chunk partials {sum, zero word} of the last summing call."""
         part = np.empty(n, dtype=np.float64)
         zero = np.empty(n, dtype=np.int32)
-        check(wfpt_debug_partials(self.handle, dptr(part),
-                                  zero.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n))
+        check(wfpt_debug_partials(self.handle, dptr(part), zero.ctypes.data_as(_PI32), n))
         return part, zero
 
 

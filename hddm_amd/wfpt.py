@@ -30,6 +30,15 @@ hddm/utils.py:241-265) on the device, and `gen_rts_stats_nodes` does so for
 the draws of either sampler without copying them out. `RegDataset(rt, design)` keeps a
 design matrix resident and forms HDDMRegressor's trial-wise parameters
 link(design . coefficients) on the device (hddm_regression.py:26-36).
+
+Shared pieces, each stated once: the samplers' argument rules (`_sampler_table`,
+`_cdf_prep`, `_drift_prep` / `_drift_seed`, `_check_drawn`, `_check_finished`)
+serve the plain samplers and `gen_rts_stats_nodes` alike; `_multi_args` builds
+the per-trial arguments of the 7- and 8-parameter forms, with `_like_multi` and
+`_like_multi_rlddm` behind every wiener_like_multi[_rlddm] spelling; the three
+resident classes share `_Resident` (close / __del__ / __len__) and `_id_array`;
+the module-level RL functions run a method over a transient `RLDataset`
+(`_on_rl_dataset`).
 """
 import ctypes
 
@@ -37,10 +46,11 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "gen_rts_from_cdf",
-           "gen_rts_from_cdf_nodes", "gen_rts_from_drift_nodes", "gen_rts_from_drift",
-           "rt_stats_rows", "rt_stats_names", "gen_rts_stats_nodes", "Dataset", "prob_ub",
-           "wiener_like_rlddm", "wiener_like_rl", "wiener_like_multi_rlddm", "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_terms",
+__all__ = ["pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "wiener_like_multi_terms",
+           "gen_rts_from_cdf", "gen_rts_from_cdf_nodes", "gen_rts_from_drift_nodes",
+           "gen_rts_from_drift", "rt_stats_rows", "rt_stats_names", "gen_rts_stats_nodes",
+           "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl", "wiener_like_multi_rlddm",
+           "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_terms",
            "wiener_like_rl_terms", "wiener_like_multi_rlddm_terms", "RegDataset"]
 
 
@@ -54,6 +64,15 @@ def _check_x(x, name="x"):
     if x.ndim != 1:
         raise ValueError(f"Buffer has wrong number of dimensions (expected 1, got {x.ndim})")
     return np.ascontiguousarray(x)
+
+
+def _i64ptr(a):
+    return a.ctypes.data_as(_lib._PI64)
+
+
+def _optr(a):
+    """double* of an optional array (None: NULL)."""
+    return _lib.dptr(a) if a is not None else None
 
 
 def pdf_array(x, v, sv, a, z, sz, t, st, err=1e-4, logp=0, n_st=2, n_sz=2, use_adaptive=1,
@@ -98,16 +117,17 @@ def prob_ub(v, a, z):
     return (np.exp(-2 * a * z * v) - 1) / (np.exp(-2 * a * v) - 1)
 
 
-def _multi_args(n, v, sv, a, z, sz, t, st, multi):
+_MULTI_NAMES = ("v", "sv", "a", "z", "sz", "t", "st")
+
+
+def _multi_args(n, names, vals, multi):
     """Per-trial arrays (pointer table, kept alive) and scalars of a
-    wiener_like_multi call (wfpt.pyx:257-260: names in `multi` are indexed per
-    trial, the others are scalars)."""
-    names = ("v", "sv", "a", "z", "sz", "t", "st")
-    vals = (v, sv, a, z, sz, t, st)
+    wiener_like_multi[_rlddm] call (wfpt.pyx:257-260, 296: names in `multi`
+    are indexed per trial, the others are scalars)."""
     multi = set(multi)
     keep = []
-    ptrs = (_lib._PD * 7)()
-    scal = np.zeros(7)
+    ptrs = (_lib._PD * len(names))()
+    scal = np.zeros(len(names))
     for j, (nm, val) in enumerate(zip(names, vals)):
         if nm in multi:
             arr = np.ascontiguousarray(np.asarray(val, dtype=np.float64))
@@ -121,20 +141,35 @@ def _multi_args(n, v, sv, a, z, sz, t, st, multi):
     return ptrs, scal, keep
 
 
+def _like_multi(ds, x, n, vals, err, multi, n_st, n_sz, use_adaptive, simps_err, p_outlier,
+                w_outlier, trials):
+    """wiener_like_multi over the resident Dataset `ds` or, with ds None, the
+    host RTs `x`; trials: (sum, per-trial terms)."""
+    ptrs, scal, keep = _multi_args(n, _MULTI_NAMES, vals, multi)
+    c = (ds.ctx if ds is not None else _lib.context()).handle
+    K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+    out = ctypes.c_double()
+    terms = np.empty(n, dtype=np.float64) if trials else None
+    args = (ptrs, _lib.dptr(scal), ctypes.byref(K), float(p_outlier), ctypes.byref(out))
+    if ds is not None:
+        rc = _lib.wfpt_wiener_like_multi_resident_ex(c, ds.handle, *args,
+                                                     _lib.dptr(terms) if trials else None)
+    elif trials:
+        rc = _lib.wfpt_wiener_like_multi_ex(c, _lib.dptr(x), n, *args, _lib.dptr(terms))
+    else:
+        rc = _lib.wfpt_wiener_like_multi(c, _lib.dptr(x), n, *args)
+    _lib.check(rc)
+    del keep
+    return (out.value, terms) if trials else out.value
+
+
 def wiener_like_multi(x, v, sv, a, z, sz, t, st, err, multi=None, n_st=10, n_sz=10,
                       use_adaptive=1, simps_err=1e-3, p_outlier=0, w_outlier=0):
     x = _check_x(x)
     if multi is None:
         return full_pdf(x, v, sv, a, z, sz, t, st, err)  # wfpt.pyx:255-256 (TypeError for arrays)
-    n = x.shape[0]
-    ptrs, scal, keep = _multi_args(n, v, sv, a, z, sz, t, st, multi)
-    c = _lib.context()
-    K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
-    out = ctypes.c_double()
-    _lib.check(_lib.wfpt_wiener_like_multi(c.handle, _lib.dptr(x), n, ptrs, _lib.dptr(scal),
-                                           ctypes.byref(K), float(p_outlier), ctypes.byref(out)))
-    del keep
-    return out.value
+    return _like_multi(None, x, x.shape[0], (v, sv, a, z, sz, t, st), err, multi, n_st, n_sz,
+                       use_adaptive, simps_err, p_outlier, w_outlier, False)
 
 
 def wiener_like_multi_terms(x, v, sv, a, z, sz, t, st, err, multi, n_st=10, n_sz=10,
@@ -142,17 +177,8 @@ def wiener_like_multi_terms(x, v, sv, a, z, sz, t, st, err, multi, n_st=10, n_sz
     """wiener_like_multi (wfpt.pyx:244-274) returning (sum, per-trial terms):
     terms[i] is trial i's addend log p_i (wfpt.pyx:261-272)."""
     x = _check_x(x)
-    n = x.shape[0]
-    ptrs, scal, keep = _multi_args(n, v, sv, a, z, sz, t, st, multi)
-    c = _lib.context()
-    K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
-    out = ctypes.c_double()
-    terms = np.empty(n, dtype=np.float64)
-    _lib.check(_lib.wfpt_wiener_like_multi_ex(c.handle, _lib.dptr(x), n, ptrs, _lib.dptr(scal),
-                                              ctypes.byref(K), float(p_outlier),
-                                              ctypes.byref(out), _lib.dptr(terms)))
-    del keep
-    return out.value, terms
+    return _like_multi(None, x, x.shape[0], (v, sv, a, z, sz, t, st), err, multi, n_st, n_sz,
+                       use_adaptive, simps_err, p_outlier, w_outlier, True)
 
 
 def gen_rts_from_cdf(v, sv, a, z, sz, t, st, samples=1000, cdf_lb=-6, cdf_ub=6, dt=1e-2):
@@ -179,6 +205,122 @@ def gen_rts_from_cdf(v, sv, a, z, sz, t, st, samples=1000, cdf_lb=-6, cdf_ub=6, 
     return rt + np.sign(rt) * delay
 
 
+# The samplers' argument rules, shared by gen_rts_from_cdf_nodes /
+# gen_rts_from_drift_nodes and the fused gen_rts_stats_nodes: each check, RNG
+# rule and error mapping is stated here and nowhere else.
+
+def _sampler_table(params, samples):
+    """The samplers' (R, 8) table, per-row counts and offsets."""
+    pm = np.asarray(params, dtype=np.float64)
+    if pm.ndim != 2 or pm.shape[1] not in (7, 8) or pm.shape[0] < 1:
+        raise ValueError("params must have shape (R, 7) or (R, 8), R >= 1")
+    R = pm.shape[0]
+    table = np.zeros((R, 8))
+    table[:, :pm.shape[1]] = pm
+    cnt = np.asarray(samples)
+    if cnt.ndim == 0:
+        cnt = np.full(R, int(cnt))
+    if cnt.shape != (R,) or not np.issubdtype(cnt.dtype, np.integer):
+        raise ValueError(f"samples must be an int or {R} ints")
+    cnt = np.ascontiguousarray(cnt, dtype=np.int64)
+    if np.any(cnt < 0):
+        raise ValueError("samples must be non-negative")
+    offsets = np.zeros(R + 1, dtype=np.int64)
+    np.cumsum(cnt, out=offsets[1:])
+    return table, cnt, offsets
+
+
+def _cdf_prep(table, cnt, offsets, cdf_lb, cdf_ub, dt, u, u_delay, seed, max_workspace):
+    """The CDF sampler's checked arguments: (grid, u, u_delay, seed, workspace
+    bytes). Without `u` and `seed` the uniforms are drawn here, from NumPy's
+    global RNG in the reference's order."""
+    R, total = table.shape[0], int(offsets[-1])
+    has_st = table[:, 6] != 0
+    if u is None and u_delay is not None:
+        raise ValueError("u_delay needs u")
+    if u is not None:
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.shape != (total,):
+            raise ValueError(f"u must hold sum(samples) = {total} uniforms")
+        if has_st.any() and u_delay is None:
+            raise ValueError("u_delay is needed: a row has st != 0")
+        if u_delay is not None:
+            u_delay = np.ascontiguousarray(u_delay, dtype=np.float64)
+            if u_delay.shape != (total,):
+                raise ValueError(f"u_delay must hold sum(samples) = {total} uniforms")
+        for nm, arr in (("u", u), ("u_delay", u_delay)):
+            if arr is not None and arr.size and not (arr.min() >= 0 and arr.max() < 1):
+                raise ValueError(f"{nm} must lie in [0, 1)")
+    elif seed is None:
+        # the reference's order of draws from the global RNG (wfpt.pyx:340-345)
+        u = np.empty(total)
+        u_delay = np.zeros(total) if has_st.any() else None
+        for r in range(R):
+            lo, hi = offsets[r], offsets[r + 1]
+            u[lo:hi] = np.random.rand(int(cnt[r]))
+            if has_st[r]:
+                u_delay[lo:hi] = np.random.rand(int(cnt[r]))
+    x = np.arange(cdf_lb, cdf_ub, dt)
+    if x.shape[0] < 2:
+        raise ValueError("the grid np.arange(cdf_lb, cdf_ub, dt) needs at least two points")
+    ws = 0 if max_workspace is None else int(max_workspace)
+    if ws < 0:
+        raise ValueError("max_workspace must be positive")
+    return x, u, u_delay, 0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF, ws
+
+
+def _drift_prep(R, dt, intra_sv, switch, max_t, unfinished):
+    """The drift sampler's checked arguments: (dt, intra_sv, max_steps, switch
+    table or None). The seed is _drift_seed's: the plain sampler checks its own
+    arguments between the two, before anything is taken from the global RNG."""
+    dt, intra_sv = float(dt), float(intra_sv)
+    if not (dt > 0 and np.isfinite(dt)):
+        raise ValueError("dt must be positive")
+    if not (intra_sv > 0 and np.isfinite(intra_sv)):
+        raise ValueError("intra_sv must be positive")
+    if not max_t > 0:
+        raise ValueError("max_t must be positive")
+    max_steps = int(np.ceil(float(max_t) / dt))
+    if not 1 <= max_steps <= 2 ** 31:
+        raise ValueError("ceil(max_t / dt) must lie in [1, 2^31]")
+    if unfinished not in ("raise", "nan"):
+        raise ValueError("unfinished must be 'raise' or 'nan'")
+    sw = None
+    if switch is not None:
+        sw = np.ascontiguousarray(switch, dtype=np.float64)
+        if sw.shape != (R, 3):
+            raise ValueError(f"switch must have shape ({R}, 3): v_switch, V_switch, t_switch")
+        if not np.all(np.round(sw[:, 2] / dt) >= 1):  # generate.py:237-239
+            raise ValueError("t_switch / dt must round to at least one step")
+    return dt, intra_sv, max_steps, sw
+
+
+def _drift_seed(seed):
+    """The drift sampler's 64-bit seed; None takes two 32-bit words from
+    NumPy's global RNG."""
+    if seed is None:
+        lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
+        seed = int(lo) | (int(hi) << 32)
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+_NO_DRAW = {"cdf": b"has no CDF", "drift": b"cannot be simulated"}
+
+
+def _check_drawn(rc, method):
+    """_lib.check for a sampler's status: a parameter row it cannot draw from
+    is a RuntimeError that names the row, not check's NotImplementedError."""
+    if rc == 4 and _NO_DRAW[method] in _lib.wfpt_last_error():
+        raise RuntimeError("wfpt_amd: " + _lib.wfpt_last_error().decode(errors="replace"))
+    _lib.check(rc)
+
+
+def _check_finished(n_unfinished, total, max_steps, max_t, unfinished):
+    if n_unfinished and unfinished == "raise":
+        raise RuntimeError(f"wfpt_amd: {n_unfinished} of {total} draws had not crossed a boundary "
+                           f"after {max_steps} steps (max_t = {max_t})")
+
+
 def gen_rts_from_cdf_nodes(params, samples, cdf_lb=-6, cdf_ub=6, dt=1e-2, u=None, u_delay=None,
                            seed=None, max_workspace=None, return_debug=False):
     """gen_rts_from_cdf (wfpt.pyx:323-354) for R parameter rows in one call:
@@ -203,75 +345,23 @@ def gen_rts_from_cdf_nodes(params, samples, cdf_lb=-6, cdf_ub=6, dt=1e-2, u=None
     (R, len(x) - 1), each draw's grid index `idx` and the uniforms `u`,
     `u_delay` used.
     """
-    pm = np.asarray(params, dtype=np.float64)
-    if pm.ndim != 2 or pm.shape[1] not in (7, 8) or pm.shape[0] < 1:
-        raise ValueError("params must have shape (R, 7) or (R, 8), R >= 1")
-    R = pm.shape[0]
-    table = np.zeros((R, 8))
-    table[:, :pm.shape[1]] = pm
-    cnt = np.asarray(samples)
-    if cnt.ndim == 0:
-        cnt = np.full(R, int(cnt))
-    if cnt.shape != (R,) or not np.issubdtype(cnt.dtype, np.integer):
-        raise ValueError(f"samples must be an int or {R} ints")
-    cnt = np.ascontiguousarray(cnt, dtype=np.int64)
-    if np.any(cnt < 0):
-        raise ValueError("samples must be non-negative")
-    offsets = np.zeros(R + 1, dtype=np.int64)
-    np.cumsum(cnt, out=offsets[1:])
-    total = int(offsets[R])
-    has_st = table[:, 6] != 0
-    if u is None and u_delay is not None:
-        raise ValueError("u_delay needs u")
-    if u is not None:
-        u = np.ascontiguousarray(u, dtype=np.float64)
-        if u.shape != (total,):
-            raise ValueError(f"u must hold sum(samples) = {total} uniforms")
-        if has_st.any():
-            if u_delay is None:
-                raise ValueError("u_delay is needed: a row has st != 0")
-        if u_delay is not None:
-            u_delay = np.ascontiguousarray(u_delay, dtype=np.float64)
-            if u_delay.shape != (total,):
-                raise ValueError(f"u_delay must hold sum(samples) = {total} uniforms")
-        for nm, arr in (("u", u), ("u_delay", u_delay)):
-            if arr is not None and arr.size and not (arr.min() >= 0 and arr.max() < 1):
-                raise ValueError(f"{nm} must lie in [0, 1)")
-    elif seed is None:
-        # the reference's order of draws from the global RNG (wfpt.pyx:340-345)
-        u = np.empty(total)
-        u_delay = np.zeros(total) if has_st.any() else None
-        for r in range(R):
-            lo, hi = offsets[r], offsets[r + 1]
-            u[lo:hi] = np.random.rand(int(cnt[r]))
-            if has_st[r]:
-                u_delay[lo:hi] = np.random.rand(int(cnt[r]))
-    x = np.arange(cdf_lb, cdf_ub, dt)
-    G = x.shape[0]
-    if G < 2:
-        raise ValueError("the grid np.arange(cdf_lb, cdf_ub, dt) needs at least two points")
-    ws = 0 if max_workspace is None else int(max_workspace)
-    if ws < 0:
-        raise ValueError("max_workspace must be positive")
-    c = _lib.context()
+    table, cnt, offsets = _sampler_table(params, samples)
+    x, u, u_delay, seed, ws = _cdf_prep(table, cnt, offsets, cdf_lb, cdf_ub, dt, u, u_delay, seed,
+                                        max_workspace)
+    R, G, total = table.shape[0], x.shape[0], int(offsets[-1])
     out = np.empty(total, dtype=np.float64)
-    seed = 0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
-    pu = _lib.dptr(u) if u is not None else None
-    pd_ = _lib.dptr(u_delay) if u_delay is not None else None
+    head = (_lib.context().handle, _lib.dptr(x), G, table.ctypes.data_as(_lib._PP), R,
+            _i64ptr(cnt), _optr(u), _optr(u_delay), seed, ws, _lib.dptr(out))
     if return_debug:
         dbg = {"x": x, "pdf": np.empty((R, G - 1)), "cdf": np.empty((R, G - 1)),
                "idx": np.empty(total, dtype=np.int64), "u": np.empty(total),
                "u_delay": np.empty(total)}
-        rc = _lib.wfpt_gen_rts_nodes_ex(
-            c.handle, _lib.dptr(x), G, table.ctypes.data_as(_lib._PP), R, _i64ptr(cnt), pu, pd_,
-            seed, ws, _lib.dptr(out), _lib.dptr(dbg["pdf"]), _lib.dptr(dbg["cdf"]),
-            _i64ptr(dbg["idx"]), _lib.dptr(dbg["u"]), _lib.dptr(dbg["u_delay"]))
+        rc = _lib.wfpt_gen_rts_nodes_ex(*head, _lib.dptr(dbg["pdf"]), _lib.dptr(dbg["cdf"]),
+                                        _i64ptr(dbg["idx"]), _lib.dptr(dbg["u"]),
+                                        _lib.dptr(dbg["u_delay"]))
     else:
-        rc = _lib.wfpt_gen_rts_nodes(c.handle, _lib.dptr(x), G, table.ctypes.data_as(_lib._PP), R,
-                                     _i64ptr(cnt), pu, pd_, seed, ws, _lib.dptr(out))
-    if rc == 4 and b"has no CDF" in _lib.wfpt_last_error():
-        raise RuntimeError("wfpt_amd: " + _lib.wfpt_last_error().decode(errors="replace"))
-    _lib.check(rc)
+        rc = _lib.wfpt_gen_rts_nodes(*head)
+    _check_drawn(rc, "cdf")
     return (out, offsets, dbg) if return_debug else (out, offsets)
 
 
@@ -304,76 +394,33 @@ def gen_rts_from_drift_nodes(params, samples, dt=1e-4, intra_sv=1., seed=None, s
     measurement knob that changes no value); with return_debug the dict then
     also holds `wave_steps`, the steps each wave's loop ran.
     """
-    pm = np.asarray(params, dtype=np.float64)
-    if pm.ndim != 2 or pm.shape[1] not in (7, 8) or pm.shape[0] < 1:
-        raise ValueError("params must have shape (R, 7) or (R, 8), R >= 1")
-    R = pm.shape[0]
-    table = np.zeros((R, 8))
-    table[:, :pm.shape[1]] = pm
-    cnt = np.asarray(samples)
-    if cnt.ndim == 0:
-        cnt = np.full(R, int(cnt))
-    if cnt.shape != (R,) or not np.issubdtype(cnt.dtype, np.integer):
-        raise ValueError(f"samples must be an int or {R} ints")
-    cnt = np.ascontiguousarray(cnt, dtype=np.int64)
-    if np.any(cnt < 0):
-        raise ValueError("samples must be non-negative")
-    dt, intra_sv = float(dt), float(intra_sv)
-    if not (dt > 0 and np.isfinite(dt)):
-        raise ValueError("dt must be positive")
-    if not (intra_sv > 0 and np.isfinite(intra_sv)):
-        raise ValueError("intra_sv must be positive")
-    if not max_t > 0:
-        raise ValueError("max_t must be positive")
-    max_steps = int(np.ceil(float(max_t) / dt))
-    if not 1 <= max_steps <= 2 ** 31:
-        raise ValueError("ceil(max_t / dt) must lie in [1, 2^31]")
-    if unfinished not in ("raise", "nan"):
-        raise ValueError("unfinished must be 'raise' or 'nan'")
-    sw = None
-    if switch is not None:
-        sw = np.ascontiguousarray(switch, dtype=np.float64)
-        if sw.shape != (R, 3):
-            raise ValueError(f"switch must have shape ({R}, 3): v_switch, V_switch, t_switch")
-        if not np.all(np.round(sw[:, 2] / dt) >= 1):  # generate.py:237-239
-            raise ValueError("t_switch / dt must round to at least one step")
+    table, cnt, offsets = _sampler_table(params, samples)
+    R, total = table.shape[0], int(offsets[-1])
+    dt, intra_sv, max_steps, sw = _drift_prep(R, dt, intra_sv, switch, max_t, unfinished)
     row0 = int(row0)
     if not 0 <= row0 < 2 ** 31:
         raise ValueError("row0 must lie in [0, 2^31)")
     wd = 0 if wave_draws is None else int(wave_draws)
     if wd < 0 or wd % 64:
         raise ValueError("wave_draws must be a positive multiple of 64")
-    offsets = np.zeros(R + 1, dtype=np.int64)
-    np.cumsum(cnt, out=offsets[1:])
-    total = int(offsets[R])
-    if seed is None:
-        lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-        seed = int(lo) | (int(hi) << 32)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    c = _lib.context()
+    seed = _drift_seed(seed)
     out = np.empty(total, dtype=np.float64)
     nun = ctypes.c_int64()
-    psw = _lib.dptr(sw) if sw is not None else None
+    head = (_lib.context().handle, table.ctypes.data_as(_lib._PP), R, _optr(sw), _i64ptr(cnt), dt,
+            intra_sv, max_steps, seed)
     if return_debug or row0 or wd:
         dbg = {k: np.empty(total) for k in ("y0", "delay", "drift", "drift_switch")}
         dbg["n_steps"] = np.empty(total, dtype=np.int64)
         if wd:
             dbg["wave_steps"] = np.empty(-(-total // wd), dtype=np.int64)
         rc = _lib.wfpt_gen_rts_drift_nodes_ex(
-            c.handle, table.ctypes.data_as(_lib._PP), R, psw, _i64ptr(cnt), dt, intra_sv,
-            max_steps, seed, row0, wd, _lib.dptr(out), ctypes.byref(nun), _lib.dptr(dbg["y0"]),
+            *head, row0, wd, _lib.dptr(out), ctypes.byref(nun), _lib.dptr(dbg["y0"]),
             _lib.dptr(dbg["delay"]), _lib.dptr(dbg["drift"]), _lib.dptr(dbg["drift_switch"]),
             _i64ptr(dbg["n_steps"]), _i64ptr(dbg["wave_steps"]) if wd else None)
     else:
-        rc = _lib.wfpt_gen_rts_drift_nodes(c.handle, table.ctypes.data_as(_lib._PP), R, psw,
-                                           _i64ptr(cnt), dt, intra_sv, max_steps, seed,
-                                           _lib.dptr(out), ctypes.byref(nun))
-    if rc == 4 and b"cannot be simulated" in _lib.wfpt_last_error():
-        raise RuntimeError("wfpt_amd: " + _lib.wfpt_last_error().decode(errors="replace"))
-    _lib.check(rc)
-    if nun.value and unfinished == "raise":
-        raise RuntimeError(f"wfpt_amd: {nun.value} of {total} draws had not crossed a boundary "
-                           f"after {max_steps} steps (max_t = {max_t})")
+        rc = _lib.wfpt_gen_rts_drift_nodes(*head, _lib.dptr(out), ctypes.byref(nun))
+    _check_drawn(rc, "drift")
+    _check_finished(nun.value, total, max_steps, max_t, unfinished)
     return (out, offsets, dbg) if return_debug else (out, offsets)
 
 
@@ -446,110 +493,29 @@ def rt_stats_rows(rts, offsets, quantiles=PPC_QUANTILES, tier=0):
     return out
 
 
-def _sampler_table(params, samples):
-    """The samplers' (R, 8) table, per-row counts and offsets."""
-    pm = np.asarray(params, dtype=np.float64)
-    if pm.ndim != 2 or pm.shape[1] not in (7, 8) or pm.shape[0] < 1:
-        raise ValueError("params must have shape (R, 7) or (R, 8), R >= 1")
-    R = pm.shape[0]
-    table = np.zeros((R, 8))
-    table[:, :pm.shape[1]] = pm
-    cnt = np.asarray(samples)
-    if cnt.ndim == 0:
-        cnt = np.full(R, int(cnt))
-    if cnt.shape != (R,) or not np.issubdtype(cnt.dtype, np.integer):
-        raise ValueError(f"samples must be an int or {R} ints")
-    cnt = np.ascontiguousarray(cnt, dtype=np.int64)
-    if np.any(cnt < 0):
-        raise ValueError("samples must be non-negative")
-    offsets = np.zeros(R + 1, dtype=np.int64)
-    np.cumsum(cnt, out=offsets[1:])
-    return table, cnt, offsets
-
-
-def _stats_from_cdf(table, cnt, offsets, q, out, stats, cdf_lb=-6, cdf_ub=6, dt=1e-2, u=None,
-                    u_delay=None, seed=None, max_workspace=None):
-    R, total = table.shape[0], int(offsets[-1])
-    has_st = table[:, 6] != 0
-    if u is None and u_delay is not None:
-        raise ValueError("u_delay needs u")
-    if u is not None:
-        u = np.ascontiguousarray(u, dtype=np.float64)
-        if u.shape != (total,):
-            raise ValueError(f"u must hold sum(samples) = {total} uniforms")
-        if has_st.any() and u_delay is None:
-            raise ValueError("u_delay is needed: a row has st != 0")
-        if u_delay is not None:
-            u_delay = np.ascontiguousarray(u_delay, dtype=np.float64)
-            if u_delay.shape != (total,):
-                raise ValueError(f"u_delay must hold sum(samples) = {total} uniforms")
-        for nm, arr in (("u", u), ("u_delay", u_delay)):
-            if arr is not None and arr.size and not (arr.min() >= 0 and arr.max() < 1):
-                raise ValueError(f"{nm} must lie in [0, 1)")
-    elif seed is None:
-        # the reference's order of draws from the global RNG (wfpt.pyx:340-345)
-        u = np.empty(total)
-        u_delay = np.zeros(total) if has_st.any() else None
-        for r in range(R):
-            lo, hi = offsets[r], offsets[r + 1]
-            u[lo:hi] = np.random.rand(int(cnt[r]))
-            if has_st[r]:
-                u_delay[lo:hi] = np.random.rand(int(cnt[r]))
-    x = np.arange(cdf_lb, cdf_ub, dt)
-    if x.shape[0] < 2:
-        raise ValueError("the grid np.arange(cdf_lb, cdf_ub, dt) needs at least two points")
-    ws = 0 if max_workspace is None else int(max_workspace)
-    if ws < 0:
-        raise ValueError("max_workspace must be positive")
-    seed = 0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+def _cdf_stats(table, cnt, offsets, q, out, stats, seed=None, cdf_lb=-6, cdf_ub=6, dt=1e-2, u=None,
+               u_delay=None, max_workspace=None):
+    x, u, u_delay, seed, ws = _cdf_prep(table, cnt, offsets, cdf_lb, cdf_ub, dt, u, u_delay, seed,
+                                        max_workspace)
     rc = _lib.wfpt_gen_rts_nodes_stats(
-        _lib.context().handle, _lib.dptr(x), x.shape[0], table.ctypes.data_as(_lib._PP), R,
-        _i64ptr(cnt), _lib.dptr(u) if u is not None else None,
-        _lib.dptr(u_delay) if u_delay is not None else None, seed, ws,
-        _lib.dptr(out) if out is not None else None, _lib.dptr(q), q.size, _lib.dptr(stats))
-    if rc == 4 and b"has no CDF" in _lib.wfpt_last_error():
-        raise RuntimeError("wfpt_amd: " + _lib.wfpt_last_error().decode(errors="replace"))
-    _lib.check(rc)
+        _lib.context().handle, _lib.dptr(x), x.shape[0], table.ctypes.data_as(_lib._PP),
+        table.shape[0], _i64ptr(cnt), _optr(u), _optr(u_delay), seed, ws, _optr(out), _lib.dptr(q),
+        q.size, _lib.dptr(stats))
+    _check_drawn(rc, "cdf")
 
 
-def _stats_from_drift(table, cnt, offsets, q, out, stats, dt=1e-4, intra_sv=1., seed=None,
-                      switch=None, max_t=20., unfinished="raise"):
-    R, total = table.shape[0], int(offsets[-1])
-    dt, intra_sv = float(dt), float(intra_sv)
-    if not (dt > 0 and np.isfinite(dt)):
-        raise ValueError("dt must be positive")
-    if not (intra_sv > 0 and np.isfinite(intra_sv)):
-        raise ValueError("intra_sv must be positive")
-    if not max_t > 0:
-        raise ValueError("max_t must be positive")
-    max_steps = int(np.ceil(float(max_t) / dt))
-    if not 1 <= max_steps <= 2 ** 31:
-        raise ValueError("ceil(max_t / dt) must lie in [1, 2^31]")
-    if unfinished not in ("raise", "nan"):
-        raise ValueError("unfinished must be 'raise' or 'nan'")
-    sw = None
-    if switch is not None:
-        sw = np.ascontiguousarray(switch, dtype=np.float64)
-        if sw.shape != (R, 3):
-            raise ValueError(f"switch must have shape ({R}, 3): v_switch, V_switch, t_switch")
-        if not np.all(np.round(sw[:, 2] / dt) >= 1):  # generate.py:237-239
-            raise ValueError("t_switch / dt must round to at least one step")
-    if seed is None:
-        lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-        seed = int(lo) | (int(hi) << 32)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+def _drift_stats(table, cnt, offsets, q, out, stats, seed=None, dt=1e-4, intra_sv=1., switch=None,
+                 max_t=20., unfinished="raise"):
+    R = table.shape[0]
+    dt, intra_sv, max_steps, sw = _drift_prep(R, dt, intra_sv, switch, max_t, unfinished)
+    seed = _drift_seed(seed)
     nun = ctypes.c_int64()
     rc = _lib.wfpt_gen_rts_drift_nodes_stats(
-        _lib.context().handle, table.ctypes.data_as(_lib._PP), R,
-        _lib.dptr(sw) if sw is not None else None, _i64ptr(cnt), dt, intra_sv, max_steps, seed,
-        _lib.dptr(out) if out is not None else None, ctypes.byref(nun), _lib.dptr(q), q.size,
+        _lib.context().handle, table.ctypes.data_as(_lib._PP), R, _optr(sw), _i64ptr(cnt), dt,
+        intra_sv, max_steps, seed, _optr(out), ctypes.byref(nun), _lib.dptr(q), q.size,
         _lib.dptr(stats))
-    if rc == 4 and b"cannot be simulated" in _lib.wfpt_last_error():
-        raise RuntimeError("wfpt_amd: " + _lib.wfpt_last_error().decode(errors="replace"))
-    _lib.check(rc)
-    if nun.value and unfinished == "raise":
-        raise RuntimeError(f"wfpt_amd: {nun.value} of {total} draws had not crossed a boundary "
-                           f"after {max_steps} steps (max_t = {max_t})")
+    _check_drawn(rc, "drift")
+    _check_finished(nun.value, int(offsets[-1]), max_steps, max_t, unfinished)
 
 
 def gen_rts_stats_nodes(params, samples, method="cdf", quantiles=PPC_QUANTILES, seed=None,
@@ -572,42 +538,18 @@ def gen_rts_stats_nodes(params, samples, method="cdf", quantiles=PPC_QUANTILES, 
     table, cnt, offsets = _sampler_table(params, samples)
     stats = np.empty((table.shape[0], 8 + 2 * q.size))
     out = np.empty(int(offsets[-1])) if return_draws else None
-    run = _stats_from_cdf if method == "cdf" else _stats_from_drift
+    run = _cdf_stats if method == "cdf" else _drift_stats
     run(table, cnt, offsets, q, out, stats, seed=seed, **sampler_kw)
     return (stats, offsets, out) if return_draws else (stats, offsets)
 
 
-class Dataset:
-    """RTs resident in HBM for repeated likelihood calls (MCMC: data fixed,
-    parameters change per proposal). Optional `node_id` groups trials into
-    `n_nodes` likelihood nodes scored together by `wiener_like_nodes`."""
-
-    def __init__(self, rt, node_id=None, n_nodes=None, device=None, ctx=None, input_order=False):
-        rt = np.ascontiguousarray(np.asarray(rt, dtype=np.float64).ravel())
-        self.ctx = ctx if ctx is not None else _lib.context(device)
-        self.n = rt.shape[0]
-        self.input_order = bool(input_order)
-        flags = _lib.WFPT_DS_INPUT_ORDER if input_order else 0
-        h = _lib._VP()
-        if node_id is not None:
-            node = np.ascontiguousarray(np.asarray(node_id, dtype=np.int32).ravel())
-            if node.shape != rt.shape:
-                raise ValueError("node_id must have one entry per trial")
-            self.n_nodes = int(n_nodes if n_nodes is not None else (node.max() + 1 if node.size
-                                                                    else 0))
-            _lib.check(_lib.wfpt_dataset_create_ex(
-                self.ctx.handle, _lib.dptr(rt), self.n,
-                node.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.n_nodes, flags,
-                ctypes.byref(h)))
-        else:
-            self.n_nodes = 0
-            _lib.check(_lib.wfpt_dataset_create_ex(self.ctx.handle, _lib.dptr(rt), self.n, None,
-                                                   0, flags, ctypes.byref(h)))
-        self.handle = h
+class _Resident:
+    """Data resident in HBM behind `handle`: n trials, freed by the class's
+    `_destroy` entry point."""
 
     def close(self):
         if getattr(self, "handle", None):
-            _lib.wfpt_dataset_destroy(self.handle)
+            self._destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -618,6 +560,37 @@ class Dataset:
 
     def __len__(self):
         return self.n
+
+
+def _id_array(ids, count):
+    """The optional per-trial ids (node_id, group_id) of a resident data set:
+    (int32 array, `count` or one more than the largest id, int32 pointer)."""
+    ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).ravel())
+    count = int(count if count is not None else (ids.max() + 1 if ids.size else 0))
+    return ids, count, ids.ctypes.data_as(_lib._PI32)
+
+
+class Dataset(_Resident):
+    """RTs resident in HBM for repeated likelihood calls (MCMC: data fixed,
+    parameters change per proposal). Optional `node_id` groups trials into
+    `n_nodes` likelihood nodes scored together by `wiener_like_nodes`."""
+    _destroy = staticmethod(_lib.wfpt_dataset_destroy)
+
+    def __init__(self, rt, node_id=None, n_nodes=None, device=None, ctx=None, input_order=False):
+        rt = np.ascontiguousarray(np.asarray(rt, dtype=np.float64).ravel())
+        self.ctx = ctx if ctx is not None else _lib.context(device)
+        self.n = rt.shape[0]
+        self.input_order = bool(input_order)
+        flags = _lib.WFPT_DS_INPUT_ORDER if input_order else 0
+        node, self.n_nodes, nptr = None, 0, None
+        if node_id is not None:
+            node, self.n_nodes, nptr = _id_array(node_id, n_nodes)
+            if node.shape != rt.shape:
+                raise ValueError("node_id must have one entry per trial")
+        h = _lib._VP()
+        _lib.check(_lib.wfpt_dataset_create_ex(self.ctx.handle, _lib.dptr(rt), self.n, nptr,
+                                               self.n_nodes, flags, ctypes.byref(h)))
+        self.handle = h
 
     def _knobs(self, err, n_st, n_sz, use_adaptive, simps_err, w_outlier):
         """The knobs struct, rebuilt only when the knobs change (they are fixed
@@ -671,8 +644,7 @@ class Dataset:
         """order()[i] = the caller's index of stored trial i (chunk c holds
         stored trials 64c .. 64c + 63)."""
         perm = np.empty(self.n, dtype=np.int64)
-        _lib.check(_lib.wfpt_dataset_order(self.handle,
-                                           perm.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        _lib.check(_lib.wfpt_dataset_order(self.handle, _i64ptr(perm)))
         return perm
 
     def local_triple(self, v, sv, a, z, sz, t, st, err, n_st=10, n_sz=10, use_adaptive=1,
@@ -703,15 +675,8 @@ class Dataset:
         """wiener_like_multi (wfpt.pyx:244-274) over this resident dataset
         (created with input_order=True): only the per-trial parameter arrays
         go to the device per call. trials=True: (sum, per-trial terms)."""
-        ptrs, scal, keep = _multi_args(self.n, v, sv, a, z, sz, t, st, multi)
-        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
-        out = ctypes.c_double()
-        terms = np.empty(self.n, dtype=np.float64) if trials else None
-        _lib.check(_lib.wfpt_wiener_like_multi_resident_ex(
-            self.ctx.handle, self.handle, ptrs, _lib.dptr(scal), ctypes.byref(K),
-            float(p_outlier), ctypes.byref(out), _lib.dptr(terms) if trials else None))
-        del keep
-        return (out.value, terms) if trials else out.value
+        return _like_multi(self, None, self.n, (v, sv, a, z, sz, t, st), err, multi, n_st, n_sz,
+                           use_adaptive, simps_err, p_outlier, w_outlier, trials)
 
     def _node_table(self, params):
         """The (n_nodes, 8) parameter table as a wfpt_params pointer, zero-copy
@@ -782,6 +747,8 @@ class Dataset:
         if not c or not h:  # closed: the C ABI's own argument error
             _lib.check(_lib.wfpt_wiener_like_nodes_multi(c, h, tb.ctypes.data_as(_lib._PP), T,
                                                          ctypes.byref(K), _lib.dptr(out)))
+            return out
+        # the per-step MCMC call: plain addresses through the raw prototype
         rc = _lib.raw_wiener_like_nodes_multi(c.value, h.value, tb.ctypes.data, T, kaddr,
                                               out.ctypes.data)
         if rc:
@@ -794,34 +761,28 @@ class Dataset:
         Returns the per-node summed log-likelihoods (float64[n_nodes]);
         trials=True: (per-node sums, per-trial log terms in the order the
         trials were given to the Dataset)."""
-        if not trials:
-            # the per-step MCMC call: plain addresses through the raw prototype
-            pm = np.ascontiguousarray(params, dtype=np.float64)
-            if self.n_nodes == 0:
-                raise ValueError("dataset was created without node ids")
-            if pm.shape != (self.n_nodes, 8):
-                raise ValueError(f"params must have shape ({self.n_nodes}, 8)")
-            K, kaddr = self._knobs_addr(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
-            out = np.empty(self.n_nodes, dtype=np.float64)
-            c, h = self.ctx.handle, self.handle
-            if c and h:
-                rc = _lib.raw_wiener_like_nodes(c.value, h.value, pm.ctypes.data, kaddr,
-                                                out.ctypes.data)
-                if rc:
-                    _lib.check(rc)
-                return out
-        table, keep = self._node_table(params)
-        K = self._knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        pm = np.ascontiguousarray(params, dtype=np.float64)
+        if self.n_nodes == 0:
+            raise ValueError("dataset was created without node ids")
+        if pm.shape != (self.n_nodes, 8):
+            raise ValueError(f"params must have shape ({self.n_nodes}, 8)")
+        K, kaddr = self._knobs_addr(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
         out = np.empty(self.n_nodes, dtype=np.float64)
+        c, h = self.ctx.handle, self.handle
         if trials:
             terms = np.empty(self.n, dtype=np.float64)
-            _lib.check(_lib.wfpt_wiener_like_nodes_ex(self.ctx.handle, self.handle, table,
+            _lib.check(_lib.wfpt_wiener_like_nodes_ex(c, h, pm.ctypes.data_as(_lib._PP),
                                                       ctypes.byref(K), _lib.dptr(out),
                                                       _lib.dptr(terms)))
             return out, terms
-        _lib.check(_lib.wfpt_wiener_like_nodes(self.ctx.handle, self.handle, table,
-                                               ctypes.byref(K), _lib.dptr(out)))
-        del keep
+        if not c or not h:  # closed: the C ABI's own argument error
+            _lib.check(_lib.wfpt_wiener_like_nodes(c, h, pm.ctypes.data_as(_lib._PP),
+                                                   ctypes.byref(K), _lib.dptr(out)))
+            return out
+        # the per-step MCMC call: plain addresses through the raw prototype
+        rc = _lib.raw_wiener_like_nodes(c.value, h.value, pm.ctypes.data, kaddr, out.ctypes.data)
+        if rc:
+            _lib.check(rc)
         return out
 
 
@@ -840,45 +801,51 @@ def _check_long(a, name):
     return np.ascontiguousarray(a)
 
 
-def _i64ptr(a):
-    return a.ctypes.data_as(_lib._PI64)
-
-
 def _same_length(n, **arrays):
     for nm, arr in arrays.items():
         if arr.shape[0] != n:
             raise ValueError(f"{nm} must have one entry per trial ({n}), got {arr.shape[0]}")
 
 
-def _multi_rl_args(n, v, sv, a, z, sz, t, st, alpha, multi):
-    """_multi_args with the eighth parameter of wiener_like_multi_rlddm, alpha
-    (wfpt.pyx:296)."""
-    names = ("v", "sv", "a", "z", "sz", "t", "st", "alpha")
-    vals = (v, sv, a, z, sz, t, st, alpha)
-    multi = set(multi)
-    keep = []
-    ptrs = (_lib._PD * 8)()
-    scal = np.zeros(8)
-    for j, (nm, val) in enumerate(zip(names, vals)):
-        if nm in multi:
-            arr = np.ascontiguousarray(np.asarray(val, dtype=np.float64))
-            if arr.shape != (n,):
-                raise ValueError(f"parameter {nm} must have one value per trial")
-            keep.append(arr)
-            ptrs[j] = _lib.dptr(arr)
-        else:
-            ptrs[j] = _lib._PD()
-            scal[j] = float(val)
-    return ptrs, scal, keep
+def _rl_outputs(n, terms):
+    """The optional per-trial terms and drifts of an RL call, and their pointers."""
+    if not terms:
+        return None, None, None, None
+    tr = np.empty(n, dtype=np.float64)
+    dr = np.empty(n, dtype=np.float64)
+    return tr, dr, _lib.dptr(tr), _lib.dptr(dr)
 
 
-class RLDataset:
+def _like_multi_rlddm(ctx, rt, response, feedback, split_by, q, vals, err, multi, n_st, n_sz,
+                      use_adaptive, simps_err, p_outlier, w_outlier, terms):
+    """wiener_like_multi_rlddm (wfpt.pyx:277-320) from host arrays, on `ctx`
+    or, with ctx None, the process-wide context; vals: v, sv, a, z, sz, t, st,
+    alpha. terms: (sum, per-trial terms, per-trial drifts)."""
+    if multi is None:
+        return full_pdf(rt, *vals[:7], err)  # wfpt.pyx:293-294 (TypeError for arrays)
+    n = rt.shape[0]
+    _same_length(n, response=response, feedback=feedback, split_by=split_by)
+    ptrs, scal, keep = _multi_args(n, _MULTI_NAMES + ("alpha",), vals, multi)  # wfpt.pyx:296
+    c = ctx if ctx is not None else _lib.context()
+    K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+    out = ctypes.c_double()
+    tr, dr, ptr, pdr = _rl_outputs(n, terms)
+    _lib.check(_lib.wfpt_wiener_like_multi_rlddm_ex(
+        c.handle, _lib.dptr(rt), _i64ptr(response), _lib.dptr(feedback), _i64ptr(split_by), n,
+        float(q), ptrs, _lib.dptr(scal), ctypes.byref(K), float(p_outlier), ctypes.byref(out),
+        ptr, pdr))
+    del keep
+    return (out.value, tr, dr) if terms else out.value
+
+
+class RLDataset(_Resident):
     """The fixed inputs of the RL likelihoods (RT, response, feedback,
     condition) resident in HBM: per call only the scalars go to the device.
     `rt` may be None for the choice-only model (wiener_like_rl). Optional
     `node_id` groups trials into `n_nodes` likelihood nodes scored together by
     `wiener_like_rlddm_nodes`. |rt| == 999 is rejected (ValueError): the RL
     likelihoods have no missing-response code."""
+    _destroy = staticmethod(_lib.wfpt_rl_dataset_destroy)
 
     def __init__(self, rt, response, feedback, split_by, node_id=None, n_nodes=None, device=None,
                  ctx=None):
@@ -893,40 +860,15 @@ class RLDataset:
         self.ctx = ctx if ctx is not None else _lib.context(device)
         self.n = n
         self._host = (rt, response, feedback, split_by)
-        node = nptr = None
-        self.n_nodes = 0
+        node, self.n_nodes, nptr = None, 0, None
         if node_id is not None:
-            node = np.ascontiguousarray(np.asarray(node_id, dtype=np.int32).ravel())
+            node, self.n_nodes, nptr = _id_array(node_id, n_nodes)
             _same_length(n, node_id=node)
-            self.n_nodes = int(n_nodes if n_nodes is not None else (node.max() + 1 if node.size
-                                                                    else 0))
-            nptr = node.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
         h = _lib._VP()
         _lib.check(_lib.wfpt_rl_dataset_create(
-            self.ctx.handle, _lib.dptr(rt) if rt is not None else None, _i64ptr(response),
-            _lib.dptr(feedback), _i64ptr(split_by), n, nptr, self.n_nodes, ctypes.byref(h)))
+            self.ctx.handle, _optr(rt), _i64ptr(response), _lib.dptr(feedback), _i64ptr(split_by),
+            n, nptr, self.n_nodes, ctypes.byref(h)))
         self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.wfpt_rl_dataset_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __len__(self):
-        return self.n
-
-    def _outputs(self, terms):
-        if not terms:
-            return None, None, None, None
-        tr = np.empty(self.n, dtype=np.float64)
-        dr = np.empty(self.n, dtype=np.float64)
-        return tr, dr, _lib.dptr(tr), _lib.dptr(dr)
 
     def wiener_like_rlddm(self, q, alpha, pos_alpha, v, sv, a, z, sz, t, st, err, n_st=10,
                           n_sz=10, use_adaptive=1, simps_err=1e-8, p_outlier=0, w_outlier=0,
@@ -936,7 +878,7 @@ class RLDataset:
         P = _lib.make_params(v, sv, a, z, sz, t, st, p_outlier)
         K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
         out = ctypes.c_double()
-        tr, dr, ptr, pdr = self._outputs(terms)
+        tr, dr, ptr, pdr = _rl_outputs(self.n, terms)
         _lib.check(_lib.wfpt_wiener_like_rlddm_ex(
             self.ctx.handle, self.handle, float(q), float(alpha), float(pos_alpha),
             ctypes.byref(P), ctypes.byref(K), ctypes.byref(out), ptr, pdr))
@@ -947,7 +889,7 @@ class RLDataset:
         """wiener_like_rl (wfpt.pyx:157-241): err, n_st, n_sz, use_adaptive and
         simps_err are accepted and ignored, as in the reference."""
         out = ctypes.c_double()
-        tr, dr, ptr, pdr = self._outputs(terms)
+        tr, dr, ptr, pdr = _rl_outputs(self.n, terms)
         _lib.check(_lib.wfpt_wiener_like_rl_ex(
             self.ctx.handle, self.handle, float(q), float(alpha), float(pos_alpha), float(v),
             float(z), float(p_outlier), float(w_outlier), ctypes.byref(out), ptr, pdr))
@@ -962,18 +904,9 @@ class RLDataset:
         rt, response, feedback, split_by = self._host
         if rt is None:
             raise ValueError("wiener_like_multi_rlddm needs RTs")
-        if multi is None:
-            return full_pdf(rt, v, sv, a, z, sz, t, st, err)  # wfpt.pyx:293-294
-        ptrs, scal, keep = _multi_rl_args(self.n, v, sv, a, z, sz, t, st, alpha, multi)
-        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
-        out = ctypes.c_double()
-        tr, dr, ptr, pdr = self._outputs(terms)
-        _lib.check(_lib.wfpt_wiener_like_multi_rlddm_ex(
-            self.ctx.handle, _lib.dptr(rt), _i64ptr(response), _lib.dptr(feedback),
-            _i64ptr(split_by), self.n, float(q), ptrs, _lib.dptr(scal), ctypes.byref(K),
-            float(p_outlier), ctypes.byref(out), ptr, pdr))
-        del keep
-        return (out.value, tr, dr) if terms else out.value
+        return _like_multi_rlddm(self.ctx, rt, response, feedback, split_by, q,
+                                 (v, sv, a, z, sz, t, st, alpha), err, multi, n_st, n_sz,
+                                 use_adaptive, simps_err, p_outlier, w_outlier, terms)
 
     def wiener_like_rlddm_nodes(self, rl_rows, params, err=1e-4, n_st=2, n_sz=2, use_adaptive=1,
                                 simps_err=1e-3, w_outlier=0.1, terms=False):
@@ -991,7 +924,7 @@ class RLDataset:
             raise ValueError(f"params must have shape ({self.n_nodes}, 8)")
         K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
         out = np.empty(self.n_nodes, dtype=np.float64)
-        tr, dr, ptr, pdr = self._outputs(terms)
+        tr, dr, ptr, pdr = _rl_outputs(self.n, terms)
         _lib.check(_lib.wfpt_wiener_like_rlddm_nodes_ex(
             self.ctx.handle, self.handle, _lib.dptr(rr), pm.ctypes.data_as(_lib._PP),
             ctypes.byref(K), _lib.dptr(out), ptr, pdr))
@@ -1034,7 +967,7 @@ def _reg_terms(model, n_cols):
     return arr, len(model)
 
 
-class RegDataset:
+class RegDataset(_Resident):
     """The fixed inputs of a regression likelihood (signed RTs and the design
     matrix) resident in HBM: per call only the coefficients go to the device,
     and the trial-wise parameters link(design . coefficients) are formed there.
@@ -1042,6 +975,7 @@ class RegDataset:
     trials into `n_groups` groups (subjects) scored together by
     `wiener_like_reg_groups`. |rt| == 999 is a missing response, as in
     wiener_like_multi (wfpt.pyx:261-270)."""
+    _destroy = staticmethod(_lib.wfpt_reg_dataset_destroy)
 
     def __init__(self, rt, design, group_id=None, n_groups=None, device=None, ctx=None):
         rt = np.ascontiguousarray(np.asarray(rt, dtype=np.float64).ravel())
@@ -1050,18 +984,14 @@ class RegDataset:
         X = np.ascontiguousarray(np.asarray(design, dtype=np.float64))
         if X.ndim != 2 or X.shape[0] != n or X.shape[1] < 1:
             raise ValueError(f"design must have shape ({n}, C) with C >= 1, got {X.shape}")
-        node = nptr = None
-        self.n_groups = 1
+        node, self.n_groups, nptr = None, 1, None
         if group_id is not None:
-            node = np.ascontiguousarray(np.asarray(group_id, dtype=np.int32).ravel())
+            node, self.n_groups, nptr = _id_array(group_id, n_groups)
             _same_length(n, group_id=node)
-            self.n_groups = int(n_groups if n_groups is not None else (node.max() + 1 if node.size
-                                                                       else 0))
             if self.n_groups < 1:
                 raise ValueError("group ids need n_groups >= 1")
             if node.size and (node.min() < 0 or node.max() >= self.n_groups):
                 raise ValueError(f"group ids must lie in [0, {self.n_groups})")
-            nptr = node.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
         self.n = n
         self.n_cols = int(X.shape[1])
         self.grouped = group_id is not None
@@ -1071,20 +1001,6 @@ class RegDataset:
             self.ctx.handle, _lib.dptr(rt), n, _lib.dptr(X), self.n_cols, nptr, self.n_groups,
             ctypes.byref(h)))
         self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.wfpt_reg_dataset_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __len__(self):
-        return self.n
 
     def _outputs(self, terms, n_terms):
         if not terms:
@@ -1144,44 +1060,30 @@ class RegDataset:
         return out, tr, {m[0]: pr[k] for k, m in enumerate(model)}
 
 
-def _rl_dataset(x, response, feedback, split_by):
-    """A transient RLDataset from arguments checked as Cython checks them, in
-    the reference's argument order."""
-    if x is not None:
+def _rl_host(x, response, feedback, split_by, x_optional=False):
+    """The RL functions' arrays, checked as Cython checks them, in the
+    reference's argument order."""
+    if not (x_optional and x is None):
         x = _check_x(x)
-    response = _check_long(response, "response")
-    feedback = _check_x(feedback, "feedback")
-    split_by = _check_long(split_by, "split_by")
-    return RLDataset(x, response, feedback, split_by)
+    return (x, _check_long(response, "response"), _check_x(feedback, "feedback"),
+            _check_long(split_by, "split_by"))
+
+
+def _on_rl_dataset(method, x, response, feedback, split_by, *args, **kw):
+    """An RLDataset method over a transient dataset of the checked arrays."""
+    ds = RLDataset(*_rl_host(x, response, feedback, split_by, x_optional=True))
+    try:
+        return method(ds, *args, **kw)
+    finally:
+        ds.close()
 
 
 def wiener_like_rlddm(x, response, feedback, split_by, q, alpha, pos_alpha, v, sv, a, z, sz, t,
                       st, err, n_st=10, n_sz=10, use_adaptive=1, simps_err=1e-8, p_outlier=0,
                       w_outlier=0):
-    ds = _rl_dataset(x, response, feedback, split_by)
-    try:
-        return ds.wiener_like_rlddm(q, alpha, pos_alpha, v, sv, a, z, sz, t, st, err, n_st, n_sz,
-                                    use_adaptive, simps_err, p_outlier, w_outlier)
-    finally:
-        ds.close()
-
-
-def wiener_like_rl(response, feedback, split_by, q, alpha, pos_alpha, v, z, err=1e-4, n_st=10,
-                   n_sz=10, use_adaptive=1, simps_err=1e-8, p_outlier=0, w_outlier=0):
-    ds = _rl_dataset(None, response, feedback, split_by)
-    try:
-        return ds.wiener_like_rl(q, alpha, pos_alpha, v, z, err, n_st, n_sz, use_adaptive,
-                                 simps_err, p_outlier, w_outlier)
-    finally:
-        ds.close()
-
-
-def wiener_like_multi_rlddm(x, response, feedback, split_by, q, v, sv, a, z, sz, t, st, alpha,
-                            err, multi=None, n_st=10, n_sz=10, use_adaptive=1, simps_err=1e-3,
-                            p_outlier=0, w_outlier=0):
-    return wiener_like_multi_rlddm_terms(x, response, feedback, split_by, q, v, sv, a, z, sz, t,
-                                         st, alpha, err, multi, n_st, n_sz, use_adaptive,
-                                         simps_err, p_outlier, w_outlier, _terms=False)
+    return _on_rl_dataset(RLDataset.wiener_like_rlddm, x, response, feedback, split_by, q, alpha,
+                          pos_alpha, v, sv, a, z, sz, t, st, err, n_st, n_sz, use_adaptive,
+                          simps_err, p_outlier, w_outlier)
 
 
 def wiener_like_rlddm_terms(x, response, feedback, split_by, q, alpha, pos_alpha, v, sv, a, z,
@@ -1190,51 +1092,43 @@ def wiener_like_rlddm_terms(x, response, feedback, split_by, q, alpha, pos_alpha
     """wiener_like_rlddm returning (sum, terms, drift): terms[i] is trial i's
     log term (0.0 for the unscored first trial of a condition), drift[i] the
     drift the recurrence holds when it reaches trial i."""
-    ds = _rl_dataset(x, response, feedback, split_by)
-    try:
-        return ds.wiener_like_rlddm(q, alpha, pos_alpha, v, sv, a, z, sz, t, st, err, n_st, n_sz,
-                                    use_adaptive, simps_err, p_outlier, w_outlier, terms=True)
-    finally:
-        ds.close()
+    return _on_rl_dataset(RLDataset.wiener_like_rlddm, x, response, feedback, split_by, q, alpha,
+                          pos_alpha, v, sv, a, z, sz, t, st, err, n_st, n_sz, use_adaptive,
+                          simps_err, p_outlier, w_outlier, terms=True)
+
+
+def wiener_like_rl(response, feedback, split_by, q, alpha, pos_alpha, v, z, err=1e-4, n_st=10,
+                   n_sz=10, use_adaptive=1, simps_err=1e-8, p_outlier=0, w_outlier=0):
+    return _on_rl_dataset(RLDataset.wiener_like_rl, None, response, feedback, split_by, q, alpha,
+                          pos_alpha, v, z, err, n_st, n_sz, use_adaptive, simps_err, p_outlier,
+                          w_outlier)
 
 
 def wiener_like_rl_terms(response, feedback, split_by, q, alpha, pos_alpha, v, z, err=1e-4,
                          n_st=10, n_sz=10, use_adaptive=1, simps_err=1e-8, p_outlier=0,
                          w_outlier=0):
     """wiener_like_rl returning (sum, terms, drift), as wiener_like_rlddm_terms."""
-    ds = _rl_dataset(None, response, feedback, split_by)
-    try:
-        return ds.wiener_like_rl(q, alpha, pos_alpha, v, z, err, n_st, n_sz, use_adaptive,
-                                 simps_err, p_outlier, w_outlier, terms=True)
-    finally:
-        ds.close()
+    return _on_rl_dataset(RLDataset.wiener_like_rl, None, response, feedback, split_by, q, alpha,
+                          pos_alpha, v, z, err, n_st, n_sz, use_adaptive, simps_err, p_outlier,
+                          w_outlier, terms=True)
+
+
+def wiener_like_multi_rlddm(x, response, feedback, split_by, q, v, sv, a, z, sz, t, st, alpha,
+                            err, multi=None, n_st=10, n_sz=10, use_adaptive=1, simps_err=1e-3,
+                            p_outlier=0, w_outlier=0):
+    return _like_multi_rlddm(None, *_rl_host(x, response, feedback, split_by), q,
+                             (v, sv, a, z, sz, t, st, alpha), err, multi, n_st, n_sz, use_adaptive,
+                             simps_err, p_outlier, w_outlier, False)
 
 
 def wiener_like_multi_rlddm_terms(x, response, feedback, split_by, q, v, sv, a, z, sz, t, st,
                                   alpha, err, multi, n_st=10, n_sz=10, use_adaptive=1,
-                                  simps_err=1e-3, p_outlier=0, w_outlier=0, _terms=True):
+                                  simps_err=1e-3, p_outlier=0, w_outlier=0):
     """wiener_like_multi_rlddm returning (sum, terms, drift); every trial is
     scored here, the first of a run at drift 0."""
-    x = _check_x(x)
-    response = _check_long(response, "response")
-    feedback = _check_x(feedback, "feedback")
-    split_by = _check_long(split_by, "split_by")
-    if multi is None:
-        return full_pdf(x, v, sv, a, z, sz, t, st, err)  # wfpt.pyx:293-294 (TypeError for arrays)
-    n = x.shape[0]
-    _same_length(n, response=response, feedback=feedback, split_by=split_by)
-    ptrs, scal, keep = _multi_rl_args(n, v, sv, a, z, sz, t, st, alpha, multi)
-    c = _lib.context()
-    K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
-    out = ctypes.c_double()
-    tr = np.empty(n, dtype=np.float64) if _terms else None
-    dr = np.empty(n, dtype=np.float64) if _terms else None
-    _lib.check(_lib.wfpt_wiener_like_multi_rlddm_ex(
-        c.handle, _lib.dptr(x), _i64ptr(response), _lib.dptr(feedback), _i64ptr(split_by), n,
-        float(q), ptrs, _lib.dptr(scal), ctypes.byref(K), float(p_outlier), ctypes.byref(out),
-        _lib.dptr(tr) if _terms else None, _lib.dptr(dr) if _terms else None))
-    del keep
-    return (out.value, tr, dr) if _terms else out.value
+    return _like_multi_rlddm(None, *_rl_host(x, response, feedback, split_by), q,
+                             (v, sv, a, z, sz, t, st, alpha), err, multi, n_st, n_sz, use_adaptive,
+                             simps_err, p_outlier, w_outlier, True)
 
 
 def wiener_like_rlddm_nodes(ds, rl_rows, params, err=1e-4, n_st=2, n_sz=2, use_adaptive=1,
