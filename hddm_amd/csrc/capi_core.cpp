@@ -332,9 +332,13 @@ static int finish_sum(wfpt_ctx* c, const wfpt_ds* d, const wfpt::Params& P, cons
 static int run_sum_fast(wfpt_ctx* c, const wfpt_ds* d, const wfpt::Params& P, const wfpt::Knobs& K,
                  double* out) {
   const int64_t n = d->n;
-  if (c->count || n <= 0 || !wfpt::has_deferred_pass(P, K)) return -1;
+  if (n <= 0 || !wfpt::has_deferred_pass(P, K)) return -1;
   const bool eng = engine_family(P, K);
   const bool lean = eng && lean_predicted(c, d);
+  // a counting call (WFPT_PROF_EVALS) keeps the predicted lean pass, whose
+  // counting build tallies its generic-site waves (wfpt_profile_lists); it
+  // never takes the level-0-only prediction of the other families
+  if (c->count && !lean) return -1;
   const bool fast = c->fast_only && d->no_defer;
   if (!lean && !fast) return -1;
   const int lp = lean ? wfpt::kPassLean : 0;

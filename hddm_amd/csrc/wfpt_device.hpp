@@ -1805,6 +1805,305 @@ __host__ __device__ inline void root_grids(const Params& P, RootGrids& R) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Uniform waves of the lean pass (lean_kernel<kAdaptTZ>). A resident dataset
+// is ordered by boundary, then |rt|, so the 64 trials of a wave almost always
+// share the series decision (small, K; pdf.pxi:36-60) of each of their five
+// t nodes. Such a wave keeps the five decisions in scalar registers and runs
+// lean_uniform_level0: per lane the same floating-point operations on the
+// same operands in the same order as eng_level0_t<kAdaptTZ, false, true>, but
+// everything that depends on (grid, K) alone is read from a host table
+// (UniformTab) with scalar loads, both series loops are scalar-counted, and
+// small_grid2d's per-node range guard is replaced by one per-trial bound
+// (uniform_guard). Any other wave runs eng_level0_t unchanged.
+
+// Per boundary: the small-time multipliers g_i + 2k of small_grid2d's term
+// loop (k2 there is the exact integer 2k, so g_i + k2 is this sum), and per K
+// the products of its prologue that depend on (grid, K) alone, in its own
+// expressions (contraction off: the bits a lane computes).
+constexpr int kUniK = 8;  // small_grid2d's K limit
+static_assert(kSinK <= 15 && kUniK <= 15, "K packs into 4 bits per t node");
+struct UniformK {
+  double u0u0;   // u0 * u0,  u0 = g_0 + (double)(2 lower)
+  double hh2;    // h * (2.0 * u0 + h),  h = g_1 - g_0
+  double hh;     // h * h
+  double u0p1;   // u0 + 1.0
+  double h;
+  double bound;  // uniform_guard's multiplier of |m| (nondecreasing in K)
+};
+struct UniformTab {
+  double u[9][5];  // u[k + 4][i] = g_i + (double)(2 k), k = -4..4
+  UniformK k[kUniK + 1];
+  double amax;     // max_i |A_i|
+};
+__host__ __device__ inline void uniform_tab(const ZGrid& G, UniformTab& T) {
+  for (int k = -4; k <= 4; ++k)
+    for (int i = 0; i < 5; ++i) T.u[k + 4][i] = G.g[i] + (double)(2 * k);
+  const double h = G.g[1] - G.g[0];
+  double bound = 0.0;
+  T.k[0] = UniformK{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int K = 1; K <= kUniK; ++K) {
+    const int lower = (int)(-floor((K - 1) / 2.));
+    const int upper = (int)ceil((K - 1) / 2.);
+    const double lo2 = (double)(2 * lower);
+    const double u0 = G.g[0] + lo2, u4 = G.g[4] + (double)(2 * upper);
+    UniformK& C = T.k[K];
+    C.u0u0 = u0 * u0;
+    C.hh2 = h * (2.0 * u0 + h);
+    C.hh = h * h;
+    C.u0p1 = u0 + 1.0;
+    C.h = h;
+    // |m| times this bounds every m-part of small_grid2d's guarded exponents
+    // at this K (uniform_guard); the running maximum makes it monotone in K
+    const double U = fmax(fabs(u0), fabs(u4)), km1 = (double)(K - 1);
+    double b = fmax(U * U, 8.0);
+    b = fmax(b, fabs(C.hh2) + 6.0 * C.hh + (4.0 * km1) * fabs(h));
+    b = fmax(b, 4.0 * fabs(C.u0p1) + 8.0 * fabs(km1 - 1.0));
+    bound = fmax(bound, b);
+    C.bound = bound;
+  }
+  double am = 0.0;
+  for (int i = 0; i < 5; ++i) am = fmax(am, fabs(G.A[i]));
+  T.amax = am;
+}
+struct UniformTabs {
+  UniformTab U[2];  // per boundary, as RootGrids::G
+};
+__host__ __device__ inline void uniform_tabs(const RootGrids& R, UniformTabs& T) {
+  for (int flip = 0; flip < 2; ++flip) uniform_tab(R.G[flip], T.U[flip]);
+}
+
+// One range test per trial in place of small_grid2d's `safe` at each of its
+// t nodes (and of tnode_pdf_sv_grid5's `moderate`). It only selects which
+// code evaluates the trial, never a value. Arguments: tt4 = tt of t node 4
+// (the smallest of the five, > 0), vvx0 = v^2 (x - lb) (the largest v^2 xx),
+// bound = UniformK::bound of the largest K among the trial's small-time
+// nodes (0 if none), amax = UniformTab::amax.
+//
+// Claim: if this returns true, `safe` (limit 640) holds at every small-time
+// node and |c_i| < 600 at every node. Proof, with M = max_j |m_j|,
+// C = max_{i,j} |c_i| over the nodes j:
+//   * m_j = -0.5 r^2, r = rsqrt(tt_j), tt_j >= tt4, so M <= (0.5 / tt4)(1 + 1e-15).
+//   * c_i = (A_i - dv) dm with 0 <= dv <= v^2 xx <= vvx0 and 0 < dm <= 1
+//     (sv = 0: dm = 1; else dm = 0.5 r^2, r = rsqrt(sv^2 xx + 1) <= 1 + 1e-15, so
+//     dm <= 0.5 (1 + 1e-15)); rounding is monotone, so C <= Cb (1 + 1e-15) with
+//     Cb = (amax + vvx0) (sv = 0 ? 1 : 0.5).
+//   * small_grid2d's guarded quantities at a node with K terms, |d1| <= 2C,
+//     |d2| <= 4C, h = g_1 - g_0:
+//       cmax <= C;   |m U^2 + cmin| <= M U^2 + C;
+//       rmax <= |aR| + 3 |aQj| + km1 |aQjk|
+//            <= M (|h (2 u0 + h)| + 6 h^2 + 4 km1 |h|) + 14 C;
+//       pmax <= |aP| + |km1 - 1| |aQk| = M (4 |u0 + 1| + 8 |km1 - 1|);
+//       qmax <= max(2 M h^2 + 4 C, 8 M, 4 M |h|);
+//     each is <= M bound_K + 14 C up to a few roundings (relative 1e-15), and
+//     bound_K <= bound (the table's running maximum over K).
+//   * The test below is (0.5 bound) / tt4 + 14 Cb < 600 multiplied by tt4 > 0,
+//     a few roundings again. So every guarded quantity is below
+//     600 (1 + 1e-14) < 640, and C <= 600 / 14 < 600.
+// A NaN anywhere compares false: the trial then takes the per-node guards.
+__host__ __device__ inline bool uniform_guard(double tt4, double vvx0, double sv, double bound,
+                                              double amax) {
+  const double Cb = (amax + vvx0) * (sv == 0 ? 1.0 : 0.5);
+  return 0.5 * bound + (14.0 * Cb) * tt4 < 600.0 * tt4;
+}
+
+// Each lane's own five decisions, by today's operations: l0_hints for t nodes
+// 0 and 4 and its `shared` rule, decide32 for nodes 1..3 otherwise. False
+// (the lane's wave takes eng_level0_t) for invalid parameters, a node with
+// x - t_node <= 0, no recurrence hint q0, an fp32 estimate that asks for the
+// fp64 decision (within 1e-5 of a threshold), or a K beyond the tables. On
+// true: kpack = K_j << 4j, smask bit j = small_j, H = the trial's hints.
+__device__ inline bool l0_decisions(const Trial& tr, const Params& P, const Knobs& K, L0Hints& H,
+                                    unsigned& kpack, unsigned& smask) {
+  kpack = 0u;
+  smask = 0u;
+  double lb, ub;
+  tree_root<kAdaptTZ>(tr, P, lb, ub);
+  H = l0_hints(tr.x, lb, ub, P.a, K.err);
+  bool ok = tr.valid && (tr.x - ub > 0) && H.q0 >= 0.0 && H.ok0 && H.ok4;
+  if (!ok) return false;
+  const double c = (ub + lb) / 2.;
+  const double d = (lb + c) / 2., e = (c + ub) / 2.;
+  auto put = [&](int j, const Decision& D) {
+    ok = ok && D.amb == 0 && D.K >= 1 && D.K <= (D.small ? kUniK : kSinK);
+    kpack |= (unsigned)(D.K & 15) << (4 * j);
+    smask |= (D.small ? 1u : 0u) << j;
+  };
+  put(0, H.D0);
+  put(4, H.D4);
+  if (H.shared) {
+    put(1, H.D0);
+    put(2, H.D0);
+    put(3, H.D0);
+  } else {
+#pragma unroll 1
+    for (int j = 1; j < 4; ++j) {
+      const double tc = j == 1 ? d : j == 2 ? c : e;
+      Decision D{0, 0, 0};
+      float args;
+      ok = decide32((tr.x - tc) * H.ia2, K.err, D, args) && ok;
+      put(j, D);
+    }
+  }
+  return ok;
+}
+
+// small_grid2d with wave-uniform K, past its guard (uniform_guard passed):
+// the same exponents, exponentials and products per lane, the (grid, K)
+// operands from the table. c: the drift exponents of z nodes 0..2.
+__device__ inline bool small_grid2d_u(double m, double f, double c0, double c1, double c2,
+                                      const UniformTab& U, int K, double (&out)[5]) {
+  const UniformK& C = U.k[K];
+  const int lower = -((K - 1) >> 1), upper = K >> 1;  // -floor((K-1)/2.), ceil((K-1)/2.)
+  const double d1 = c1 - c0;
+  const double d2 = (c2 - c1) - d1;
+  const double a00 = m * C.u0u0 + c0;
+  const double aR = m * C.hh2 + d1;
+  const double aQj = (2.0 * m) * C.hh + d2;
+  const double aP = (4.0 * m) * C.u0p1;
+  const double aQk = 8.0 * m;
+  const double aQjk = (4.0 * m) * C.h;
+  double E0 = exp_val(a00), R0 = exp_val(aR), P = exp_val(aP);
+  const double Qj = exp_val(aQj), Qk = exp_val(aQk), Qjk = exp_val(aQjk);
+  double s[5];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) s[i] = 0.0;
+#pragma unroll 1
+  for (int k = lower; k <= upper; ++k) {
+    const double* u = U.u[k + 4];
+    double E = E0, R = R0;
+    s[0] = madd(u[0], E, s[0]);
+#pragma unroll
+    for (int i = 1; i < 5; ++i) {
+      E = E * R;
+      if (i < 4) R = R * Qj;
+      s[i] = madd(u[i], E, s[i]);
+    }
+    E0 = E0 * P;
+    P = P * Qk;
+    R0 = R0 * Qjk;
+  }
+  bool clean = true;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    out[i] = s[i] * f;
+    clean = clean & (s[i] > 0) & !__builtin_isinf(out[i]);
+  }
+  return clean;
+}
+
+// eng_level0_t<kAdaptTZ, false, true> of one trial of a uniform wave: kpack,
+// smask (wave-uniform: l0_decisions of every lane agree), H the lane's own
+// hints, uniform_guard passed. bail: a node was not clean (a non-positive
+// series value, an infinite product), which the fix-up code of
+// tnode_pdf_sv_grid5 handles: the caller reruns the whole wave on
+// eng_level0_t and discards this result.
+__device__ inline int lean_uniform_level0(const Trial& tr, const Params& P, const Knobs& K,
+                                          const ZGrid& G, const UniformTab& U, const double* stab,
+                                          const L0Hints& H, unsigned kpack, unsigned smask,
+                                          double& p, long long& ne, unsigned& pend, bool& bail) {
+  p = 0.0;
+  pend = 0u;
+  double lb, ub;
+  tree_root<kAdaptTZ>(tr, P, lb, ub);
+  const double sv = P.sv, v = tr.v, x = tr.x;
+  const double iw = 1.0 / (ub - lb);
+  const double tcc = (ub + lb) / 2.;
+  const double tcd = (lb + tcc) / 2., tce = (tcc + ub) / 2.;
+  const double iZz = 1.0 / ((tr.z + tr.sz / 2.) - (tr.z - tr.sz / 2.));
+  const double h = ub - lb;
+  int flags = 0;
+  bool clean = true;
+  double X = 0.0, Y = 0.0, Z = 0.0, y4 = 0.0;
+  // unrolled like eng_level0_t's node loop (a rolled loop measured 3% slower):
+  // tc, qh(j) and the Simpson bookkeeping fold per node
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const int Kj = (int)((kpack >> (4 * j)) & 15u);
+    const bool small = ((smask >> j) & 1u) != 0u;
+    const double tc = j == 0 ? lb : j == 1 ? tcd : j == 2 ? tcc : j == 3 ? tce : ub;
+    // tnode_setup_r with the known decision
+    const double xx = x - tc;
+    const double tt = xx * H.ia2;
+    double sc = H.ia2, cden = 0.0;
+    if (sv != 0) {
+      const double r = rsqrt(((sv * sv) * xx) + 1.0);
+      cden = (0.5 * r) * r;
+      sc = sc * r;
+    }
+    const double vvx = (v * v) * xx;
+    const double dv = (sv == 0) ? vvx * 0.5 : vvx, dm = (sv == 0) ? 1.0 : cden;
+    const double c0 = (G.A[0] - dv) * dm, c1 = (G.A[1] - dv) * dm, c2 = (G.A[2] - dv) * dm;
+    double f[5];
+    if (small) {
+      const double r = rsqrt(tt), r2 = r * r;
+      const double rn = kInvSqrt2Pi * (r2 * r);
+      const double m = -0.5 * r2;
+      clean = small_grid2d_u(m, rn * sc, c0, c1, c2, U, Kj, f) && clean;
+    } else {
+      // (H.q0 >= 0: the recurrence's q, as tnode_setup_r takes it from qh(j))
+      const double m = H.qh(j);
+      const double q2 = m * m;
+      double pp[5];
+      double e = m, r = m * q2;
+#pragma unroll
+      for (int i = 0; i < 5; ++i) pp[i] = m * stab[5 + i];
+#pragma unroll 1
+      for (int k = 2; k <= Kj; ++k) {
+        e = e * r;
+        r = r * q2;
+        const double ke = (double)k * e;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) pp[i] = madd(ke, stab[5 * k + i], pp[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < 5; ++i) pp[i] = pp[i] * kPi;
+      // the drift factors (|c| < 600 by uniform_guard: the `moderate` form)
+      const double d1 = c1 - c0;
+      const double d2 = (c2 - c1) - d1;
+      double ex = exp_val(c0);
+      double rr = exp_val(d1);
+      const double qd = exp_val(d2);
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        f[i] = (pp[i] * ex) * sc;
+        clean = clean & (pp[i] > 0) & !__builtin_isinf(f[i]);
+        ex = ex * rr;
+        rr = rr * qd;
+      }
+    }
+    // inner_root
+#pragma unroll
+    for (int i = 0; i < 5; ++i) f[i] = f[i] * iZz;
+    ne += 5;
+    const Simp s = simp5p(G.h6, G.h12, f[0], f[1], f[2], f[3], f[4]);
+    if (simpson_refine(s.S, s.S2, K.simps_err, K.n_sz, flags)) pend |= 1u << (j * (kTreeW / 4));
+    const double y = simp_value(s) * iw;
+    // the root Simpson sums, as eng_level0_t (KEEP_F = false)
+    const double x4 = X + (4 * y);
+    if (j == 2) Z = (h / 12) * (Y + y);
+    Y = (j == 1 || j == 2) ? x4 : Y;
+    X = (j == 0 || j == 2) ? y : (j == 3 ? x4 : X);
+    y4 = y;
+  }
+  bail = !clean;
+  if (flags & kFlagExact) return kExact;
+  if (pend) return kTree;
+  Simp s;
+  s.S = (h / 6) * (Y + y4);
+  s.Sl = Z;
+  s.Sr = (h / 12) * (X + y4);
+  s.S2 = s.Sl + s.Sr;
+  const bool refine = simpson_refine(s.S, s.S2, K.simps_err, K.n_st, flags);
+  if (flags & kFlagExact) return kExact;
+  if (refine) return kTree;
+  p = s.S2 + (s.S2 - s.S) / 15;
+  if (p > kExactBelow) return kFinal;  // (x - lb > 0: never structural)
+  if (!tiny_absorbed(p, P.p_outlier, K.w_outlier)) return kExact;
+  p = 0.0;
+  return kFinal;
+}
+
 // Per-call constants of the direct family (simple DDM: one pdf_sv per trial,
 // pdf.pxi:74-102 at w = z) for both boundaries, computed once on the host with
 // the device's operations (bit-identical): the flipped v and w (pdf.pxi:

@@ -18,7 +18,10 @@
 // Adaptive / direct integration families (the HDDM case), one resident call:
 //   lean_kernel<MODE>     level 0 of every trial, one 64-trial chunk per wave,
 //                         boundary-uniform root grids in scalar registers (4
-//                         waves/SIMD): a chunk none of whose trials refines
+//                         waves/SIMD; the 2-D family's waves whose lanes agree on
+//                         every t node's series decision keep those in scalar
+//                         registers too: lean_uniform_level0, wfpt_device.hpp):
+//                         a chunk none of whose trials refines
 //                         ends here (mixture, log, chunk partial); a chunk that
 //                         refines is flagged for the engine's redo pass
 //   engine_kernel<MODE>   level 0 + in-wave refinement rounds (z walks, t-node

@@ -2,7 +2,10 @@
 //   direct_kernel        the simple DDM (one pdf_sv per trial)
 //   lean_kernel<MODE>    level 0 of every trial of the adaptive families, one
 //                        64-trial chunk per wave; a chunk that refines is
-//                        flagged for the engine's redo pass (wfpt_engine.hip)
+//                        flagged for the engine's redo pass (wfpt_engine.hip).
+//                        The 2-D family has two sites: waves whose lanes agree
+//                        on every t node's series decision (lean_uniform_level0,
+//                        wfpt_device.hpp) and the per-lane one (eng_level0_t)
 // (One-block calls run level 0 and the finalize in one launch: wfpt_sum.hip.)
 #include "wfpt_kernel_common.hpp"
 
@@ -73,9 +76,11 @@ void direct_kernel(TrialArgs A, Work W, DirectArgs D) {
 #endif
 constexpr int kLeanBlock = WFPT_LEAN_BLOCK;
 static_assert(kLeanBlock % 64 == 0 && kLeanBlock <= kFastBlock, "kLeanBlock");
+static_assert(sizeof(TrialArgs) + sizeof(Work) + sizeof(RootGrids) + sizeof(UniformTabs) <= 4096,
+              "lean_kernel's arguments exceed the 4 KB kernel argument segment");
 template <int MODE, bool COUNT, int OUT>
 __global__ __launch_bounds__(kLeanBlock, FastWaves<MODE>::value > 0 ? FastWaves<MODE>::value : 1)
-void lean_kernel(TrialArgs A, Work W, RootGrids R) {
+void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T) {
 #ifdef WFPT_PHASE_TIMING
   const long long rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -98,13 +103,57 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R) {
   const bool pos = x0 > 0;
   const unsigned long long bo = __ballot(own), bp = __ballot(own && pos);
   const int b = (bp == bo) ? 1 : 0;  // every trial upper: 1; otherwise lower first
-  if (own && pos == (b != 0))
-    oc = eng_level0_t<MODE, false, true>(trial_setup_b(x0, A.P, b != 0), A.P, A.K,
-                                         zgrid_uniform(R, b), p, f0, ne0, pend0, &R.S[b][0][0]);
-  if (bp != 0ull && bp != bo) {  // mixed wave: its upper-boundary lanes
-    if (own && pos)
-      oc = eng_level0_t<MODE, false, true>(trial_setup_b(x0, A.P, true), A.P, A.K, R.G[1], p, f0,
-                                           ne0, pend0, &R.S[1][0][0]);
+  // kAdaptTZ: a wave of one boundary whose own lanes all reach the same
+  // (small, K) at each of the five t nodes, each by its own decision, and all
+  // pass the per-trial range test keeps the decisions in scalar registers
+  // (lean_uniform_level0). Every other wave, and a uniform wave one of whose
+  // lanes met a value the fix-up code handles, runs the generic site below.
+  bool done = false;
+  if constexpr (MODE == kAdaptTZ) {
+    if (bp == bo || bp == 0ull) {
+      const Trial tr = trial_setup_b(x0, A.P, b != 0);
+      L0Hints H;
+      unsigned kp, sm;
+      const bool okd = own && l0_decisions(tr, A.P, A.K, H, kp, sm);
+      const unsigned kp0 = __builtin_amdgcn_readfirstlane(kp);
+      const unsigned sm0 = __builtin_amdgcn_readfirstlane(sm);
+      if (__ballot(okd && kp == kp0 && sm == sm0) == bo) {
+        int kmax = 0;  // the largest K among the small-time nodes
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+          const int kj = (int)((kp0 >> (4 * j)) & 15u);
+          if (((sm0 >> j) & 1u) != 0u && kj > kmax) kmax = kj;
+        }
+        const UniformTab& U = T.U[b];
+        double lb, ub;
+        tree_root<MODE>(tr, A.P, lb, ub);
+        const bool safe = uniform_guard((tr.x - ub) * H.ia2, (tr.v * tr.v) * (tr.x - lb), A.P.sv,
+                                        U.k[kmax].bound, U.amax);
+        if (__ballot(own && safe) == bo) {
+          bool bail = false;
+          if (own)
+            oc = lean_uniform_level0(tr, A.P, A.K, zgrid_uniform(R, b), U, &R.S[b][0][0], H, kp0,
+                                     sm0, p, ne0, pend0, bail);
+          done = __ballot(own && bail) == 0ull;
+        }
+      }
+    }
+  }
+  if (!done) {
+    p = 0.0;
+    ne0 = 0;
+    pend0 = 0u;
+    oc = kFinal;
+    if (own && pos == (b != 0))
+      oc = eng_level0_t<MODE, false, true>(trial_setup_b(x0, A.P, b != 0), A.P, A.K,
+                                           zgrid_uniform(R, b), p, f0, ne0, pend0, &R.S[b][0][0]);
+    if (bp != 0ull && bp != bo) {  // mixed wave: its upper-boundary lanes
+      if (own && pos)
+        oc = eng_level0_t<MODE, false, true>(trial_setup_b(x0, A.P, true), A.P, A.K, R.G[1], p, f0,
+                                             ne0, pend0, &R.S[1][0][0]);
+    }
+    // counting build: the lean waves that took the generic site
+    if (COUNT && MODE == kAdaptTZ && lane == 0) atomicAdd(&W.prof[3], 1);
   }
   if (__ballot(oc == kTree) != 0ull) {
     if (lane == 0) {
@@ -146,10 +195,13 @@ void launch_direct(bool count, int out, const TrialArgs& A, const Work& W, hipSt
 void launch_lean(int mode, bool count, int out, const TrialArgs& A, const Work& W, hipStream_t s) {
   RootGrids R;
   root_grids(A.P, R);
+  UniformTabs T;  // read by the 2-D family's uniform waves only
+  uniform_tabs(R, T);
   with_value<kAdaptT, kAdaptTZ>(mode, [&](auto m) {
     with_build<false>(count, out, [&](auto c, auto o) {
       hipLaunchKernelGGL((lean_kernel<decltype(m)::value, decltype(c)::value, decltype(o)::value>),
-                         dim3((A.n + kLeanBlock - 1) / kLeanBlock), dim3(kLeanBlock), 0, s, A, W, R);
+                         dim3((A.n + kLeanBlock - 1) / kLeanBlock), dim3(kLeanBlock), 0, s, A, W, R,
+                         T);
     });
   });
 }

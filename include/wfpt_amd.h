@@ -613,7 +613,11 @@ int wfpt_profile_read(wfpt_ctx *ctx, double *kernel_ms, int64_t *launches, int64
  * (wfpt_wiener_like_nodes, adaptive families) adds to the same counters, plus
  * counts[3] trials its level-0 pass left to the chunk engine and counts[0]
  * node segments the chunk engine ran (one per node present in a listed
- * chunk). */
+ * chunk). A resident full-DDM call whose level 0 is the lean pass adds to
+ * counts[3] the number of its waves (64-trial chunks) that took the generic
+ * per-lane site instead of the uniform-wave one (every slot 0..10 has a
+ * writer: counts[8] is the z walks after level 0; slot 3 is the one a
+ * resident call leaves alone). */
 int wfpt_profile_lists(wfpt_ctx *ctx, int64_t counts[16], int reset);
 /* Diagnostic builds (WFPT_PHASE_TIMING): the last engine launch's per-wave
  * records, 8 words per 64-trial chunk {start, end (100 MHz real-time clock),
