@@ -112,9 +112,34 @@ def variant_path(name):
     return os.path.join(LIBDIR, f"libwfpt_amd_{name}.so")
 
 
+# The exact path's two headers as device kernels of their own, one element per
+# lane (tests/c/exact_device.hip, loaded by tests/test_exact_device.py): test
+# infrastructure built with the library's flags, not part of the library or of
+# its source digest.
+PROBE = os.path.join(LIBDIR, "libwfpt_exact_probe.so")
+PROBE_SRC = os.path.join(ROOT, "tests", "c", "exact_device.hip")
+
+
+def build_probe(force=False, verbose=False):
+    os.makedirs(LIBDIR, exist_ok=True)
+    deps = [PROBE_SRC] + [os.path.join(CSRC, f) for f in ("wfpt_crlibm.hpp", "wfpt_exact.hpp")]
+    if not force and not _stale(PROBE, deps):
+        return PROBE
+    tmp = PROBE + ".tmp"
+    cmd = [HIPCC, *CFLAGS, "-shared", "-o", tmp, PROBE_SRC, "-Wl,-rpath,/opt/rocm/lib"]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    os.replace(tmp, PROBE)
+    return PROBE
+
+
 def build_variants(force=False, verbose=False):
-    return [build(force=force, verbose=verbose, defines=d, out=variant_path(k))
+    """The diagnostic libraries and the exact-path probe: everything the GPU
+    tests load besides the product."""
+    libs = [build(force=force, verbose=verbose, defines=d, out=variant_path(k))
             for k, d in VARIANTS.items()]
+    return libs + [build_probe(force=force, verbose=verbose)]
 
 
 if __name__ == "__main__":

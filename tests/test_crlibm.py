@@ -6,8 +6,10 @@ The header is compiled with gcc (tests/c/crlibm_check.cpp) and checked:
   * against this host's glibc (what the reference's CPU build calls): the
     disagreement rate must be glibc's own misrounding rate (< 0.2%), far below
     OCML's 1-24% (tools/libm_probe.hip).
-The same source is compiled for gfx950 into the exact path; IEEE operations and
-fma() give the same bits on both.
+The same source is compiled for gfx950 into the exact path. That build is not
+taken on trust: tests/test_exact_device.py runs it on the device (the
+generators below, 200,000 inputs each) and requires the host build's bits and,
+on 1,500 samples per function, the exact value rounded once.
 """
 import decimal
 import os
