@@ -140,6 +140,8 @@ _SIGNATURES = {
     "wfpt_wiener_like_multi_rlddm_ex": (_I, _RL_HOST + _MULTI + [_PD, _PD]),
     "wfpt_wiener_like_rlddm_nodes": (_I, [_VP, _VP, _PD, _PP, _PK, _PD]),
     "wfpt_wiener_like_rlddm_nodes_ex": (_I, [_VP, _VP, _PD, _PP, _PK, _PD, _PD, _PD]),
+    "wfpt_wiener_like_rlddm_nodes_multi": (_I, [_VP, _VP, _PD, _PP, _I32, _PK, _PD]),
+    "wfpt_wiener_like_rlddm_nodes_multi_ex": (_I, [_VP, _VP, _PD, _PP, _I32, _PK, _PD, _PD, _PD]),
     # regression likelihoods
     "wfpt_reg_dataset_create": (_I, [_VP, _PD, _I64, _PD, _I32, _PI32, _I32, _PVP]),
     "wfpt_reg_dataset_destroy": (None, [_VP]),

@@ -29,9 +29,16 @@ struct wfpt_rl_ds : DsBase {
   std::vector<int64_t> c2caller;    // host [m]: the caller's index of a compact trial
   std::vector<int64_t> node_off_host;  // host copy of node_off
   int64_t node_max = 0;             // most scored trials in one node
+  // the multi-table node batch's view of the scored trials, grown on demand
+  // (rl_replicate): x_c and the nodes' compact ranges once per table
+  mutable int32_t rep_tables = 0;
+  mutable DevBuf<double> x_rep;            // [rep_tables x m]
+  mutable DevBuf<int64_t> off_rep;         // [rep_tables x n_nodes + 1]
+  mutable std::vector<int64_t> off_rep_host;
   void free_device() override {
     release_all(x_c, lane_start, lane_out, lane_len, lane_node, step_off, resp_t, fb_t, caller,
-                resp_c, node_c, node_off);
+                resp_c, node_c, node_off, x_rep, off_rep);
+    rep_tables = 0;
   }
 };
 #pragma GCC visibility pop
@@ -207,32 +214,64 @@ wfpt::RlLayout rl_layout(const wfpt_rl_ds* d) {
 // call, c->rl.drift_in (every trial, the caller's order). Opens the call's
 // profile bracket.
 int rl_scan(wfpt_ctx* c, const wfpt_rl_ds* d, const wfpt::RlRow& one, const wfpt::RlRow* rows,
-            const double* vmul, const double* rate, bool want_drift) {
-  HIP_TRY(c->rl.drift.reserve(std::max<int64_t>(d->m, 1)));
+            const double* vmul, const double* rate, bool want_drift, int32_t n_tables = 0) {
+  const int64_t T = std::max<int32_t>(n_tables, 1);
+  HIP_TRY(c->rl.drift.reserve(std::max<int64_t>(T * d->m, 1)));
   const bool separate = want_drift && !d->by_runs;  // by_runs: compact == the caller's order
-  if (separate) HIP_TRY(c->rl.drift_in.reserve(std::max<int64_t>(d->n, 1)));
+  if (separate) HIP_TRY(c->rl.drift_in.reserve(std::max<int64_t>(T * d->n, 1)));
   if (c->count) HIP_TRY(hipMemsetAsync(c->evals.p, 0, sizeof(unsigned long long), c->stream));
   if (c->profile) HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  wfpt::launch_rl_scan(rl_layout(d), one, rows, vmul, rate, c->rl.drift.p,
-                       separate ? c->rl.drift_in.p : nullptr, c->stream);
+  double* drift_in = separate ? c->rl.drift_in.p : nullptr;
+  if (n_tables > 0)  // the multi-table node batch: rows holds n_tables x n_nodes rows
+    wfpt::launch_rl_scan_multi(rl_layout(d), wfpt::RlTables{n_tables, d->n_nodes, d->m, d->n},
+                               rows, c->rl.drift.p, drift_in, c->stream);
+  else
+    wfpt::launch_rl_scan(rl_layout(d), one, rows, vmul, rate, c->rl.drift.p, drift_in, c->stream);
   HIP_TRY(hipGetLastError());
   return WFPT_OK;
 }
 
 
 // The _ex outputs of a finished call, in the caller's order: out_trial (each
-// scored trial's term from c->lp, 0.0 for an unscored first trial), out_drift.
-int rl_outputs(wfpt_ctx* c, const wfpt_rl_ds* d, double* out_trial, double* out_drift) {
+// scored trial's term from c->lp, 0.0 for an unscored first trial), out_drift;
+// T tables of a multi-table call one after the other (n values each).
+int rl_outputs(wfpt_ctx* c, const wfpt_rl_ds* d, double* out_trial, double* out_drift,
+               int64_t T = 1) {
   if (out_trial && d->n > 0) {
-    std::vector<double> h(std::max<int64_t>(d->m, 1));
+    std::vector<double> h(std::max<int64_t>(T * d->m, 1));
     if (d->m > 0)
-      HIP_TRY(hipMemcpy(h.data(), c->lp.p, d->m * sizeof(double), hipMemcpyDeviceToHost));
-    std::fill(out_trial, out_trial + d->n, 0.0);
-    for (int64_t i = 0; i < d->m; ++i) out_trial[d->c2caller[i]] = h[i];
+      HIP_TRY(hipMemcpy(h.data(), c->lp.p, T * d->m * sizeof(double), hipMemcpyDeviceToHost));
+    std::fill(out_trial, out_trial + T * d->n, 0.0);
+    for (int64_t t = 0; t < T; ++t)
+      for (int64_t i = 0; i < d->m; ++i)
+        out_trial[t * d->n + d->c2caller[i]] = h[t * d->m + i];
   }
   if (out_drift && d->n > 0)
     HIP_TRY(hipMemcpy(out_drift, d->by_runs ? c->rl.drift.p : c->rl.drift_in.p,
-                      d->n * sizeof(double), hipMemcpyDeviceToHost));
+                      T * d->n * sizeof(double), hipMemcpyDeviceToHost));
+  return WFPT_OK;
+}
+
+// Grows the dataset's replicated view to T tables: x_rep = x_c T times over,
+// off_rep[t n_nodes + j] = t m + node_off[j] (the compact range of node j in
+// table t; T n_nodes + 1 offsets). The stream is idle here: every call on the
+// context ends in its completion wait.
+int rl_replicate(wfpt_ctx* c, const wfpt_rl_ds* d, int32_t T) {
+  if (T <= d->rep_tables) return WFPT_OK;
+  const int64_t m = d->m, nn = d->n_nodes;
+  d->rep_tables = 0;
+  HIP_TRY(d->x_rep.reserve(std::max<int64_t>(T * m, 1)));
+  HIP_TRY(d->off_rep.reserve(T * nn + 1));
+  for (int64_t t = 0; t < T && m > 0; ++t)
+    HIP_TRY(hipMemcpyAsync(d->x_rep.p + t * m, d->x_c.p, m * sizeof(double),
+                           hipMemcpyDeviceToDevice, c->stream));
+  d->off_rep_host.resize(T * nn + 1);
+  for (int64_t t = 0; t < T; ++t)
+    for (int64_t j = 0; j < nn; ++j) d->off_rep_host[t * nn + j] = t * m + d->node_off_host[j];
+  d->off_rep_host[T * nn] = T * m;
+  HIP_TRY(hipMemcpyAsync(d->off_rep.p, d->off_rep_host.data(), (T * nn + 1) * sizeof(int64_t),
+                         hipMemcpyHostToDevice, c->stream));
+  d->rep_tables = T;
   return WFPT_OK;
 }
 
@@ -446,6 +485,80 @@ int wfpt_wiener_like_rlddm_nodes(wfpt_ctx* c, const wfpt_rl_ds* d, const double*
                                  const wfpt_params* per_node, const wfpt_knobs* k,
                                  double* out_logp) {
   return wfpt_wiener_like_rlddm_nodes_ex(c, d, rl_rows, per_node, k, out_logp, nullptr, nullptr);
+}
+
+int wfpt_wiener_like_rlddm_nodes_multi_ex(wfpt_ctx* c, const wfpt_rl_ds* d,
+                                          const double* rl_tables, const wfpt_params* tables,
+                                          int32_t n_tables, const wfpt_knobs* k, double* out_logp,
+                                          double* out_trial, double* out_drift) {
+  if (!c || !d || !rl_tables || !tables || !k || !out_logp)
+    return fail(WFPT_ERR_ARG, "null pointer");
+  if (n_tables < 1) return fail(WFPT_ERR_ARG, "n_tables < 1");
+  if (int rc = rl_check_ds(c, d, true)) return rc;
+  const int32_t nn = d->n_nodes;
+  if (nn <= 0) return fail(WFPT_ERR_ARG, "RL dataset was created without node ids");
+  if (d->node_max > wfpt::kRlNodeMax)
+    return fail(WFPT_ERR_UNSUPPORTED, "a node holds more scored trials than the per-node sum takes");
+  // the scan's lanes, the rows and the scoring pass's deferred-record count are ints
+  const int64_t T = n_tables, G = T * nn, m = d->m;
+  if (T * d->n_seg > INT32_MAX || T * m > INT32_MAX || G > INT32_MAX)
+    return fail(WFPT_ERR_UNSUPPORTED,
+                "n_tables x segments, scored trials or nodes exceeds the kernels' index range");
+  for (int64_t j = 1; j < G; ++j)  // the per-trial-parameter pass takes one p_outlier
+    if (tables[j].p_outlier != tables[0].p_outlier)
+      return fail(WFPT_ERR_UNSUPPORTED,
+                  "the RL node batch needs one p_outlier for all nodes of all tables");
+  const double p_outlier = tables[0].p_outlier;
+  if (!p_outlier_in_range(p_outlier)) {  // wfpt.pyx:102-103, every node of every table
+    for (int64_t j = 0; j < G; ++j) out_logp[j] = -INFINITY;
+    return WFPT_OK;
+  }
+  const wfpt::Knobs K = to_knobs(k);
+  WFPT_RANGE("wfpt_wiener_like_rlddm_nodes_multi");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  std::vector<wfpt::RlRow> rows(G);
+  std::vector<wfpt::Params> par(G);
+  for (int64_t j = 0; j < G; ++j) {
+    rows[j] = rl_row(rl_tables[3 * j], rl_tables[3 * j + 1], rl_tables[3 * j + 2], tables[j].v);
+    par[j] = to_params(&tables[j]);
+  }
+  // one copy each for all tables
+  HIP_TRY(c->rl.rows.reserve(G));
+  HIP_TRY(c->rl.par.reserve(G));
+  HIP_TRY(hipMemcpyAsync(c->rl.rows.p, rows.data(), G * sizeof(wfpt::RlRow),
+                         hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->rl.par.p, par.data(), G * sizeof(wfpt::Params),
+                         hipMemcpyHostToDevice, c->stream));
+  if (int rc = rl_replicate(c, d, n_tables)) return rc;
+  // The one-table call's sequence over T x the work: table t's scored trials
+  // are trials [t m, (t + 1) m) of every per-trial array, its nodes groups
+  // [t n_nodes, (t + 1) n_nodes) of score_runs. The scoring kernels work trial
+  // by trial and the per-node sum counts its blocks from the node's first
+  // trial, so no bit depends on where a table starts.
+  constexpr int mask = 0x2e;  // sv, a, z, t per trial; sz and st scalars of the pass
+  const int64_t tm = T * m;
+  HIP_TRY(c->rl.arr.reserve(std::max<int64_t>(4 * tm, 1)));
+  if (int rc = rl_scan(c, d, wfpt::RlRow{}, c->rl.rows.p, nullptr, nullptr, out_drift != nullptr,
+                       n_tables))
+    return rc;
+  wfpt::launch_rl_fill_multi(d->node_c.p, wfpt::RlTables{n_tables, nn, m, d->n}, c->rl.par.p, mask,
+                             c->rl.arr.p, c->stream);
+  HIP_TRY(hipGetLastError());
+  double* field[7] = {c->rl.drift.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int f = 1, slot = 0; f < 7; ++f)
+    if (mask & (1 << f)) field[f] = c->rl.arr.p + (int64_t)slot++ * tm;
+  if (int rc = score_runs(c, d->x_rep.p, field, tables, (int32_t)G, d->off_rep_host.data(),
+                          d->off_rep.p, c->rl.npart, K, p_outlier, out_logp))
+    return rc;
+  return rl_outputs(c, d, out_trial, out_drift, T);
+}
+
+int wfpt_wiener_like_rlddm_nodes_multi(wfpt_ctx* c, const wfpt_rl_ds* d, const double* rl_tables,
+                                       const wfpt_params* tables, int32_t n_tables,
+                                       const wfpt_knobs* k, double* out_logp) {
+  return wfpt_wiener_like_rlddm_nodes_multi_ex(c, d, rl_tables, tables, n_tables, k, out_logp,
+                                               nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -49,6 +49,20 @@ void launch_rl_scan(const RlLayout& L, const RlRow& one, const RlRow* rows,
                     const double* vmul, const double* rate, double* drift_c,
                     double* drift_in, hipStream_t s);
 
+// The shape of a multi-table node batch: n_tables row tables of n_nodes rows
+// over a dataset of n trials, m of them scored.
+struct RlTables {
+  int32_t n_tables, n_nodes;
+  int64_t m, n;
+};
+
+// launch_rl_scan with the rows of T.n_tables tables (rows[t n_nodes + node]),
+// one lane per (table, segment): table t's drifts at drift_c[t m ..] and
+// drift_in[t n ..] (nullable), each bit for bit the one-table scan's with that
+// table's rows. n_tables x n_seg must fit an int32_t.
+void launch_rl_scan_multi(const RlLayout& L, const RlTables& T, const RlRow* rows,
+                          double* drift_c, double* drift_in, hipStream_t s);
+
 // wiener_like_rl's choice probability (wfpt.pyx:210-227) of m compact trials:
 // lp[i] = log(p (1 - p_outlier) + wp_outlier), then the per-block sums into
 // part / zeros (blocks_for(m) of them, lp_sum_kernel's order) for
@@ -62,6 +76,11 @@ void launch_rl_choice(const double* drift_c, const unsigned char* resp_c, int64_
 // mask, slots counted over the set bits in rising order.
 void launch_rl_fill(const int32_t* node_c, int64_t m, const Params* P, int mask,
                     double* dst, hipStream_t s);
+
+// launch_rl_fill over T.n_tables tables: dst[slot * (n_tables m) + t m + i] =
+// field f of P[t n_nodes + node_c[i]].
+void launch_rl_fill_multi(const int32_t* node_c, const RlTables& T, const Params* P, int mask,
+                          double* dst, hipStream_t s);
 
 // res[j] = the sum of lp[off[j] .. off[j + 1]) in the order lp_sum_kernel +
 // finalize_kernel (one block) add a call's terms: bit for bit the sum of the

@@ -4,6 +4,7 @@
 //
 //   rl_scan_kernel      the Q-value recurrence, one lane per segment -> each
 //                       trial's drift (qs[1] - qs[0]) * v
+//   rl_scan_multi_kernel, rl_fill_multi_kernel  the same over several row tables
 //   rl_choice_kernel    wiener_like_rl's choice probability, one trial per lane
 //   rl_fill_kernel      node parameter rows -> per-trial arrays (node batch)
 //   rl_node_sum_kernel  per-node sums in the single-node call's order
@@ -31,14 +32,9 @@ constexpr int kRlAhead = 8;        // steps whose inputs the scan loads ahead
 // fused multiply-add whatever the contraction setting), the learning-rate
 // choice the strict feedback > q (wfpt.pyx:145). A one-ulp difference in q
 // could flip that comparison and change every later trial.
-__global__ __launch_bounds__(kRlScanBlock) void rl_scan_kernel(RlLayout L, RlRow one,
-                                                               const RlRow* rows,
-                                                               const double* vmul,
-                                                               const double* rate, double* drift_c,
-                                                               double* drift_in) {
-  const int r = blockIdx.x * kRlScanBlock + threadIdx.x;
-  if (r >= L.n_seg) return;
-  const RlRow R = rows ? rows[L.lane_node ? L.lane_node[r] : 0] : one;
+__device__ __forceinline__ void rl_scan_lane(const RlLayout& L, int r, const RlRow& R,
+                                             const double* vmul, const double* rate,
+                                             double* drift_c, double* drift_in) {
   const int64_t start = L.lane_start[r], len = L.lane_len[r];
   const int64_t out0 = L.lane_out[r] - (L.score_first ? 0 : 1);
   double q0 = R.q, q1 = R.q;  // qs[0] lower, qs[1] upper boundary (wfpt.pyx:118-119)
@@ -77,6 +73,33 @@ __global__ __launch_bounds__(kRlScanBlock) void rl_scan_kernel(RlLayout L, RlRow
       }
     }
   }
+}
+
+__global__ __launch_bounds__(kRlScanBlock) void rl_scan_kernel(RlLayout L, RlRow one,
+                                                               const RlRow* rows,
+                                                               const double* vmul,
+                                                               const double* rate, double* drift_c,
+                                                               double* drift_in) {
+  const int r = blockIdx.x * kRlScanBlock + threadIdx.x;
+  if (r >= L.n_seg) return;
+  const RlRow R = rows ? rows[L.lane_node ? L.lane_node[r] : 0] : one;
+  rl_scan_lane(L, r, R, vmul, rate, drift_c, drift_in);
+}
+
+// The same recurrence over T.n_tables row tables: lane g scans segment g %
+// n_seg with table g / n_seg's row of the segment's node, so the lanes of one
+// table read the step-major addresses the one-table scan reads, and writes
+// into that table's block of drift_c (m each) and drift_in (n each).
+__global__ __launch_bounds__(kRlScanBlock) void rl_scan_multi_kernel(RlLayout L, RlTables T,
+                                                                     const RlRow* rows,
+                                                                     double* drift_c,
+                                                                     double* drift_in) {
+  const int g = blockIdx.x * kRlScanBlock + threadIdx.x;
+  if (g >= T.n_tables * L.n_seg) return;
+  const int t = g / L.n_seg, r = g - t * L.n_seg;
+  const RlRow R = rows[(int64_t)t * T.n_nodes + L.lane_node[r]];
+  rl_scan_lane(L, r, R, nullptr, nullptr, drift_c + (int64_t)t * T.m,
+               drift_in ? drift_in + (int64_t)t * T.n : nullptr);
 }
 
 // wfpt.pyx:210-227: p = 0.5 at drift 0, else the ratio of the two
@@ -126,6 +149,26 @@ __global__ __launch_bounds__(kBlock) void rl_fill_kernel(const int32_t* node_c, 
   for (int f = 1; f < 7; ++f) {
     if (mask & (1 << f)) {
       dst[(int64_t)slot * m + i] = row[f];
+      ++slot;
+    }
+  }
+}
+
+// rl_fill_kernel over T.n_tables tables: trial i of the T.n_tables x T.m
+// takes the row of its node in table i / m.
+__global__ __launch_bounds__(kBlock) void rl_fill_multi_kernel(const int32_t* node_c, RlTables T,
+                                                                 const Params* P, int mask,
+                                                                 double* dst) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t total = (int64_t)T.n_tables * T.m;
+  if (i >= total) return;
+  const int64_t t = i / T.m;
+  const double* row = reinterpret_cast<const double*>(P + t * T.n_nodes + node_c[i - t * T.m]);
+  int slot = 0;
+#pragma unroll
+  for (int f = 1; f < 7; ++f) {
+    if (mask & (1 << f)) {
+      dst[(int64_t)slot * total + i] = row[f];
       ++slot;
     }
   }
@@ -184,6 +227,15 @@ void launch_rl_scan(const RlLayout& L, const RlRow& one, const RlRow* rows, cons
                      drift_c, drift_in);
 }
 
+void launch_rl_scan_multi(const RlLayout& L, const RlTables& T, const RlRow* rows, double* drift_c,
+                          double* drift_in, hipStream_t s) {
+  const int64_t lanes = (int64_t)T.n_tables * L.n_seg;
+  if (lanes <= 0) return;
+  const int nb = (int)((lanes + kRlScanBlock - 1) / kRlScanBlock);
+  hipLaunchKernelGGL(rl_scan_multi_kernel, dim3(nb), dim3(kRlScanBlock), 0, s, L, T, rows, drift_c,
+                     drift_in);
+}
+
 void launch_rl_choice(const double* drift_c, const unsigned char* resp_c, int64_t m, double z,
                       double p_outlier, double wp_outlier, double* lp, double* part, int* zeros,
                       hipStream_t s) {
@@ -198,6 +250,13 @@ void launch_rl_fill(const int32_t* node_c, int64_t m, const Params* P, int mask,
   const int64_t nb = (m + kBlock - 1) / kBlock;
   if (nb == 0 || (mask & 0x7e) == 0) return;
   hipLaunchKernelGGL(rl_fill_kernel, dim3(nb), dim3(kBlock), 0, s, node_c, m, P, mask, dst);
+}
+
+void launch_rl_fill_multi(const int32_t* node_c, const RlTables& T, const Params* P, int mask,
+                          double* dst, hipStream_t s) {
+  const int64_t nb = ((int64_t)T.n_tables * T.m + kBlock - 1) / kBlock;
+  if (nb == 0 || (mask & 0x7e) == 0) return;
+  hipLaunchKernelGGL(rl_fill_multi_kernel, dim3(nb), dim3(kBlock), 0, s, node_c, T, P, mask, dst);
 }
 
 static_assert(kBlock == 256, "rl_node_partials (rl_internal.h) counts 256-trial blocks");

@@ -52,8 +52,11 @@ _COL = {"v": 0, "sv": 1, "a": 2, "z": 3, "sz": 4, "t": 5, "st": 6, "p_outlier": 
 # so the scalar fast paths of the densities see what they always saw.
 # group_prior: of the group mean; subject: density kind of the subject nodes
 # around it (gamma by mean and sd); std_sd: sd of the HalfNormal prior of the
-# std node; start: (group, subject, std); widths: slice width (value, std)
-Family = namedtuple("Family", "group_prior subject std_sd start lower widths")
+# std node; start: (group, subject, std); widths: slice width (value, std);
+# std_prior: the std node's density when it is not that HalfNormal (rl.py's
+# learning-rate families: Uniform, base.py:310-369), else None
+Family = namedtuple("Family", "group_prior subject std_sd start lower widths std_prior",
+                    defaults=(None,))
 Inter = namedtuple("Inter", "prior start width")  # start: when included, else 0
 MODEL = {  # priors and starting values hddm_info.py:121-140, widths hddm_info.py:103-105
     "a": Family(("gamma", 1.5, 0.75), "gamma", 2.0, (1.5, 1.0, 0.1), 0.0, (1, 1)),
@@ -65,9 +68,21 @@ INTER = {
     "sz": Inter(("beta", 1, 3), 0.01, 1.1),
     "st": Inter(("halfnormal", 0.3), 0.001, 0.1),
 }
-SLICE_WIDTHS = {**{f: s.widths[0] for f, s in MODEL.items()},
-                **{f + "_std": s.widths[1] for f, s in MODEL.items()},
-                **{n: s.width for n, s in INTER.items()}}
+
+
+def slice_widths(model):
+    """{node name: slice width} of a family table and INTER."""
+    return {**{f: s.widths[0] for f, s in model.items()},
+            **{f + "_std": s.widths[1] for f, s in model.items()},
+            **{n: s.width for n, s in INTER.items()}}
+
+
+def std_density(spec):
+    """The (kind, *parameters) density of a family's std node."""
+    return spec.std_prior or ("halfnormal", spec.std_sd)
+
+
+SLICE_WIDTHS = slice_widths(MODEL)
 
 
 def param_table(shape, cols, p_outlier):
@@ -118,8 +133,14 @@ def beta_logpdf(x, a, b):
     return np.where((x > 0) & (x < 1), out, -np.inf)
 
 
+def uniform_logpdf(x, lower, upper):
+    """pm.Uniform(lower, upper): -log(upper - lower) inside [lower, upper]."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where((x >= lower) & (x <= upper), -math.log(upper - lower), -np.inf)
+
+
 LOGPDF = {"gamma": gamma_logpdf_mean_sd, "normal": normal_logpdf, "halfnormal": halfnormal_logpdf,
-          "beta": beta_logpdf}
+          "beta": beta_logpdf, "uniform": uniform_logpdf}
 
 
 def logpdf(density, x):
@@ -247,6 +268,9 @@ class HDDM:
     """
 
     FAMILIES = ("a", "v", "t")
+    # the family table and slice widths the methods below read (a subclass
+    # with further families merges its own into them: rl.py)
+    MODEL, SLICE_WIDTHS = MODEL, SLICE_WIDTHS
     _COL = _COL
     _trace_shape, _progress_note = (-1,), ""  # HDDMChains: (-1, C), " (C chains)"
 
@@ -320,9 +344,9 @@ class HDDM:
     def _init_values(self):
         """Starting values of hddm_info.py:121-140."""
         fams = self.FAMILIES
-        self.group = {f: np.full(len(self.levels[f]), MODEL[f].start[0]) for f in fams}
-        self.subj = {f: np.full(self.n_units[f], MODEL[f].start[1]) for f in fams}
-        self.std = {f: MODEL[f].start[2] for f in fams}
+        self.group = {f: np.full(len(self.levels[f]), self.MODEL[f].start[0]) for f in fams}
+        self.subj = {f: np.full(self.n_units[f], self.MODEL[f].start[1]) for f in fams}
+        self.std = {f: self.MODEL[f].start[2] for f in fams}
         self.inter = {n: s.start if n in self.include else 0.0 for n, s in INTER.items()}
 
     def group_nodes(self):
@@ -392,24 +416,25 @@ class HDDM:
         return self.group[fam][np.arange(self.n_units[fam]) % len(self.levels[fam])]
 
     def subj_prior(self, fam, x):
-        return LOGPDF[MODEL[fam].subject](x, self._unit_group(fam), self.std[fam])
+        return LOGPDF[self.MODEL[fam].subject](x, self._unit_group(fam), self.std[fam])
 
     def logp(self):
         """Joint log density of the model at the current values."""
         lp = float(np.sum(self.node_logp()))
         for fam in self.FAMILIES:
             lp += float(np.sum(self.subj_prior(fam, self.subj[fam])))
-        for fam in ("a", "t", "v"):  # the order these terms have always been summed in
+        # a, t, v: the order these terms have always been summed in
+        for fam in ("a", "t", "v") + tuple(f for f in self.FAMILIES if f not in MODEL):
             lp += float(np.sum(self._group_prior(fam, self.group[fam])))
-        lp += float(np.sum([halfnormal_logpdf(self.std[f], MODEL[f].std_sd)
+        lp += float(np.sum([logpdf(std_density(self.MODEL[f]), self.std[f])
                             for f in self.FAMILIES]))
         for name in self.inter_names:
             lp += float(logpdf(INTER[name].prior, self.inter[name]))
         return lp
 
-    @staticmethod
-    def _group_prior(fam, x):
-        return logpdf(MODEL[fam].group_prior, x)
+    @classmethod
+    def _group_prior(cls, fam, x):
+        return logpdf(cls.MODEL[fam].group_prior, x)
 
     # -- updates ---------------------------------------------------------------
     def _update_subject(self, fam):
@@ -425,14 +450,14 @@ class HDDM:
             return (np.bincount(unit, weights=r[0], minlength=nu) + self.subj_prior(fam, xl),
                     np.bincount(unit, weights=r[1], minlength=nu) + self.subj_prior(fam, xr))
 
-        self.subj[fam], _ = slice_step(self.subj[fam], logp, SLICE_WIDTHS[fam], self.rng,
-                                       lower=MODEL[fam].lower,
+        self.subj[fam], _ = slice_step(self.subj[fam], logp, self.SLICE_WIDTHS[fam], self.rng,
+                                       lower=self.MODEL[fam].lower,
                                        logp_pair=logp_pair if self.paired_probes else None)
 
     def _update_group(self, fam):
         nl = len(self.levels[fam])
         lv = np.arange(self.n_units[fam]) % nl
-        spec = MODEL[fam]
+        spec = self.MODEL[fam]
         if spec.subject == "normal":  # kNormalNormal: conjugate Normal mean (hddm_info.py:167-168)
             _, mu0, sd0 = spec.group_prior
             tau0 = sd0 ** -2
@@ -449,18 +474,22 @@ class HDDM:
                     out[k] += np.sum(gamma_logpdf_mean_sd(self.subj[fam][lv == k], g[k],
                                                           self.std[fam]))
                 return out
-            self.group[fam], _ = slice_step(self.group[fam], logp, SLICE_WIDTHS[fam], self.rng,
-                                            lower=spec.lower)
+            self.group[fam], _ = slice_step(self.group[fam], logp, self.SLICE_WIDTHS[fam],
+                                            self.rng, lower=spec.lower)
         subject = LOGPDF[spec.subject]
+        std_prior = std_density(spec)
 
         def logp_std(s):
             s = float(s[0])
             if s <= 0:
                 return np.array([-np.inf])
+            pr = float(logpdf(std_prior, s))
+            if pr == -np.inf:  # outside a bounded prior's support (Uniform)
+                return np.array([-np.inf])
             ll = subject(self.subj[fam], self._unit_group(fam), s)
-            return np.array([float(halfnormal_logpdf(s, spec.std_sd)) + float(np.sum(ll))])
+            return np.array([pr + float(np.sum(ll))])
 
-        new, _ = slice_step(np.array([self.std[fam]]), logp_std, SLICE_WIDTHS[fam + "_std"],
+        new, _ = slice_step(np.array([self.std[fam]]), logp_std, self.SLICE_WIDTHS[fam + "_std"],
                             self.rng, lower=0.0)
         self.std[fam] = float(new[0])
 

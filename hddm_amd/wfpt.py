@@ -50,7 +50,8 @@ __all__ = ["pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "wiener_
            "gen_rts_from_cdf", "gen_rts_from_cdf_nodes", "gen_rts_from_drift_nodes",
            "gen_rts_from_drift", "rt_stats_rows", "rt_stats_names", "gen_rts_stats_nodes",
            "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl", "wiener_like_multi_rlddm",
-           "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_terms",
+           "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_nodes_multi",
+           "wiener_like_rlddm_terms",
            "wiener_like_rl_terms", "wiener_like_multi_rlddm_terms", "RegDataset"]
 
 
@@ -930,6 +931,30 @@ class RLDataset(_Resident):
             ctypes.byref(K), _lib.dptr(out), ptr, pdr))
         return (out, tr, dr) if terms else out
 
+    def wiener_like_rlddm_nodes_multi(self, rl_tables, params, err=1e-4, n_st=2, n_sz=2,
+                                      use_adaptive=1, simps_err=1e-3, w_outlier=0.1, terms=False):
+        """wiener_like_rlddm_nodes for T row tables in ONE call (both probes of
+        a slice step): rl_tables (T, n_nodes, 3), params (T, n_nodes, 8), one
+        p_outlier throughout. Returns the (T, n_nodes) sums, row t bit for bit
+        the one-table call's on table t; terms=True: (sums, (T, n) per-trial
+        terms, (T, n) drifts)."""
+        if self.n_nodes == 0:
+            raise ValueError("dataset was created without node ids")
+        rr = np.ascontiguousarray(rl_tables, dtype=np.float64)
+        pm = np.ascontiguousarray(params, dtype=np.float64)
+        if rr.ndim != 3 or rr.shape[0] < 1 or rr.shape[1:] != (self.n_nodes, 3):
+            raise ValueError(f"rl_tables must have shape (T, {self.n_nodes}, 3) with T >= 1")
+        T = rr.shape[0]
+        if pm.shape != (T, self.n_nodes, 8):
+            raise ValueError(f"params must have shape ({T}, {self.n_nodes}, 8)")
+        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        out = np.empty((T, self.n_nodes), dtype=np.float64)
+        tr, dr, ptr, pdr = _rl_outputs((T, self.n), terms)
+        _lib.check(_lib.wfpt_wiener_like_rlddm_nodes_multi_ex(
+            self.ctx.handle, self.handle, _lib.dptr(rr), pm.ctypes.data_as(_lib._PP), T,
+            ctypes.byref(K), _lib.dptr(out), ptr, pdr))
+        return (out, tr, dr) if terms else out
+
 
 # ---------------------------------------------------------------------------
 # Regression likelihoods (hddm/models/hddm_regression.py:26-36)
@@ -1136,3 +1161,10 @@ def wiener_like_rlddm_nodes(ds, rl_rows, params, err=1e-4, n_st=2, n_sz=2, use_a
     """RLDataset.wiener_like_rlddm_nodes as a module function."""
     return ds.wiener_like_rlddm_nodes(rl_rows, params, err, n_st, n_sz, use_adaptive, simps_err,
                                       w_outlier, terms)
+
+
+def wiener_like_rlddm_nodes_multi(ds, rl_tables, params, err=1e-4, n_st=2, n_sz=2, use_adaptive=1,
+                                  simps_err=1e-3, w_outlier=0.1, terms=False):
+    """RLDataset.wiener_like_rlddm_nodes_multi as a module function."""
+    return ds.wiener_like_rlddm_nodes_multi(rl_tables, params, err, n_st, n_sz, use_adaptive,
+                                            simps_err, w_outlier, terms)

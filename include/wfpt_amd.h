@@ -183,6 +183,7 @@ int wfpt_wiener_like_multi_resident_ex(wfpt_ctx *ctx, const wfpt_ds *ds,
  *   wfpt_wiener_like_rl*          <- wfpt.wiener_like_rl          src/wfpt.pyx:157-241
  *   wfpt_wiener_like_multi_rlddm* <- wfpt.wiener_like_multi_rlddm src/wfpt.pyx:277-320
  *   wfpt_wiener_like_rlddm_nodes* <- one wiener_like_rlddm per node, batched
+ *   wfpt_wiener_like_rlddm_nodes_multi* <- ... for several row tables at once
  * The recurrence runs on the device bit for bit as the reference computes it
  * (learning rates pow(2.718281828459, alpha) / (1 + pow(2.718281828459,
  * alpha)) from the host's libm; q + alfa * (f - q) in three roundings; strict
@@ -264,6 +265,29 @@ int wfpt_wiener_like_rlddm_nodes(wfpt_ctx *ctx, const wfpt_rl_ds *ds, const doub
 int wfpt_wiener_like_rlddm_nodes_ex(wfpt_ctx *ctx, const wfpt_rl_ds *ds, const double *rl_rows,
                                     const wfpt_params *per_node, const wfpt_knobs *k,
                                     double *out_logp, double *out_trial, double *out_drift);
+/* n_tables evaluations of wienerRL_like per node (hddm/models/hddm_rl.py:61-73)
+ * in one call: the node batch above over n_tables row tables, e.g. both
+ * stepping-out probes of a slice step. rl_tables[3 (t n_nodes + j) ..] = (q,
+ * alpha, pos_alpha) of node j in table t, tables[t n_nodes + j] its DDM row,
+ * out_logp[t n_nodes + j] its sum. out_trial / out_drift (nullable): n_tables
+ * x n values, table t's at [t n + i] in the caller's order. Row t of every
+ * output is bit for bit what wfpt_wiener_like_rlddm_nodes_ex returns for
+ * table t alone. When every row of every table shares sz and st the call makes
+ * the one-table call's launches, each over n_tables times the work (one scan
+ * over n_tables x segments lanes, one fill, one scoring pass, one per-node
+ * sum, one finalize, one wait); otherwise the scoring pass splits into runs of
+ * consecutive (table, node) rows that share them. WFPT_ERR_ARG: a null
+ * pointer, n_tables < 1, a dataset without node ids. WFPT_ERR_UNSUPPORTED: a
+ * p_outlier that differs anywhere across rows or tables, a node of more than
+ * 2^22 scored trials, n_tables x segments (or scored trials) beyond 2^31 - 1.
+ * A p_outlier outside [0, 1] sets every sum to -inf. */
+int wfpt_wiener_like_rlddm_nodes_multi(wfpt_ctx *ctx, const wfpt_rl_ds *ds,
+                                       const double *rl_tables, const wfpt_params *tables,
+                                       int32_t n_tables, const wfpt_knobs *k, double *out_logp);
+int wfpt_wiener_like_rlddm_nodes_multi_ex(wfpt_ctx *ctx, const wfpt_rl_ds *ds,
+                                          const double *rl_tables, const wfpt_params *tables,
+                                          int32_t n_tables, const wfpt_knobs *k, double *out_logp,
+                                          double *out_trial, double *out_drift);
 
 /* ---- regression likelihoods (HDDMRegressor) ------------------------------ */
 /* The reference's regression node (hddm/models/hddm_regression.py:26-36,

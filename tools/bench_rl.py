@@ -4,6 +4,8 @@ existed without them.
   1. resident `RLDataset.wiener_like_rlddm`: one node, 4 conditions x 75
      trials, full DDM, HDDM's knobs;
   2. `RLDataset.wiener_like_rlddm_nodes`: 40 copies of that node in one call;
+     twice in a row, and `wiener_like_rlddm_nodes_multi` with T = 2 tables on
+     the same data set (both stepping-out probes of a slice step in one call);
   3. emulation: the Q recurrence as a Python loop, then
      `Dataset.wiener_like_multi(multi=['v'])` on a resident input-order dataset
      of the scored trials (a Python loop plus an n-double upload per call).
@@ -113,6 +115,15 @@ def main():
                               [KNOBS["p_outlier"]]), (m, 1))
     nk = dict(err=ERR, n_st=2, n_sz=2, use_adaptive=1, simps_err=1e-3, w_outlier=0.1)
     call2 = lambda: batch.wiener_like_rlddm_nodes(rows, params, **nk)
+    # two probes of a slice step: two one-table calls, or one two-table call
+    rows2 = np.stack([rows, rows + np.array([0.0, 0.3, 0.0])])
+    params2 = np.stack([params, params])
+
+    def call2_twice():
+        return np.stack([batch.wiener_like_rlddm_nodes(rows2[0], params2[0], **nk),
+                         batch.wiener_like_rlddm_nodes(rows2[1], params2[1], **nk)])
+
+    call2_multi = lambda: batch.wiener_like_rlddm_nodes_multi(rows2, params2, **nk)
 
     _, scored = python_drift(response, feedback, split_by, *ROW, DDM["v"])
     emu = wfpt.Dataset(x[scored], input_order=True)
@@ -124,10 +135,14 @@ def main():
 
     v1, v2, v3 = call1(), call2(), call3()
     same = bool(np.all(v2 == v1))
+    multi_same = bool(np.array_equal(call2_multi(), call2_twice()))
     out = {"build": hb.built_digest(_lib.LIB_PATH), "source": hb.source_digest(),
            "trials_per_node": int(x.size), "nodes": m, "seconds": a.seconds,
-           "logp": {"resident": v1, "emulated": v3, "batch_equals_resident": same}, "rows": []}
+           "logp": {"resident": v1, "emulated": v3, "batch_equals_resident": same,
+                    "multi_equals_two_calls": multi_same}, "rows": []}
     for name, call in (("resident_rlddm_1_node", call1), (f"node_batch_{m}_nodes", call2),
+                       (f"node_batch_{m}_nodes_two_calls", call2_twice),
+                       (f"node_batch_multi_{m}_nodes_T2", call2_multi),
                        ("python_scan_plus_multi", call3)):
         ms, reps = timed(call, a.seconds)
         out["rows"].append({"call": name, "call_ms": ms, "repeats": reps,

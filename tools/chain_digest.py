@@ -4,10 +4,11 @@
     python tools/chain_digest.py > after.jsonl     # on the branch
     cmp before.jsonl after.jsonl
 
-Each model's chain is a function of its seed. This tool runs HDDM, HDDMChains
-and HDDMRegressor over the oracle-backed stand-ins of the resident data sets
-that the tests define (tests/test_hierarchical.py::_OracleDataset,
-tests/test_regressor.py::_OracleRegDataset), so it needs no GPU, and prints one
+Each model's chain is a function of its seed. This tool runs HDDM, HDDMChains,
+HDDMRegressor and HDDMrl over the oracle-backed stand-ins of the resident data
+sets that the tests define (tests/test_hierarchical.py::_OracleDataset,
+tests/test_regressor.py::_OracleRegDataset, tests/test_hddmrl.py::_OracleRLDataset),
+so it needs no GPU, and prints one
 JSON line per model: the trace keys in order, the number of likelihood calls
 and a SHA-256 over the traces, the subject traces, the generator's state after
 sampling, the call_stats keys with their counts and logp() at the final state
@@ -75,6 +76,16 @@ def main():
                          reg_data, tr.MODELS, include=("st",), group_only_regressors=group_only,
                          seed=0),
                      dict(iter=5, burn=1)))
+    import test_hddmrl as trl
+    from hddm_amd import rl
+    rl._wfpt.RLDataset = trl._OracleRLDataset
+    rl_data, _ = trl._cpu_data()
+    rl_runs = [dict(dual=dual, paired_probes=paired) for dual in (False, True)
+               for paired in (True, False)] + [dict(include=("sz", "st"))]
+    for kw in rl_runs:
+        runs.append(("HDDMrl " + " ".join(f"{k}={list(v) if k == 'include' else v}"
+                                          for k, v in kw.items()),
+                     lambda kw=kw: rl.HDDMrl(rl_data, seed=0, **kw), dict(iter=5, burn=1)))
     for name, make, how in runs:
         m = make()
         m.sample(**how)
