@@ -56,6 +56,12 @@ class Knobs(ctypes.Structure):
                 ("simps_err", _D), ("w_outlier", _D)]
 
 
+class RlSource(ctypes.Structure):
+    """wfpt_rl_source: the closed-loop simulator's reward source (addresses)."""
+    _fields_ = [(n, _VP) for n in ("p", "rew_up", "rew_low", "obs_response", "obs_feedback",
+                                   "start")] + [("n", _I64)]
+
+
 class RegTerm(ctypes.Structure):
     _fields_ = [(n, _I32) for n in ("param", "link", "col0", "ncol")]
 
@@ -70,6 +76,7 @@ _PVP = ctypes.POINTER(_VP)
 _PP = ctypes.POINTER(Params)
 _PK = ctypes.POINTER(Knobs)
 _PT = ctypes.POINTER(RegTerm)
+_PS = ctypes.POINTER(RlSource)
 
 # Every entry point of include/wfpt_amd.h: name -> (restype, argtypes). Each
 # becomes a module attribute below, and EXPORTED is this table's names.
@@ -79,6 +86,7 @@ _RL_HOST = [_VP, _PD, _PI64, _PD, _PI64, _I64, _D]  # ctx, rt, response, feedbac
 _REG = [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD]  # ctx, ds, terms, n_terms, coef, params, ...
 _GEN_CDF = [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD]
 _GEN_DRIFT = [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64]
+_GEN_RLDDM = [_VP, _PP, _PD, _I64, _PI64, _PS, _D, _D, _I64, _U64]
 _SIGNATURES = {
     "wfpt_last_error": (_CP, []),
     "wfpt_device_count": (_I, [_PI]),
@@ -157,6 +165,10 @@ _SIGNATURES = {
     "wfpt_gen_rts_drift_nodes_ex": (_I, _GEN_DRIFT + [_I64, _I32, _PD, _PI64, _PD, _PD, _PD, _PD,
                                                       _PI64, _PI64]),
     "wfpt_gen_rts_drift_nodes_stats": (_I, _GEN_DRIFT + [_PD, _PI64, _PD, _I32, _PD]),
+    "wfpt_gen_rlddm_rows": (_I, _GEN_RLDDM + [_PD, _PI64]),
+    "wfpt_gen_rlddm_rows_ex": (_I, _GEN_RLDDM + [_I64, _I32, _PD, _PI64] + [_PD] * 7
+                               + [_PI64, _PI64]),
+    "wfpt_gen_rlddm_rows_stats": (_I, _GEN_RLDDM + [_PD, _PI64, _PI64, _I64, _PD, _I32, _PD]),
     "wfpt_rt_stats_rows": (_I, [_VP, _PD, _PI64, _I64, _PD, _I32, _PD]),
     "wfpt_rt_stats_rows_ex": (_I, [_VP, _PD, _PI64, _I64, _PD, _I32, _I32, _PD]),
 }

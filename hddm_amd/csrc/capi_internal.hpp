@@ -28,6 +28,7 @@
 namespace wfpt {
 struct RlRow;     // rl_internal.h
 struct DriftRow;  // sim_internal.h
+struct RlSimRow;  // sim_internal.h
 
 namespace capi {
 
@@ -182,6 +183,9 @@ struct SimWork {
   DevBuf<Params> rows;
   DevBuf<int64_t> off, idx;
   DevBuf<DriftRow> drift_rows;  // the diffusion-path simulator's row table
+  DevBuf<RlSimRow> rl_rows;     // the closed-loop RLDDM simulator's row table,
+  DevBuf<double> rl_in;         // its supplied rewards / observed feedback,
+  DevBuf<int64_t> rl_idx;       // observed responses and the statistics' group offsets
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   double ms[4] = {0, 0, 0, 0};  // profiled time by stage: density, scan, normalise, draws
   ~SimWork() {
@@ -408,6 +412,9 @@ int score_runs(wfpt_ctx* c, const double* dx, double* const field[7], const wfpt
 // is "<name>: negative count in row r".
 int counts_to_offsets(const char* name, const int64_t* counts, int64_t R,
                       std::vector<int64_t>* off);
+// The learning rate of the unbounded alpha as every RL entry forms it
+// (wfpt.pyx:123-125), defined in capi_rl.cpp.
+double rl_rate(double alpha);
 
 }  // namespace capi
 }  // namespace wfpt

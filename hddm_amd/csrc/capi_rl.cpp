@@ -149,18 +149,17 @@ RlHostLayout rl_layout_host(const double* rt, const int64_t* response, const dou
   return H;
 }
 
+// (2.718281828459**alpha) / (1 + 2.718281828459**alpha), libm pow (wfpt.pyx:123-125)
+double rl_rate(double alpha) {
+  constexpr double kRlBase = 2.718281828459;  // the reference's literal (wfpt.pyx:123)
+  const double e = std::pow(kRlBase, alpha);
+  return e / (1 + e);
+}
+
 }  // namespace capi
 }  // namespace wfpt
 
 namespace {
-
-constexpr double kRlBase = 2.718281828459;  // the reference's literal (wfpt.pyx:123)
-
-// (2.718281828459**alpha) / (1 + 2.718281828459**alpha), libm pow (wfpt.pyx:123-125)
-double rl_rate(double alpha) {
-  const double e = std::pow(kRlBase, alpha);
-  return e / (1 + e);
-}
 
 // Lays the trials out (rl_layout_host) and uploads them (context locked by the
 // caller). The dataset is not registered: a resident one is by its entry point.

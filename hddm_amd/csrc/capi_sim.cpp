@@ -1,6 +1,7 @@
 // capi_sim.cpp — the samplers of the C ABI (include/wfpt_amd.h): the batched
 // inverse-CDF RT sampler and the diffusion-path simulator (sim_kernels.hip),
-// and the per-row RT statistics (stats_kernels.hip) alone or fused onto either.
+// the closed-loop RLDDM simulator (rl_sim_kernels.hip), and the per-row RT
+// statistics (stats_kernels.hip) alone or fused onto any of them.
 #include "capi_internal.hpp"
 #include "sim_internal.h"
 #include "stats_internal.h"
@@ -292,6 +293,15 @@ int gen_rts_nodes_impl(wfpt_ctx* c, const double* grid, int64_t G, const wfpt_pa
 // ---------------------------------------------------------------------------
 // Diffusion-path simulator (sim_drift_kernel; hddm/generate.py:208-319)
 
+// What a walk needs of a parameter row (generate.py:245-253: the start point
+// lies between the boundaries).
+bool walk_row_ok(const wfpt_params& P) {
+  const bool finite = std::isfinite(P.v) && std::isfinite(P.sv) && std::isfinite(P.a) &&
+                      std::isfinite(P.z) && std::isfinite(P.sz) && std::isfinite(P.t) &&
+                      std::isfinite(P.st);
+  return finite && P.a > 0 && !(P.z - P.sz / 2. < 0) && !(P.z + P.sz / 2. > 1);
+}
+
 int gen_rts_drift_nodes_impl(wfpt_ctx* c, const wfpt_params* rows, int64_t R, const double* sw,
                              const int64_t* counts, double dt, double intra_sv,
                              int64_t max_steps, uint64_t seed, int64_t row0, int32_t wave_draws,
@@ -346,11 +356,7 @@ int gen_rts_drift_nodes_impl(wfpt_ctx* c, const wfpt_params* rows, int64_t R, co
   if (!c) return fail(WFPT_ERR_ARG, "null pointer (context)");
   for (int64_t r = 0; r < R; ++r) {
     const wfpt::DriftRow& Q = tab[r];
-    const bool finite = std::isfinite(Q.v) && std::isfinite(Q.sv) && std::isfinite(Q.a) &&
-                        std::isfinite(Q.z) && std::isfinite(Q.sz) && std::isfinite(Q.t) &&
-                        std::isfinite(Q.st) && std::isfinite(Q.v_switch) &&
-                        std::isfinite(Q.V_switch);
-    if (!finite || !(Q.a > 0) || Q.z - Q.sz / 2. < 0 || Q.z + Q.sz / 2. > 1)
+    if (!walk_row_ok(rows[r]) || !std::isfinite(Q.v_switch) || !std::isfinite(Q.V_switch))
       return fail(WFPT_ERR_UNSUPPORTED,
                   "gen_rts_drift_nodes: row " + std::to_string(r) +
                       " cannot be simulated (a non-finite parameter, a <= 0, or a start "
@@ -444,6 +450,225 @@ int gen_rts_drift_nodes_impl(wfpt_ctx* c, const wfpt_params* rows, int64_t R, co
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   int64_t nan = (int64_t)nan_dev;  // only a draw that ran out of steps is NaN
+  if (out)
+    for (int64_t i = 0; i < total; ++i) nan += std::isnan(out[i]) ? 1 : 0;
+  *n_unfinished = nan;
+  return WFPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Closed-loop RLDDM simulator (rl_sim_kernel; hddm/generate.py:430-516, 608-661)
+
+struct RlSimDebug {
+  double *feedback, *q_up, *q_low, *sim_drift, *drift, *y0, *delay;
+  int64_t *n_steps, *wave_steps;
+};
+// The statistics rows of a fused call: groups of consecutive sequence rows.
+struct RlSimGroups {
+  const int64_t* off;
+  int64_t n;
+};
+
+int gen_rlddm_rows_impl(wfpt_ctx* c, const wfpt_params* rows, const double* rl_rows, int64_t R,
+                        const int64_t* counts, const wfpt_rl_source* src, double dt,
+                        double intra_sv, int64_t max_steps, uint64_t seed, int64_t row0,
+                        int32_t wave_rows, double* out, int64_t* n_unfinished,
+                        const RlSimDebug& D, const RlSimGroups* G, const StatsReq* sr) {
+  const std::string name = "gen_rlddm_rows";
+  if (!rows || !rl_rows || !counts || !src || !n_unfinished)
+    return fail(WFPT_ERR_ARG, "null pointer (rows / rl_rows / counts / source / n_unfinished)");
+  if (R < 1) return fail(WFPT_ERR_ARG, name + ": R < 1");
+  if (row0 < 0 || R > ((int64_t)1 << 31) || row0 > ((int64_t)1 << 31) - R)
+    return fail(WFPT_ERR_ARG, name + ": row0 + R must lie in [1, 2^31]");
+  if (!(dt > 0) || !std::isfinite(dt)) return fail(WFPT_ERR_ARG, name + ": dt <= 0");
+  if (!(intra_sv > 0) || !std::isfinite(intra_sv))
+    return fail(WFPT_ERR_ARG, name + ": intra_sv <= 0");
+  if (max_steps < 1 || max_steps > (int64_t)1 << 31)
+    return fail(WFPT_ERR_ARG, name + ": max_steps outside [1, 2^31]");
+  if (wave_rows < 0 || wave_rows % 64 != 0)
+    return fail(WFPT_ERR_ARG, name + ": wave_rows must be a multiple of 64 (0: default)");
+  if (D.wave_steps && wave_rows == 0)
+    return fail(WFPT_ERR_ARG, name + ": out_wave_steps needs an explicit wave_rows");
+  const double root = std::sqrt(dt);
+  const double step = root * intra_sv, scale = root / intra_sv;  // generate.py:258, 279
+  if (!(step > 0) || !std::isfinite(step) || !std::isfinite(scale))
+    return fail(WFPT_ERR_ARG, name + ": sqrt(dt) * intra_sv is not a usable step");
+  std::vector<int64_t> off;
+  if (int rc = counts_to_offsets(name.c_str(), counts, R, &off)) return rc;
+  const int64_t total = off[R];
+  if (!out && total > 0 && !sr) return fail(WFPT_ERR_ARG, "null pointer (out)");
+  // the reward source
+  const bool has_rew = src->rew_up || src->rew_low, has_obs = src->obs_response || src->obs_feedback;
+  if ((src->p ? 1 : 0) + (has_rew ? 1 : 0) + (has_obs ? 1 : 0) != 1)
+    return fail(WFPT_ERR_ARG, name + ": exactly one reward source (p, rew_up / rew_low or "
+                                     "obs_response / obs_feedback) must be given");
+  if ((has_rew && (!src->rew_up || !src->rew_low)) ||
+      (has_obs && (!src->obs_response || !src->obs_feedback)))
+    return fail(WFPT_ERR_ARG, name + ": null pointer (one array of the reward source's pair)");
+  const int32_t source = src->p ? wfpt::kRlSimBernoulli
+                                : has_rew ? wfpt::kRlSimSupplied : wfpt::kRlSimObserved;
+  if (source != wfpt::kRlSimBernoulli) {
+    if (src->n < 0) return fail(WFPT_ERR_ARG, name + ": negative length of the source arrays");
+    for (int64_t r = 0; r < R; ++r) {
+      const int64_t s0 = src->start ? src->start[r] : off[r];
+      if (s0 < 0 || s0 > src->n || counts[r] > src->n - s0)
+        return fail(WFPT_ERR_ARG, name + ": row " + std::to_string(r) + " reads [" +
+                                      std::to_string(s0) + ", +" + std::to_string(counts[r]) +
+                                      ") of source arrays of " + std::to_string(src->n));
+    }
+  }
+  std::vector<wfpt::RlSimRow> tab((size_t)R);
+  for (int64_t r = 0; r < R; ++r) {
+    const wfpt_params& P = rows[r];
+    const double q = rl_rows[3 * r], alpha = rl_rows[3 * r + 1], pos_alpha = rl_rows[3 * r + 2];
+    wfpt::RlSimRow& Q = tab[r];
+    Q = wfpt::RlSimRow{P.v, P.sv, P.a, P.z, P.sz, P.t, P.st, q, 0.0, 0.0, 0.0, 0.0, 0};
+    Q.alfa = rl_rate(alpha);
+    Q.pos_alfa = pos_alpha == 100.00 ? Q.alfa : rl_rate(pos_alpha);  // wfpt.pyx:105-108
+    if (std::isnan(q) || std::isnan(Q.alfa) || std::isnan(Q.pos_alfa))
+      return fail(WFPT_ERR_ARG, name + ": NaN in RL row " + std::to_string(r) +
+                                    " (q, or a learning rate that is NaN)");
+    if (source == wfpt::kRlSimBernoulli) {
+      Q.p_up = src->p[2 * r];
+      Q.p_low = src->p[2 * r + 1];
+      if (!(Q.p_up >= 0 && Q.p_up <= 1) || !(Q.p_low >= 0 && Q.p_low <= 1))
+        return fail(WFPT_ERR_ARG, name + ": reward probability outside [0, 1] in row " +
+                                      std::to_string(r));
+    } else {
+      Q.src = src->start ? src->start[r] : off[r];
+    }
+  }
+  StatsPlan plan;
+  std::vector<int64_t> goff;  // the groups' offsets into the trials
+  if (sr) {
+    if (int rc = stats_check_q("gen_rlddm_rows_stats", sr->q, sr->nq, sr->out)) return rc;
+    if (!G || !G->off) return fail(WFPT_ERR_ARG, "null pointer (group_off)");
+    if (G->n < 1 || G->n >= (int64_t)1 << 31)
+      return fail(WFPT_ERR_ARG, name + "_stats: n_groups outside [1, 2^31)");
+    if (G->off[0] != 0 || G->off[G->n] != R)
+      return fail(WFPT_ERR_ARG, name + "_stats: group_off must run from 0 to R");
+    goff.resize((size_t)G->n + 1);
+    for (int64_t g = 0; g <= G->n; ++g) {
+      if (g > 0 && G->off[g] < G->off[g - 1])
+        return fail(WFPT_ERR_ARG, name + "_stats: group_off falls at group " + std::to_string(g - 1));
+      if (G->off[g] < 0 || G->off[g] > R)
+        return fail(WFPT_ERR_ARG, name + "_stats: group_off outside [0, R]");
+      goff[g] = off[G->off[g]];
+    }
+    if (int rc = stats_plan("gen_rlddm_rows_stats", goff.data(), G->n, sr->q, sr->nq, 0, &plan))
+      return rc;
+  }
+  for (int64_t r = 0; r < R; ++r)
+    if (!walk_row_ok(rows[r]))
+      return fail(WFPT_ERR_UNSUPPORTED,
+                  name + ": row " + std::to_string(r) +
+                      " cannot be simulated (a non-finite parameter, a <= 0, or a start "
+                      "point outside [0, 1]); no draws are returned");
+  if (!c) return fail(WFPT_ERR_ARG, "null pointer (context)");
+  // Rows per wave: one per lane until that gives every SIMD four waves, then
+  // up to 16 per lane, taken in turn as rows end (gen_rts_drift_nodes' rule).
+  const int64_t wd = wave_rows > 0 ? wave_rows
+                                   : 64 * std::min<int64_t>(16, std::max<int64_t>(1, R / (64 * 4096)));
+  const int64_t waves = (R + wd - 1) / wd;
+  *n_unfinished = 0;
+  if (total == 0 && !sr) return WFPT_OK;
+  WFPT_RANGE("wfpt_gen_rlddm_rows");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const bool dbg = D.feedback || D.q_up || D.q_low || D.sim_drift || D.drift || D.y0 || D.delay;
+  const int64_t n_in = source == wfpt::kRlSimBernoulli ? 0 : src->n;
+  const int64_t n_obs = source == wfpt::kRlSimObserved ? n_in : 0;
+  HIP_TRY(c->sim.rl_rows.reserve(R));
+  HIP_TRY(c->sim.off.reserve(R + 1));
+  HIP_TRY(c->sim.out.reserve(std::max<int64_t>(total, 1)));
+  HIP_TRY(c->sim.rl_in.reserve(std::max<int64_t>(2 * n_in, 1)));
+  HIP_TRY(c->sim.rl_idx.reserve(n_obs + (int64_t)goff.size() + 1));
+  if (dbg) HIP_TRY(c->sim.u.reserve(std::max<int64_t>(7 * total, 1)));
+  if (D.n_steps || D.wave_steps) HIP_TRY(c->sim.idx.reserve(total + waves));
+  HIP_TRY(hipMemcpyAsync(c->sim.rl_rows.p, tab.data(), R * sizeof(wfpt::RlSimRow),
+                         hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->sim.off.p, off.data(), (R + 1) * sizeof(int64_t),
+                         hipMemcpyHostToDevice, c->stream));
+  if (n_in > 0) {
+    const double* first = source == wfpt::kRlSimSupplied ? src->rew_up : src->obs_feedback;
+    HIP_TRY(hipMemcpyAsync(c->sim.rl_in.p, first, n_in * sizeof(double), hipMemcpyHostToDevice,
+                           c->stream));
+    if (source == wfpt::kRlSimSupplied)
+      HIP_TRY(hipMemcpyAsync(c->sim.rl_in.p + n_in, src->rew_low, n_in * sizeof(double),
+                             hipMemcpyHostToDevice, c->stream));
+    else
+      HIP_TRY(hipMemcpyAsync(c->sim.rl_idx.p, src->obs_response, n_in * sizeof(int64_t),
+                             hipMemcpyHostToDevice, c->stream));
+  }
+  int64_t* const d_goff = c->sim.rl_idx.p + n_obs;
+  if (sr)
+    HIP_TRY(hipMemcpyAsync(d_goff, goff.data(), goff.size() * sizeof(int64_t),
+                           hipMemcpyHostToDevice, c->stream));
+  if (c->profile)
+    for (int k = 0; k < 2; ++k)
+      if (!c->sim.ev[k]) HIP_TRY(hipEventCreate(&c->sim.ev[k]));
+  wfpt::RlSimCall C;
+  C.rows = c->sim.rl_rows.p;
+  C.off = c->sim.off.p;
+  C.R = R;
+  C.row0 = row0;
+  C.dt = dt;
+  C.step = step;
+  C.scale = scale;
+  C.max_steps = (uint32_t)max_steps;
+  C.wave_rows = (int32_t)wd;
+  C.seed = seed;
+  C.source = source;
+  C.in_up = c->sim.rl_in.p;
+  C.in_low = c->sim.rl_in.p + n_in;
+  C.obs_resp = c->sim.rl_idx.p;
+  C.out = c->sim.out.p;
+  double* const host_dbg[7] = {D.feedback, D.q_up, D.q_low, D.sim_drift, D.drift, D.y0, D.delay};
+  double** const dev_dbg[7] = {&C.feedback, &C.q_up, &C.q_low, &C.sim_drift,
+                               &C.drift,    &C.y0,   &C.delay};
+  for (int k = 0; k < 7; ++k) *dev_dbg[k] = host_dbg[k] ? c->sim.u.p + k * total : nullptr;
+  C.n_steps = D.n_steps ? c->sim.idx.p : nullptr;
+  C.wave_steps = D.wave_steps ? c->sim.idx.p + total : nullptr;
+  if (c->profile) HIP_TRY(hipEventRecord(c->sim.ev[0], c->stream));
+  wfpt::launch_rl_sim(C, c->stream);
+  HIP_TRY(hipGetLastError());
+  if (c->profile) {
+    HIP_TRY(hipEventRecord(c->sim.ev[1], c->stream));
+    HIP_TRY(hipEventSynchronize(c->sim.ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->sim.ev[0], c->sim.ev[1]));
+    c->k_ms += ms;
+    c->launches += 1;
+  }
+  if (out && total > 0)
+    HIP_TRY(hipMemcpyAsync(out, c->sim.out.p, total * sizeof(double), hipMemcpyDeviceToHost,
+                           c->stream));
+  for (int k = 0; k < 7; ++k)
+    if (host_dbg[k] && total > 0)
+      HIP_TRY(hipMemcpyAsync(host_dbg[k], *dev_dbg[k], total * sizeof(double),
+                             hipMemcpyDeviceToHost, c->stream));
+  if (D.n_steps && total > 0)
+    HIP_TRY(hipMemcpyAsync(D.n_steps, C.n_steps, total * sizeof(int64_t), hipMemcpyDeviceToHost,
+                           c->stream));
+  if (D.wave_steps)
+    HIP_TRY(hipMemcpyAsync(D.wave_steps, C.wave_steps, waves * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, c->stream));
+  if (sr) {
+    if (int rc = stats_run(c, plan, c->sim.out.p, d_goff, goff.data(), G->n, sr->out)) return rc;
+  } else {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  unsigned long long nan_dev = 0;
+  if (!out && total > 0) {  // the draws stay on the device: their NaNs are counted there
+    HIP_TRY(c->stats.count.reserve(1));
+    HIP_TRY(hipMemsetAsync(c->stats.count.p, 0, sizeof(unsigned long long), c->stream));
+    wfpt::launch_stats_count_nan(c->sim.out.p, total, c->stats.count.p, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&nan_dev, c->stats.count.p, sizeof(unsigned long long),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  int64_t nan = (int64_t)nan_dev;  // only a cut trial and the rest of its row are NaN
   if (out)
     for (int64_t i = 0; i < total; ++i) nan += std::isnan(out[i]) ? 1 : 0;
   *n_unfinished = nan;
@@ -546,6 +771,38 @@ int wfpt_gen_rts_drift_nodes(wfpt_ctx* c, const wfpt_params* rows, int64_t R, co
   return wfpt_gen_rts_drift_nodes_ex(c, rows, R, sw, counts, dt, intra_sv, max_steps, seed, 0, 0,
                                      out, n_unfinished, nullptr, nullptr, nullptr, nullptr,
                                      nullptr, nullptr);
+}
+
+int wfpt_gen_rlddm_rows_ex(wfpt_ctx* c, const wfpt_params* rows, const double* rl_rows, int64_t R,
+                           const int64_t* counts, const wfpt_rl_source* source, double dt,
+                           double intra_sv, int64_t max_steps, uint64_t seed, int64_t row0,
+                           int32_t wave_rows, double* out, int64_t* n_unfinished,
+                           double* out_feedback, double* out_q_up, double* out_q_low,
+                           double* out_sim_drift, double* out_drift, double* out_y0,
+                           double* out_delay, int64_t* out_n_steps, int64_t* out_wave_steps) {
+  const RlSimDebug D{out_feedback, out_q_up, out_q_low, out_sim_drift, out_drift,
+                     out_y0,       out_delay, out_n_steps, out_wave_steps};
+  return gen_rlddm_rows_impl(c, rows, rl_rows, R, counts, source, dt, intra_sv, max_steps, seed,
+                             row0, wave_rows, out, n_unfinished, D, nullptr, nullptr);
+}
+
+int wfpt_gen_rlddm_rows(wfpt_ctx* c, const wfpt_params* rows, const double* rl_rows, int64_t R,
+                        const int64_t* counts, const wfpt_rl_source* source, double dt,
+                        double intra_sv, int64_t max_steps, uint64_t seed, double* out,
+                        int64_t* n_unfinished) {
+  return gen_rlddm_rows_impl(c, rows, rl_rows, R, counts, source, dt, intra_sv, max_steps, seed, 0,
+                             0, out, n_unfinished, RlSimDebug{}, nullptr, nullptr);
+}
+
+int wfpt_gen_rlddm_rows_stats(wfpt_ctx* c, const wfpt_params* rows, const double* rl_rows,
+                              int64_t R, const int64_t* counts, const wfpt_rl_source* source,
+                              double dt, double intra_sv, int64_t max_steps, uint64_t seed,
+                              double* out, int64_t* n_unfinished, const int64_t* group_off,
+                              int64_t n_groups, const double* q, int32_t nq, double* stats_out) {
+  const StatsReq sr{q, nq, stats_out};
+  const RlSimGroups G{group_off, n_groups};
+  return gen_rlddm_rows_impl(c, rows, rl_rows, R, counts, source, dt, intra_sv, max_steps, seed, 0,
+                             0, out, n_unfinished, RlSimDebug{}, &G, &sr);
 }
 
 int wfpt_profile_stages(wfpt_ctx* c, double stage_ms[4], int reset) {

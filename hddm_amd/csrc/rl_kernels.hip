@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rl_internal.h"
+#include "rl_update.hpp"
 #include "wfpt_kernel_common.hpp"
 
 #pragma clang fp contract(off)
@@ -28,10 +29,10 @@ constexpr int kRlAhead = 8;        // steps whose inputs the scan loads ahead
 
 // The Q recurrence. Bit-exact with the reference's arithmetic: the drift is one
 // subtraction and one multiplication, the update q + alfa * (f - q) three
-// separately rounded operations (the empty asm keeps the product out of any
-// fused multiply-add whatever the contraction setting), the learning-rate
-// choice the strict feedback > q (wfpt.pyx:145). A one-ulp difference in q
-// could flip that comparison and change every later trial.
+// separately rounded operations (rl_q_update, shared with the closed-loop
+// simulator), the learning-rate choice the strict feedback > q (wfpt.pyx:145).
+// A one-ulp difference in q could flip that comparison and change every later
+// trial.
 __device__ __forceinline__ void rl_scan_lane(const RlLayout& L, int r, const RlRow& R,
                                              const double* vmul, const double* rate,
                                              double* drift_c, double* drift_in) {
@@ -65,9 +66,7 @@ __device__ __forceinline__ void rl_scan_lane(const RlLayout& L, int r, const RlR
         if (drift_in) drift_in[L.caller ? L.caller[j] : j] = drift;
         const double qs = resp[u] ? q1 : q0;
         const double a = rate ? al[u] : (f[u] > qs ? R.pos_alfa : R.alfa);
-        double prod = a * (f[u] - qs);
-        asm volatile("" : "+v"(prod));
-        const double qn = qs + prod;
+        const double qn = rl_q_update(qs, a, f[u]);
         if (resp[u]) q1 = qn;
         else q0 = qn;
       }

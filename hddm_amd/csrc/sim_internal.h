@@ -1,5 +1,6 @@
 // sim_internal.h — launcher interface between the C ABI (capi_*.cpp) and the
-// RT sampler kernels (sim_kernels.hip). Not part of the public ABI.
+// RT sampler kernels (sim_kernels.hip, rl_sim_kernels.hip). Not part of the
+// public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -94,5 +95,58 @@ struct DriftCall {
   int64_t* wave_steps;   // [ceil(total / wave_draws)] steps each wave's loop ran
 };
 void launch_sim_drift(const DriftCall& C, hipStream_t s);
+
+// The closed-loop RLDDM simulator (rl_sim_kernels.hip; hddm/generate.py:430-516,
+// 608-661): one sequence row of the call's table. alfa / pos_alfa
+// are the squashed learning rates (pos_alfa == alfa for "use alpha"), p_up /
+// p_low the Bernoulli reward probabilities (kRlSimBernoulli only), src the
+// row's first element in the call's supplied / observed arrays.
+struct RlSimRow {
+  double v, sv, a, z, sz, t, st;
+  double q, alfa, pos_alfa;
+  double p_up, p_low;
+  int64_t src;
+};
+
+enum RlSimSource : int32_t {
+  kRlSimBernoulli = 0,  // reward = u < p, u the option's own Philox stream
+  kRlSimSupplied = 1,   // reward = in_up / in_low[src + k]
+  kRlSimObserved = 2,   // Q moves by obs_resp / in_up (the observed feedback)[src + k]
+};
+
+// Trial k of global row row0 + r is element off[r] + k of out and of the
+// (nullable) per-trial arrays. A lane owns one row and walks its trials in
+// order; a wave owns rows [w * wave_rows, + wave_rows) and hands the next one
+// to a lane whose row has ended. The walk is sim_drift_kernel's (DriftCall:
+// step, scale, max_steps), its random words Philox4x32-10 at counter (k lo, k
+// hi, row0 + r, stream): streams 1, 2, 3 and 16 + step / 4 as there, 5 / 6 the
+// upper / lower option's reward uniform. A trial cut at max_steps is NaN and
+// so is every later trial of its row.
+constexpr uint32_t kRlSimStreamUp = 5, kRlSimStreamLow = 6;
+struct RlSimCall {
+  const RlSimRow* rows;  // [R]
+  const int64_t* off;    // [R + 1] prefix sums of the trial counts
+  int64_t R;
+  int64_t row0;
+  double dt, step, scale;
+  uint32_t max_steps;  // 1 .. 2^31
+  int32_t wave_rows;   // a multiple of 64
+  uint64_t seed;
+  int32_t source;          // RlSimSource
+  const double* in_up;     // supplied: the upper option's rewards; observed: the feedback
+  const double* in_low;    // supplied: the lower option's rewards
+  const int64_t* obs_resp;  // observed: the responses (0 lower, else upper)
+  double* out;
+  double* feedback;   // the feedback that moved Q
+  double* q_up;       // the Q values before the trial's update
+  double* q_low;
+  double* sim_drift;  // (q_up - q_low) * v
+  double* drift;      // the walk's drift: sim_drift (+ sv * normal)
+  double* y0;
+  double* delay;
+  int64_t* n_steps;     // steps taken; 0 for a trial after a cut one
+  int64_t* wave_steps;  // [ceil(R / wave_rows)] steps each wave's loop ran
+};
+void launch_rl_sim(const RlSimCall& C, hipStream_t s);
 
 }  // namespace wfpt

@@ -23,9 +23,13 @@ tables, each row bit for bit the one-table call's.
   std node is slice-sampled inside its Uniform support (width 1).
 * a node's q is its first row's q_init (hddm_rl.py:69; default 0.5).
 
-The posterior predictive of an RL model needs a closed-loop simulator on the
-device (every draw feeds the next trial's drift) and is not part of this
-module; `gen_rl_data` below is the host-driven closed loop for synthetic data.
+The posterior predictive of an RL model is a closed loop: every simulated
+choice picks the reward that moves the Q values behind the next trial's drift.
+`HDDMrl.post_pred_sim` / `post_pred_sim_stats` run it on the device, one lane
+per (sweep, node, condition) sequence in ONE `wfpt.gen_rlddm_rows` launch
+(DESIGN.md §22), given the reward schedule to run on, or one step ahead of the
+observed choices (mode='onestep'). `gen_rl_data` below makes synthetic data by
+the host-driven loop or, with closed_loop='device', by the same launch.
 """
 import time
 
@@ -145,11 +149,129 @@ class HDDMrl(HDDM):
 
     optimize = quantile_objective = _refuses("HDDMrl: point fits are not implemented")
     post_pred_rows = post_pred_gen = post_pred_stats = _refuses(
-        "HDDMrl: the posterior predictive needs a closed-loop simulator and is not implemented")
+        "HDDMrl: a data-only posterior predictive has no reward schedule to run on; use "
+        "post_pred_sim / post_pred_sim_stats")
+
+    # -- posterior predictive ------------------------------------------------
+    def post_pred_sim_rows(self, samples=500):
+        """The sequence rows post_pred_sim simulates, as a dict: `picked` (S,)
+        the kept sweeps (HDDM.post_pred_rows' choice); `node`, `split_by`,
+        `counts` (Rn,) the (node, condition) sequences of the data, conditions
+        rising inside a node, with their trial counts; `params` (S * Rn, 8) and
+        `rl_rows` (S * Rn, 3) the rows in (sweep, node, condition) order, q the
+        node's node_q and the other values the sweep's; `order` the data's
+        trials sorted into that sequence order (the caller's order kept inside
+        a sequence) and `first` (Rn,) each sequence's first element there."""
+        picked, P = HDDM.post_pred_rows(self, samples)
+        split = self.data["split_by"].to_numpy().astype(np.int64)
+        order = np.lexsort((np.arange(split.size), split, self.node_codes))
+        pairs, first, counts = np.unique(np.stack([self.node_codes[order], split[order]], axis=1),
+                                         axis=0, return_index=True, return_counts=True)
+        node = pairs[:, 0]
+        S = picked.size
+        rl = np.empty((S, node.size, 3))
+        rl[:, :, 0] = self.node_q[node]
+        rl[:, :, 2] = NO_POS_ALPHA
+        for fam in self.rl_families:
+            rl[:, :, _RL_COL[fam]] = self.trace_subj[fam][picked][:, self.node_unit[fam][node]]
+        return {"picked": picked, "node": node, "split_by": pairs[:, 1],
+                "counts": counts.astype(np.int64), "params": P[:, node].reshape(-1, 8),
+                "rl_rows": rl.reshape(-1, 3), "order": order, "first": first.astype(np.int64)}
+
+    def _sim_source(self, T, rewards, mode):
+        """gen_rlddm_rows' reward source for the rows T of post_pred_sim_rows."""
+        S = T["picked"].size
+        if mode == "onestep":
+            data = self.data
+            return {"observed": (data["response"].to_numpy().astype(np.int64)[T["order"]],
+                                 data["feedback"].to_numpy(dtype=np.float64)[T["order"]],
+                                 np.tile(T["first"], S))}
+        if mode != "closed":
+            raise ValueError("mode must be 'closed' or 'onestep'")
+        if rewards is None:
+            raise ValueError("mode='closed' needs rewards: {split_by value: (p_upper, p_lower)}")
+        missing = sorted(set(T["split_by"].tolist()) - {int(k) for k in rewards})
+        if missing:
+            raise KeyError(f"rewards has no entry for the split_by values {missing}")
+        by_cond = {int(k): v for k, v in rewards.items()}
+        p = np.array([by_cond[c] for c in T["split_by"].tolist()], dtype=np.float64)
+        return {"rewards": np.tile(p.reshape(-1, 2), (S, 1))}
+
+    def post_pred_sim(self, rewards=None, samples=500, seed=None, dt=1e-4, mode="closed",
+                      return_debug=False):
+        """Posterior predictive data of the RL model (the reference's workflow
+        over gen_rand_rlddm_data, hddm/generate.py:430-516): for each of
+        `samples` evenly spaced kept sweeps, each node and each split_by
+        condition of the node, one simulated sequence of as many trials as the
+        node has in that condition, at the sweep's parameters and from the
+        node's initial Q value -- all sequences in ONE wfpt.gen_rlddm_rows
+        launch (post_pred_sim_rows documents its rows).
+
+        rewards: {split_by value: (p_upper, p_lower)}, the reward schedule the
+        simulated choices run on (binary rewards drawn on the device); needed
+        for mode='closed'. mode='onestep' is the reference's one-step-ahead
+        simulator (generate.py:608-661): Q follows the observed responses and
+        feedback, and every trial's RT is simulated at the drift they give.
+
+        Returns a DataFrame with columns sample (index of the kept sweep), node
+        (index into node_keys), split_by, trial (1-based inside the sequence),
+        rt (signed), response (1 upper / 0 lower: the simulated choice) and
+        feedback (the value that moved Q); with return_debug also q_up, q_low
+        and sim_drift."""
+        import pandas as pd
+        T = self.post_pred_sim_rows(samples)
+        source = self._sim_source(T, rewards, mode)
+        S = T["picked"].size
+        if seed is None:
+            seed = int(self.rng.integers(0, 2 ** 63))
+        cnt = np.tile(T["counts"], S)
+        rts, _, dbg = _wfpt.gen_rlddm_rows(T["params"], T["rl_rows"], cnt, dt=dt, seed=seed,
+                                           return_debug=True, **source)
+        rep = lambda per_row: np.repeat(np.tile(per_row, S), cnt)
+        frame = pd.DataFrame({
+            "sample": np.repeat(np.repeat(T["picked"], T["node"].size), cnt),
+            "node": rep(T["node"]), "split_by": rep(T["split_by"]),
+            "trial": np.concatenate([np.arange(1, c + 1) for c in cnt]),
+            "rt": rts, "response": (rts > 0).astype(np.int64), "feedback": dbg["feedback"]})
+        if return_debug:
+            for k in ("q_up", "q_low", "sim_drift"):
+                frame[k] = dbg[k]
+        return frame
+
+    def post_pred_sim_stats(self, rewards=None, samples=500, seed=None, dt=1e-4, mode="closed",
+                            quantiles=(10, 30, 50, 70, 90), return_sampled=False):
+        """The posterior predictive check over post_pred_sim's sequences without
+        the data sets: the same draws (same arguments, same seed) are reduced to
+        gen_ppc_stats' statistics per (sweep, node) on the device by ONE fused
+        call (wfpt.gen_rlddm_stats_rows: a node's statistics row covers its
+        condition sequences; no draw is copied to the host), the observed nodes
+        by one wfpt.rt_stats_rows call, and ppc.summarize compares the two.
+
+        Returns ppc.summarize's DataFrame indexed by (node, stat), shaped like
+        HDDM.post_pred_stats'; with return_sampled=True also the sampled
+        statistics (len(picked), n_nodes, K)."""
+        from . import ppc
+        T = self.post_pred_sim_rows(samples)
+        source = self._sim_source(T, rewards, mode)
+        S = T["picked"].size
+        if seed is None:
+            seed = int(self.rng.integers(0, 2 ** 63))
+        per_node = np.bincount(T["node"], minlength=self.n_nodes)
+        groups = np.r_[0, np.cumsum(np.tile(per_node, S))]
+        sampled, _ = _wfpt.gen_rlddm_stats_rows(T["params"], T["rl_rows"], np.tile(T["counts"], S),
+                                                groups, quantiles=quantiles, dt=dt, seed=seed,
+                                                **source)
+        sampled = sampled.reshape(S, self.n_nodes, -1)
+        order = np.argsort(self.node_codes, kind="stable")
+        offsets = np.zeros(self.n_nodes + 1, dtype=np.int64)
+        np.cumsum(self.node_counts, out=offsets[1:])
+        observed = _wfpt.rt_stats_rows(self.signed_rt[order], offsets, quantiles)
+        table = ppc.summarize(observed, sampled, _wfpt.rt_stats_names(quantiles))
+        return (table, sampled) if return_sampled else table
 
 
 def gen_rl_data(n_subj, n_trials, conds, a, t, v, alpha, pos_alpha=None, z=0.5, q_init=0.5,
-                jitter=0.1, seed=20261020, dt=1e-3, draw=None):
+                jitter=0.1, seed=20261020, dt=1e-3, draw=None, closed_loop="host"):
     """Synthetic two-armed-bandit data from the RLDDM in closed loop
     (hddm/generate.py:430-516): n_trials trials for each of n_subj subjects in
     each condition of `conds`, {split_by value: (p_upper, p_lower)} the reward
@@ -166,10 +288,15 @@ def gen_rl_data(n_subj, n_trials, conds, a, t, v, alpha, pos_alpha=None, z=0.5, 
     drift exactly. draw(drifts) -> signed RTs replaces the device draw
     (wfpt.gen_rts_from_cdf_nodes with a device seed per step).
 
+    closed_loop='device' runs the whole loop in ONE wfpt.gen_rlddm_rows launch
+    instead: the same up-front rewards from the same generator stream go in as
+    supplied arrays, every RT is a simulated diffusion path with time step dt,
+    and the Q values move on the device in the likelihood's rounding (`draw`
+    is not used). The columns are the same.
+
     Returns (DataFrame, truth): columns rt (signed), response, feedback,
     split_by, subj_idx, q_init, trial, q_up, q_low, sim_drift; truth the true
     subject parameters {'a', 't', 'v', 'alpha'[, 'pos_alpha']}."""
-    import pandas as pd
     rng = np.random.default_rng(seed)
     labels = [int(c) for c in conds]
     jit = lambda: jitter * rng.uniform(-1, 1)
@@ -187,10 +314,25 @@ def gen_rl_data(n_subj, n_trials, conds, a, t, v, alpha, pos_alpha=None, z=0.5, 
     rew = {(s, c): (rng.binomial(1, conds[c][0], n_trials).astype(np.float64),
                     rng.binomial(1, conds[c][1], n_trials).astype(np.float64))
            for s, c in seqs}
+    if closed_loop not in ("host", "device"):
+        raise ValueError("closed_loop must be 'host' or 'device'")
     P = np.zeros((S, 8))
     P[:, 2] = [truth["a"][s] for s, _ in seqs]
     P[:, 3] = z
     P[:, 5] = [truth["t"][s] for s, _ in seqs]
+    if closed_loop == "device":
+        P[:, 0] = [truth["v"][s] for s, _ in seqs]
+        rows = np.empty((S, 3))
+        rows[:, 0] = q_init
+        rows[:, 1] = [truth["alpha"][s] for s, _ in seqs]
+        rows[:, 2] = [truth["pos_alpha"][s] for s, _ in seqs] if pos_alpha is not None \
+            else NO_POS_ALPHA
+        arrays = tuple(np.concatenate([rew[sc][i] for sc in seqs]) for i in (0, 1))
+        rts, _, dbg = _wfpt.gen_rlddm_rows(P, rows, n_trials, reward_arrays=arrays, dt=dt,
+                                           seed=int(rng.integers(0, 2 ** 63)), return_debug=True)
+        cols = {"rt": rts, "response": rts > 0, **{k: dbg[k] for k in ("feedback", "q_up",
+                                                                       "q_low", "sim_drift")}}
+        return _rl_frame(cols, seqs, n_trials, q_init), truth
     if draw is None:
         def draw(drifts):
             P[:, 0] = drifts
@@ -219,12 +361,17 @@ def gen_rl_data(n_subj, n_trials, conds, a, t, v, alpha, pos_alpha=None, z=0.5, 
                 q_up[i] = q
             else:
                 q_low[i] = q
-    frame = pd.DataFrame({
+    return _rl_frame(cols, seqs, n_trials, q_init), truth
+
+
+def _rl_frame(cols, seqs, n_trials, q_init):
+    """gen_rl_data's frame from per-trial columns, sequence after sequence."""
+    import pandas as pd
+    return pd.DataFrame({
         "rt": cols["rt"].ravel(), "response": cols["response"].ravel().astype(np.int64),
         "feedback": cols["feedback"].ravel(),
         "split_by": np.repeat([c for _, c in seqs], n_trials).astype(np.int64),
         "subj_idx": np.repeat([s for s, _ in seqs], n_trials).astype(np.int64),
-        "q_init": float(q_init), "trial": np.tile(np.arange(1, n_trials + 1), S),
+        "q_init": float(q_init), "trial": np.tile(np.arange(1, n_trials + 1), len(seqs)),
         "q_up": cols["q_up"].ravel(), "q_low": cols["q_low"].ravel(),
         "sim_drift": cols["sim_drift"].ravel()})
-    return frame, truth

@@ -27,7 +27,10 @@ predictive data sets: HDDM.post_pred_gen). `gen_rts_from_drift_nodes` /
 in-trial drift switch) on the device. `rt_stats_rows` reduces many rows of
 signed RTs to the posterior predictive check's statistics (gen_ppc_stats,
 hddm/utils.py:241-265) on the device, and `gen_rts_stats_nodes` does so for
-the draws of either sampler without copying them out. `RegDataset(rt, design)` keeps a
+the draws of either sampler without copying them out. `gen_rlddm_rows` simulates
+RLDDM sequences in closed loop on the device (hddm/generate.py:430-516: every
+trial's drift comes from the Q values the earlier simulated trials left), and
+`gen_rlddm_stats_rows` reduces its draws likewise. `RegDataset(rt, design)` keeps a
 design matrix resident and forms HDDMRegressor's trial-wise parameters
 link(design . coefficients) on the device (hddm_regression.py:26-36).
 
@@ -49,6 +52,7 @@ from . import _lib
 __all__ = ["pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "wiener_like_multi_terms",
            "gen_rts_from_cdf", "gen_rts_from_cdf_nodes", "gen_rts_from_drift_nodes",
            "gen_rts_from_drift", "rt_stats_rows", "rt_stats_names", "gen_rts_stats_nodes",
+           "gen_rlddm_rows", "gen_rlddm_stats_rows",
            "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl", "wiener_like_multi_rlddm",
            "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_nodes_multi",
            "wiener_like_rlddm_terms",
@@ -542,6 +546,171 @@ def gen_rts_stats_nodes(params, samples, method="cdf", quantiles=PPC_QUANTILES, 
     run = _cdf_stats if method == "cdf" else _drift_stats
     run(table, cnt, offsets, q, out, stats, seed=seed, **sampler_kw)
     return (stats, offsets, out) if return_draws else (stats, offsets)
+
+
+# The closed-loop RLDDM simulator (wfpt_gen_rlddm_rows).
+
+_RL_DEBUG = ("feedback", "q_up", "q_low", "sim_drift", "drift", "y0", "delay")
+
+
+def _rl_source(R, cnt, offsets, rewards, reward_arrays, observed):
+    """The checked reward source of a closed-loop call: (_lib.RlSource, the
+    arrays it points into). Exactly one of the three is given."""
+    if sum(x is not None for x in (rewards, reward_arrays, observed)) != 1:
+        raise ValueError("exactly one of rewards, reward_arrays and observed must be given")
+    src, keep = _lib.RlSource(), []
+
+    def addr(a):
+        keep.append(a)
+        return a.ctypes.data
+
+    if rewards is not None:
+        p = np.asarray(rewards, dtype=np.float64)
+        if p.shape == (2,):
+            p = np.tile(p, (R, 1))
+        if p.shape != (R, 2):
+            raise ValueError(f"rewards must have shape (2,) or ({R}, 2): p_upper, p_lower")
+        if not np.all((p >= 0) & (p <= 1)):  # NaN fails both comparisons
+            raise ValueError("reward probabilities must lie in [0, 1]")
+        src.p = addr(np.ascontiguousarray(p))
+        return src, keep
+    name = "reward_arrays" if reward_arrays is not None else "observed"
+    parts = tuple(reward_arrays if reward_arrays is not None else observed)
+    if len(parts) not in (2, 3):
+        raise ValueError(f"{name} must be (first, second) or (first, second, start)")
+    first = np.ascontiguousarray(parts[0], dtype=np.float64 if observed is None else np.int64)
+    second = np.ascontiguousarray(parts[1], dtype=np.float64)
+    if first.ndim != 1 or first.shape != second.shape:
+        raise ValueError(f"the two arrays of {name} must be 1-D and of one length")
+    if len(parts) == 3:
+        start = np.ascontiguousarray(parts[2], dtype=np.int64)
+        if start.shape != (R,):
+            raise ValueError(f"the start offsets of {name} must hold {R} entries")
+    else:
+        start = offsets[:-1]
+    if np.any(start < 0) or np.any(start + cnt > first.size):
+        raise ValueError(f"a row reads outside the {first.size} elements of {name}")
+    if len(parts) == 3:
+        src.start = addr(start)
+    src.n = first.size
+    if observed is None:
+        src.rew_up, src.rew_low = addr(first), addr(second)
+    else:
+        src.obs_response, src.obs_feedback = addr(first), addr(second)
+    return src, keep
+
+
+def _rlddm_prep(params, rl_rows, n_trials, rewards, reward_arrays, observed, dt, intra_sv, max_t,
+                unfinished, row0):
+    """The closed-loop simulator's checked arguments, before the seed is taken
+    and before any context is loaded."""
+    table, cnt, offsets = _sampler_table(params, n_trials)
+    R = table.shape[0]
+    rl = np.ascontiguousarray(rl_rows, dtype=np.float64)
+    if rl.shape != (R, 3):
+        raise ValueError(f"rl_rows must have shape ({R}, 3): q, alpha, pos_alpha")
+    if np.isnan(rl).any():
+        raise ValueError("rl_rows must not hold NaN")
+    dt, intra_sv, max_steps, _ = _drift_prep(R, dt, intra_sv, None, max_t, unfinished)
+    row0 = int(row0)
+    if not 0 <= row0 <= 2 ** 31 - R:
+        raise ValueError("row0 + R must lie in [1, 2^31]")
+    src, keep = _rl_source(R, cnt, offsets, rewards, reward_arrays, observed)
+    return table, rl, cnt, offsets, dt, intra_sv, max_steps, row0, src, keep
+
+
+def gen_rlddm_rows(params, rl_rows, n_trials, rewards=None, reward_arrays=None, observed=None,
+                   dt=1e-4, intra_sv=1., seed=None, max_t=20., unfinished='raise',
+                   return_debug=False, row0=0, wave_rows=None):
+    """gen_rand_rlddm_data (hddm/generate.py:430-516) for R sequences in ONE
+    launch on the GPU (wfpt_gen_rlddm_rows): a lane owns a sequence and closes
+    the loop itself -- simulate the trial as a diffusion path (the arithmetic
+    and random streams of gen_rts_from_drift_nodes with the draw index set to
+    the trial index), take the chosen option's reward, move its Q value
+    exactly as the likelihood does, form the next drift (q_up - q_low) * v.
+
+    params: (R, 7) or (R, 8) rows of v (the drift scaling), sv, a, z, sz, t,
+    st[, p_outlier]. rl_rows: (R, 3) rows of q, alpha, pos_alpha (alpha on the
+    unbounded scale, pos_alpha == 100.0: use alpha). n_trials: trials per row,
+    an int or R ints. Exactly one reward source:
+      rewards        (2,) or (R, 2) probabilities p_upper, p_lower: binary
+                     rewards drawn on the device;
+      reward_arrays  (rew_up, rew_low[, start]): the two options' rewards per
+                     trial; trial k of row r reads element start[r] + k
+                     (default: the row's own offset), so replicate rows can
+                     share one copy;
+      observed       (response, feedback[, start]): the reference's
+                     one-step-ahead simulator (generate.py:608-661): Q follows
+                     the observed pair, the simulated RT is only recorded.
+    Returns (rts, offsets): row r's trials are rts[offsets[r]:offsets[r + 1]].
+
+    seed, max_t and unfinished are gen_rts_from_drift_nodes' (a cut walk makes
+    its trial and every later trial of the row NaN). return_debug: also a dict
+    of the per-trial `feedback`, `q_up`, `q_low` (before the update),
+    `sim_drift`, the walk's `drift`, `y0`, `delay` and `n_steps`. row0 is added
+    to the row index of the random streams; wave_rows (a multiple of 64) is a
+    measurement knob that changes no value and adds `wave_steps` to the dict.
+    """
+    table, rl, cnt, offsets, dt, intra_sv, max_steps, row0, src, keep = _rlddm_prep(
+        params, rl_rows, n_trials, rewards, reward_arrays, observed, dt, intra_sv, max_t,
+        unfinished, row0)
+    R, total = table.shape[0], int(offsets[-1])
+    wd = 0 if wave_rows is None else int(wave_rows)
+    if wd < 0 or wd % 64:
+        raise ValueError("wave_rows must be a positive multiple of 64")
+    seed = _drift_seed(seed)
+    out = np.empty(total, dtype=np.float64)
+    nun = ctypes.c_int64()
+    head = (_lib.context().handle, table.ctypes.data_as(_lib._PP), _lib.dptr(rl), R, _i64ptr(cnt),
+            ctypes.byref(src), dt, intra_sv, max_steps, seed)
+    if return_debug or row0 or wd:
+        dbg = {k: np.empty(total) for k in _RL_DEBUG}
+        dbg["n_steps"] = np.empty(total, dtype=np.int64)
+        if wd:
+            dbg["wave_steps"] = np.empty(-(-R // wd), dtype=np.int64)
+        rc = _lib.wfpt_gen_rlddm_rows_ex(
+            *head, row0, wd, _lib.dptr(out), ctypes.byref(nun),
+            *[_lib.dptr(dbg[k]) for k in _RL_DEBUG], _i64ptr(dbg["n_steps"]),
+            _i64ptr(dbg["wave_steps"]) if wd else None)
+    else:
+        rc = _lib.wfpt_gen_rlddm_rows(*head, _lib.dptr(out), ctypes.byref(nun))
+    _check_drawn(rc, "drift")
+    _check_finished(nun.value, total, max_steps, max_t, unfinished)
+    return (out, offsets, dbg) if return_debug else (out, offsets)
+
+
+def gen_rlddm_stats_rows(params, rl_rows, n_trials, groups, rewards=None, reward_arrays=None,
+                         observed=None, quantiles=PPC_QUANTILES, dt=1e-4, intra_sv=1., seed=None,
+                         max_t=20., unfinished='raise', return_draws=False):
+    """gen_rlddm_rows' draws (same arguments, same seed: the same draws)
+    reduced to rt_stats_rows' statistics while they are still in device memory
+    (wfpt_gen_rlddm_rows_stats). groups: G + 1 rising offsets from 0 to R over
+    the rows; statistics row g covers the trials of rows groups[g] ..
+    groups[g + 1], a node made of its condition sequences. Returns (stats,
+    trial offsets of the groups), and the draws as a third element with
+    return_draws=True; stats is (G, 8 + 2 len(quantiles)) in rt_stats_names'
+    order."""
+    q = _check_quantiles(quantiles)
+    table, rl, cnt, offsets, dt, intra_sv, max_steps, _, src, keep = _rlddm_prep(
+        params, rl_rows, n_trials, rewards, reward_arrays, observed, dt, intra_sv, max_t,
+        unfinished, 0)
+    R, total = table.shape[0], int(offsets[-1])
+    goff = np.ascontiguousarray(groups, dtype=np.int64)
+    if goff.ndim != 1 or goff.size < 2 or goff[0] != 0 or goff[-1] != R \
+            or np.any(np.diff(goff) < 0):
+        raise ValueError(f"groups must hold G + 1 >= 2 offsets rising from 0 to {R}")
+    seed = _drift_seed(seed)
+    G = goff.size - 1
+    stats = np.empty((G, 8 + 2 * q.size))
+    out = np.empty(total) if return_draws else None
+    nun = ctypes.c_int64()
+    rc = _lib.wfpt_gen_rlddm_rows_stats(
+        _lib.context().handle, table.ctypes.data_as(_lib._PP), _lib.dptr(rl), R, _i64ptr(cnt),
+        ctypes.byref(src), dt, intra_sv, max_steps, seed, _optr(out), ctypes.byref(nun),
+        _i64ptr(goff), G, _lib.dptr(q), q.size, _lib.dptr(stats))
+    _check_drawn(rc, "drift")
+    _check_finished(nun.value, total, max_steps, max_t, unfinished)
+    return (stats, offsets[goff], out) if return_draws else (stats, offsets[goff])
 
 
 class _Resident:

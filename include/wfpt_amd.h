@@ -23,6 +23,7 @@
  *                             src/wfpt.pyx:323-354
  *   wfpt_gen_rts_drift_nodes <- generate._gen_rts_from_simulated_drift, many rows
  *                             hddm/generate.py:208-319
+ *   wfpt_gen_rlddm_rows    <- generate.gen_rand_rlddm_data, many sequences in closed loop
  *   wfpt_rt_stats_rows     <- utils.gen_ppc_stats applied to many rows of RTs
  *                             hddm/utils.py:241-265
  * The Python binding that keeps the reference signatures is
@@ -563,6 +564,69 @@ int wfpt_gen_rts_drift_nodes_ex(wfpt_ctx *ctx, const wfpt_params *rows, int64_t 
                                 double *out_drift_switch, int64_t *out_n_steps,
                                 int64_t *out_wave_steps);
 
+/* ---- closed-loop RLDDM simulator ------------------------------------------ */
+/* Where the reward of a simulated trial comes from; exactly one of the three
+ * must be given (the other pointers NULL):
+ *   p             R pairs {p_upper, p_lower} in [0, 1]: the option's reward is
+ *                 1.0 if u < p else 0.0, u a device uniform (below)
+ *   rew_up/_low   the two options' rewards per trial (any finite or infinite
+ *                 value; generate.py:463-464 draws them up front)
+ *   obs_response/ observed mode, the reference's one-step-ahead simulator
+ *   obs_feedback  (generate.py:608-661): Q moves by the observed pair (response
+ *                 0 lower, else upper) and the simulated RT is only recorded
+ * Trial k of row r reads element start[r] + k of the supplied / observed
+ * arrays of n elements (start NULL: the row's own offset, sum of the counts
+ * before it), so replicate rows can share one copy. */
+typedef struct {
+  const double *p;
+  const double *rew_up, *rew_low;
+  const int64_t *obs_response;
+  const double *obs_feedback;
+  const int64_t *start;
+  int64_t n;
+} wfpt_rl_source;
+/* gen_rand_rlddm_data (hddm/generate.py:430-516) for R sequence rows in one
+ * launch, one lane per sequence. Row r: the DDM row rows[r] (v is the drift
+ * scaling; p_outlier ignored), the RL row rl_rows[3 r ..] = {q, alpha,
+ * pos_alpha} with wfpt_wiener_like_rlddm's conventions (alpha unbounded, the
+ * rate 2.718281828459**alpha / (1 + 2.718281828459**alpha) by libm pow;
+ * pos_alpha == 100.0: use alpha) and counts[r] >= 0 trials; trial k of row r is
+ * element off[r] + k of out. Per trial, in this order: drift = (q_up - q_low)
+ * v (+ sv n when sv != 0); start point, delay and walk as in
+ * wfpt_gen_rts_drift_nodes, operation for operation; response = rt > 0; the
+ * feedback is the chosen option's reward; rate = pos rate if feedback >
+ * q_chosen (strict) else rate; q_chosen += rate (feedback - q_chosen), three
+ * separately rounded operations as in the likelihood.
+ * Random numbers: wfpt_gen_rts_drift_nodes' Philox counters with draw = the
+ * trial index k: {k lo, k hi, row, stream}, streams 1, 2, 3 and 16 + step / 4
+ * as there; stream 5 / 6: the upper / lower option's reward uniform. A row
+ * whose drift never moves draws what row r of wfpt_gen_rts_drift_nodes draws.
+ * A walk cut at max_steps makes its trial NaN and ends the sequence: every
+ * later trial of the row is NaN; *n_unfinished counts the NaN trials.
+ * WFPT_ERR_ARG before any device work: null pointers, R < 1, dt / intra_sv /
+ * max_steps as in wfpt_gen_rts_drift_nodes, a negative count, none or more than
+ * one reward source, a p outside [0, 1], a NaN in rl_rows, a start[r] with
+ * start[r] + counts[r] outside the n elements. WFPT_ERR_UNSUPPORTED, naming
+ * the row: a row wfpt_gen_rts_drift_nodes cannot simulate. */
+int wfpt_gen_rlddm_rows(wfpt_ctx *ctx, const wfpt_params *rows, const double *rl_rows, int64_t R,
+                        const int64_t *counts, const wfpt_rl_source *source, double dt,
+                        double intra_sv, int64_t max_steps, uint64_t seed, double *out,
+                        int64_t *n_unfinished);
+/* As wfpt_gen_rlddm_rows. row0 (row0 + R <= 2^31): added to the row index in
+ * the Philox counter. wave_rows: rows handed to one wave, a multiple of 64 (0:
+ * the library's choice) -- it changes no value. Per trial, each nullable:
+ * out_feedback; out_q_up / out_q_low the Q values before the trial's update;
+ * out_sim_drift = (q_up - q_low) v; out_drift the walk's drift; out_y0;
+ * out_delay; out_n_steps (0 for a trial after a cut one, whose other outputs
+ * are NaN). out_wave_steps [ceil(R / wave_rows), wave_rows > 0]. */
+int wfpt_gen_rlddm_rows_ex(wfpt_ctx *ctx, const wfpt_params *rows, const double *rl_rows,
+                           int64_t R, const int64_t *counts, const wfpt_rl_source *source,
+                           double dt, double intra_sv, int64_t max_steps, uint64_t seed,
+                           int64_t row0, int32_t wave_rows, double *out, int64_t *n_unfinished,
+                           double *out_feedback, double *out_q_up, double *out_q_low,
+                           double *out_sim_drift, double *out_drift, double *out_y0,
+                           double *out_delay, int64_t *out_n_steps, int64_t *out_wave_steps);
+
 /* ---- per-row RT statistics ----------------------------------------------- */
 /* gen_ppc_stats (hddm/utils.py:241-265), the posterior predictive check's
  * summary statistics, for R rows of signed RTs in one call. Row r's draws are
@@ -610,6 +674,18 @@ int wfpt_gen_rts_drift_nodes_stats(wfpt_ctx *ctx, const wfpt_params *rows, int64
                                    double intra_sv, int64_t max_steps, uint64_t seed,
                                    double *out, int64_t *n_unfinished, const double *q,
                                    int32_t nq, double *stats_out);
+
+/* wfpt_gen_rlddm_rows followed by the statistics of its draws while they are
+ * still in device memory. Statistics row g covers the trials of the rows
+ * [group_off[g], group_off[g + 1]) (n_groups + 1 rising offsets from 0 to R):
+ * a node made of its condition sequences. stats_out [n_groups x (8 + 2 nq)] is
+ * what wfpt_rt_stats_rows gives for those draws; out may be NULL; *n_unfinished
+ * is counted either way. */
+int wfpt_gen_rlddm_rows_stats(wfpt_ctx *ctx, const wfpt_params *rows, const double *rl_rows,
+                              int64_t R, const int64_t *counts, const wfpt_rl_source *source,
+                              double dt, double intra_sv, int64_t max_steps, uint64_t seed,
+                              double *out, int64_t *n_unfinished, const int64_t *group_off,
+                              int64_t n_groups, const double *q, int32_t nq, double *stats_out);
 
 /* ---- measurement -------------------------------------------------------- */
 /* Under WFPT_PROF_EVENTS: device milliseconds of the RT sampler's stages
