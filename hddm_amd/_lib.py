@@ -291,7 +291,7 @@ class Context:
             return {}
         check(wfpt_profile_lists(self.handle, a, 1 if reset else 0))
         v = list(a)
-        return {"segments": v[0], "node_deferred": v[3], "lean_generic": v[3],
+        return {"segments": v[0], "lean_table": v[0], "node_deferred": v[3], "lean_generic": v[3],
                 "tasks1": v[1], "tasks2": v[2], "records": v[4], "exact": v[5],
                 "walk": v[6], "zwalks": v[7], "zwalks0": v[8], "zwalks1": v[9],
                 "zwalks2": v[10], "phase_kcycles": v[11:16]}

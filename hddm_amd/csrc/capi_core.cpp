@@ -162,6 +162,21 @@ bool engine_family(const wfpt::Params& P, const wfpt::Knobs& K) {
   return m >= wfpt::kAdaptT && m <= wfpt::kAdaptTZ;
 }
 
+// The context's decision table for err (the caller holds the context's lock).
+// Outside decide32's range of err the uniform site keeps what it had before
+// the table: no wave settled there (a table that never answers).
+static const wfpt::DecisionTab* decision_tab_of(wfpt_ctx* c, double err) {
+  uint64_t key;
+  std::memcpy(&key, &err, sizeof key);
+  if (!c->dtab_valid || c->dtab_err != key) {
+    if (err > 1e-30 && err < 1e30) wfpt::decision_tab(err, c->dtab);
+    else wfpt::decision_tab_clear(c->dtab);
+    c->dtab_err = key;
+    c->dtab_valid = true;
+  }
+  return &c->dtab;
+}
+
 // Likelihood sum over device x[n]: adaptive / direct families run the level-0
 // pass and (part & kPassDeferred) the deferred-trial pass, fixed Simpson one
 // trial kernel; then finalize writes {sum, zeros, errors, deferred} + the
@@ -206,7 +221,12 @@ int run_sum(wfpt_ctx* c, const double* dx, int64_t n, const wfpt::Params& P,
   const wfpt::Split S = eng ? split_of(d) : wfpt::Split{};
   wfpt::launch_trials(c->trial ? 3 : 0, adaptive ? part : wfpt::kPassAll, dx, n, P, K, c->part.p,
                       c->zero.p, c->count ? c->evals.p : nullptr, c->status.p, 0, W, c->stream,
-                      prof ? c->ev1 : nullptr, &S, c->trial);
+                      prof ? c->ev1 : nullptr, &S, c->trial,
+                      // (only the 2-D family's lean kernel reads the table)
+                      ((part & wfpt::kPassLean) &&
+                       wfpt::select_mode(P.sz, P.st, K.use_adaptive) == wfpt::kAdaptTZ)
+                          ? decision_tab_of(c, K.err)
+                          : nullptr);
   if (!adaptive) {
     c->path |= WFPT_PATH_FIXED;
   } else {

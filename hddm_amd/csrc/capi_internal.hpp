@@ -235,6 +235,13 @@ struct wfpt_ctx {
   DevBuf<int> fin_ticket;    // its last-block ticket (0 at rest)
   DevBuf<int> prof;          // 16 refinement work counters (PROF_EVALS)
   DevBuf<unsigned long long> phase;  // engine phase cycles (diagnostic builds)
+  // The lean pass's series-decision table (wfpt_device.hpp: decision_tab). It
+  // depends on err alone and costs ~0.2 ms of bisection, so it is kept here,
+  // keyed by err's bit pattern, and rebuilt only when err changes. It travels
+  // to the kernel by value, so there is nothing to upload.
+  wfpt::DecisionTab dtab;
+  uint64_t dtab_err = 0;
+  bool dtab_valid = false;
   DevBuf<int> defer;         // dmat_cdf_array: deferred trial indices + count
   DevBuf<double> cdf_tab;    // dmat_cdf_array: the call's parameter-only tables
   DevBuf<double> rows_in;    // dmat_cdf_rows: the call's rows | x | freq_obs | n_samples, packed

@@ -1907,6 +1907,175 @@ __host__ __device__ inline bool uniform_guard(double tt4, double vvx0, double sv
   return 0.5 * bound + (14.0 * Cb) * tt4 < 600.0 * tt4;
 }
 
+// The series decision as a table over tt. (small, K) of pdf.pxi:36-60 depends
+// on (tt, err) alone and is piecewise constant in tt with a handful of pieces
+// (err = 1e-4: small K = 3, small K = 4 from 0.0553, large K = 4 from 0.1537,
+// K = 3 from 0.2161, K = 2 from 0.4492, K = 1 from 1.546). The host finds the
+// breakpoints once per err (decision_tab) and a wave of the lean pass looks
+// up the tt of its two extreme |rt| at each t node instead of estimating
+// every lane's decision (table_decisions).
+//
+// edge[]: lo_0 < hi_0 < lo_1 < hi_1 < ... (unused entries +inf), code[i] =
+// small << 4 | K of piece i. A piece whose K exceeds the uniform site's tables
+// (kUniK small-time, kSinK large-time) is left out, so is everything outside
+// the domain [kDecLo, decision_hi(err)]: the table does not answer there.
+//
+// Claim: for every tt with lo_i <= tt < hi_i the reference's decision
+// (decide64's expressions on the reference's own xx / a2) is piece i's, and
+// decide64 does not mark it ambiguous. Argument:
+//   * decision_tab brackets every change of the decision between two adjacent
+//     doubles l < r (bisection on the fp64 expressions with the host libm,
+//     which is what the reference runs), so between two neighbouring brackets
+//     the decision is constant, provided it does not leave a piece and come
+//     back to it inside one cell of the log-spaced scan (several pieces in a
+//     row inside one cell are found one by one). It cannot: on the domain ks
+//     is nondecreasing and kl nonincreasing in tt, so `small` flips once and
+//     K moves one way on either side; tests/c/lean_decision_host.cpp checks
+//     that monotonicity and the pieces against a dense scan for the errs in
+//     use.
+//   * lo_i = r (1 + kDecBand), hi_i = l (1 - kDecBand) with kDecBand = 1e-6:
+//     the lane's tt = (x - tc) * ia2 and the reference's xx / a2 differ by at
+//     most 2 ulp (4.5e-16 relative), and a libm whose log differs by an ulp
+//     moves a breakpoint by ~1e-15 relative; both are nine orders inside
+//     the band. Conversely a tt at least 1e-6 (relative) from a breakpoint
+//     leaves ks - kl and kk - rint(kk) further than ~1e-7 from zero (their
+//     slopes in log tt are of order 0.1 to 10 on the domain), far outside
+//     decide64's 1e-12 ambiguity zone; the host test checks that too.
+//   * decide64's other two ambiguity tests, arg_l = 1 and arg_s = 1, are no
+//     decision changes; the domain ends at half the smaller of the two tt
+//     they occur at (decision_hi), so no tt of the table is near them.
+// (kDecBand is below decide32's own 1e-5 zone for tidiness only.)
+constexpr int kDecPieces = 32;  // 2 edges per piece: one edge per lane
+constexpr double kDecLo = 1e-6, kDecHiMax = 1e3, kDecBand = 1e-6;
+struct DecisionTab {
+  double edge[2 * kDecPieces];
+  unsigned code[kDecPieces];
+};
+inline void decision_tab_clear(DecisionTab& T) {
+  for (int e = 0; e < 2 * kDecPieces; ++e) T.edge[e] = __builtin_inf();
+  for (int i = 0; i < kDecPieces; ++i) T.code[i] = 0u;
+}
+// The reference's decision with the host libm, as a piece code: decide64's
+// expressions; 0 for a K outside the uniform site's tables (or a NaN).
+inline unsigned decision_code(double tt, double err) {
+  double kl, ks;
+  const double sqt = sqrt(tt);
+  const double inv_pi_sqt = 1. / (kPi * sqt);
+  const double arg_l = (kPi * tt) * err;
+  const double arg_s = (2.0 * sqrt((2.0 * kPi) * tt)) * err;
+  if (arg_l < 1.0) {
+    kl = sqrt((-2.0 * log(arg_l)) / (kPi2 * tt));
+    kl = (kl < inv_pi_sqt) ? inv_pi_sqt : kl;
+  } else {
+    kl = inv_pi_sqt;
+  }
+  if (arg_s < 1.0) {
+    ks = 2.0 + sqrt((-2.0 * tt) * log(arg_s));
+    const double b = sqt + 1.0;
+    ks = (ks < b) ? b : ks;
+  } else {
+    ks = 2.0;
+  }
+  const bool small = ks < kl;
+  const double ck = ceil(small ? ks : kl);
+  if (!(ck >= 1.0 && ck <= (double)(small ? kUniK : kSinK))) return 0u;
+  return (small ? 16u : 0u) | (unsigned)(int)ck;
+}
+// The table's upper end: half the smaller tt at which arg_l or arg_s reaches 1.
+inline double decision_hi(double err) {
+  return fmin(kDecHiMax, fmin(0.5 / (kPi * err), 0.5 / ((8.0 * kPi) * (err * err))));
+}
+inline void decision_tab(double err, DecisionTab& T) {
+  decision_tab_clear(T);
+  if (!(err > 0.0 && err < 1.0)) return;
+  const double lo = kDecLo, hi = decision_hi(err);
+  if (!(lo < hi)) return;
+  constexpr int kCells = 2048;
+  const double step = log(hi / lo) / kCells;
+  int np = 0;
+  bool full = false;
+  auto emit = [&](double s, double e, unsigned code) {
+    if (code == 0u || !(s < e)) return;
+    if (np == kDecPieces) {
+      full = true;
+      return;
+    }
+    T.edge[2 * np] = s;
+    T.edge[2 * np + 1] = e;
+    T.code[np] = code;
+    ++np;
+  };
+  double start = lo, a = lo;
+  unsigned ca = decision_code(a, err);
+  for (int i = 1; i <= kCells; ++i) {
+    const double b = i == kCells ? hi : lo * exp(step * i);
+    const unsigned cb = decision_code(b, err);
+    while (ca != cb) {
+      // adjacent doubles l < r with the piece's code at l and another at r
+      double l = a, r = b;
+      for (;;) {
+        const double m = l + (r - l) * 0.5;
+        if (!(l < m && m < r)) break;
+        if (decision_code(m, err) == ca) l = m;
+        else r = m;
+      }
+      emit(start, l * (1.0 - kDecBand), ca);
+      start = r * (1.0 + kDecBand);
+      a = r;
+      ca = decision_code(r, err);
+    }
+    a = b;
+  }
+  emit(start, hi, ca);
+  if (full) decision_tab_clear(T);  // more pieces than lanes: never answers
+}
+// The table's answer for one tt, as a wave forms it (table_decisions): the
+// number of edges <= tt is odd inside a piece. The host tests use it.
+inline unsigned decision_lookup(const DecisionTab& T, double tt, int* count = nullptr) {
+  int n = 0;
+  for (int e = 0; e < 2 * kDecPieces; ++e) n += T.edge[e] <= tt ? 1 : 0;
+  if (count) *count = n;
+  return (n & 1) ? T.code[(n >> 1) & (kDecPieces - 1)] : 0u;
+}
+
+// The five decisions of a one-boundary wave from the table. Every lane of the
+// wave is active; lane l holds edge[l]. xs: the lane's |rt|. The wave's own
+// lanes are a prefix (own = ballot of them, lane 0 is one); if their |rt| is
+// nondecreasing across lanes (checked here, never assumed), tt_j = (x - tc_j)
+// * ia2 is nondecreasing too (a rounded subtraction and a product with ia2 >
+// 0 are monotone), so the tt of the first and the last own lane bracket every
+// own lane's at each node: both inside the same piece means every lane's is.
+// True: kpack / smask hold the codes (wave-uniform). False: no answer.
+__device__ inline bool table_decisions(const DecisionTab& D, double xs, double lb, double ub,
+                                       double ia2, unsigned long long own, int lane,
+                                       unsigned& kpack, unsigned& smask) {
+  kpack = 0u;
+  smask = 0u;
+  const double prev = __shfl_up(xs, 1);
+  const bool mine = ((own >> lane) & 1ull) != 0ull;
+  if (__ballot(mine && !(prev <= xs)) != 0ull) return false;
+  const int last = __popcll(own) - 1;
+  const double xmin = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xs), 0),
+                                       __builtin_amdgcn_readlane(__double2loint(xs), 0));
+  const double xmax = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xs), last),
+                                       __builtin_amdgcn_readlane(__double2loint(xs), last));
+  const double e = D.edge[lane];
+  const double c = (ub + lb) / 2.;
+  const double d = (lb + c) / 2., f = (c + ub) / 2.;
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const double tc = j == 0 ? lb : j == 1 ? d : j == 2 ? c : j == 3 ? f : ub;
+    const int n0 = __popcll(__ballot(e <= (xmin - tc) * ia2));
+    const int n1 = __popcll(__ballot(e <= (xmax - tc) * ia2));
+    const unsigned code = D.code[(n0 >> 1) & (kDecPieces - 1)];
+    ok = ok && n0 == n1 && (n0 & 1) != 0 && code != 0u;
+    kpack |= (code & 15u) << (4 * j);
+    smask |= ((code >> 4) & 1u) << j;
+  }
+  return ok;
+}
+
 // Each lane's own five decisions, by today's operations: l0_hints for t nodes
 // 0 and 4 and its `shared` rule, decide32 for nodes 1..3 otherwise. False
 // (the lane's wave takes eng_level0_t) for invalid parameters, a node with

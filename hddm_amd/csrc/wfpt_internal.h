@@ -12,6 +12,7 @@
 namespace wfpt {
 struct Params;
 struct Knobs;
+struct DecisionTab;
 
 // Deferred-trial state of one call, slot-indexed (slot = chunk * 64 + rank
 // of the trial among its chunk's deferred trials; nslots = chunks * 64). The
@@ -89,12 +90,14 @@ int64_t partials_for(int64_t n, const Params& P, const Knobs& K);
 // without the in-wave refinement; a chunk that refines is flagged in W.redo
 // and counted as deferred), and kPassRedo runs the engine over the flagged
 // chunks (before the fold). fast_done (optional) is recorded right after the
-// level-0 / trial kernel.
+// level-0 / trial kernel. dtab (optional): the lean pass's series-decision
+// table for K.err (decision_tab; null: its waves decide per lane).
 constexpr int kPassFast = 1, kPassDeferred = 2, kPassAll = 3, kPassLean = 4, kPassRedo = 8;
 void launch_trials(int out_kind, int part, const double* x, int64_t n, const Params& P,
                    const Knobs& K, double* out, int* zeros, unsigned long long* evals, int* status,
                    int logp, const Work& W, hipStream_t s, hipEvent_t fast_done = nullptr,
-                   const Split* split = nullptr, double* trial = nullptr);
+                   const Split* split = nullptr, double* trial = nullptr,
+                   const DecisionTab* dtab = nullptr);
 // out[0..3] = {sum of nb partials, #zero trials, encoded error flags,
 // kResDeferred (defer_bits: some chunk's zero word carries kZeroDefer) |
 // kResTree (*tree_any; then *tree_any = 0)}, out[6] = *tree_any (chunks that

@@ -5,7 +5,17 @@
 //                        flagged for the engine's redo pass (wfpt_engine.hip).
 //                        The 2-D family has two sites: waves whose lanes agree
 //                        on every t node's series decision (lean_uniform_level0,
-//                        wfpt_device.hpp) and the per-lane one (eng_level0_t)
+//                        wfpt_device.hpp) and the per-lane one (eng_level0_t).
+//                        A wave learns that its lanes agree from the decision's
+//                        breakpoint table (table_decisions: its two extreme
+//                        |rt| looked up) or, where the table has no answer,
+//                        from every lane's own fp32 estimate and a vote
+//                        (l0_decisions). Static counts from the assembly with
+//                        line tables (hipcc -S -gline-tables-only): the table
+//                        stage issues ~62 VALU per lane (35 in
+//                        table_decisions, 27 in the kernel's lines around it,
+//                        the 1 / a^2 division among them), the per-lane
+//                        pre-pass 170 to 410
 // (One-block calls run level 0 and the finalize in one launch: wfpt_sum.hip.)
 #include "wfpt_kernel_common.hpp"
 
@@ -76,11 +86,12 @@ void direct_kernel(TrialArgs A, Work W, DirectArgs D) {
 #endif
 constexpr int kLeanBlock = WFPT_LEAN_BLOCK;
 static_assert(kLeanBlock % 64 == 0 && kLeanBlock <= kFastBlock, "kLeanBlock");
-static_assert(sizeof(TrialArgs) + sizeof(Work) + sizeof(RootGrids) + sizeof(UniformTabs) <= 4096,
+static_assert(sizeof(TrialArgs) + sizeof(Work) + sizeof(RootGrids) + sizeof(UniformTabs) +
+                      sizeof(DecisionTab) <= 4096,
               "lean_kernel's arguments exceed the 4 KB kernel argument segment");
 template <int MODE, bool COUNT, int OUT>
 __global__ __launch_bounds__(kLeanBlock, FastWaves<MODE>::value > 0 ? FastWaves<MODE>::value : 1)
-void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T) {
+void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T, DecisionTab D) {
 #ifdef WFPT_PHASE_TIMING
   const long long rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -104,20 +115,47 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T) {
   const unsigned long long bo = __ballot(own), bp = __ballot(own && pos);
   const int b = (bp == bo) ? 1 : 0;  // every trial upper: 1; otherwise lower first
   // kAdaptTZ: a wave of one boundary whose own lanes all reach the same
-  // (small, K) at each of the five t nodes, each by its own decision, and all
-  // pass the per-trial range test keeps the decisions in scalar registers
-  // (lean_uniform_level0). Every other wave, and a uniform wave one of whose
-  // lanes met a value the fix-up code handles, runs the generic site below.
+  // (small, K) at each of the five t nodes, by the table or each by its own
+  // decision, and all pass the per-trial range test keeps the decisions in
+  // scalar registers (lean_uniform_level0). Every other wave, and a uniform
+  // wave one of whose lanes met a value the fix-up code handles, runs the
+  // generic site below.
   bool done = false;
   if constexpr (MODE == kAdaptTZ) {
     if (bp == bo || bp == 0ull) {
       const Trial tr = trial_setup_b(x0, A.P, b != 0);
+      double lb, ub;
+      tree_root<MODE>(tr, A.P, lb, ub);
       L0Hints H;
-      unsigned kp, sm;
-      const bool okd = own && l0_decisions(tr, A.P, A.K, H, kp, sm);
-      const unsigned kp0 = __builtin_amdgcn_readfirstlane(kp);
-      const unsigned sm0 = __builtin_amdgcn_readfirstlane(sm);
-      if (__ballot(okd && kp == kp0 && sm == sm0) == bo) {
+      unsigned kp0, sm0;
+      // The table stage (table_decisions): the wave's two extreme |rt| looked
+      // up among the decision's breakpoints settle all five nodes for every
+      // lane. What l0_decisions asks besides the decisions is tested per lane
+      // here: valid parameters, x - ub > 0, and the recurrence's q0 / R where
+      // a large-time node reads them (only there are they computed).
+      H.q0 = -1.0;
+      H.R = 0.0;
+      H.ia2 = 1.0 / (A.P.a * A.P.a);
+      H.D0 = H.D4 = Decision{0, 0, 0};
+      H.ok0 = H.ok4 = H.shared = false;
+      bool tab = __ballot(own && tr.valid && tr.x - ub > 0) == bo &&
+                 table_decisions(D, tr.x, lb, ub, H.ia2, bo, lane, kp0, sm0);
+      if (tab && sm0 != 31u) {
+        const double q0 = exp_node((-kPi2 * ((tr.x - lb) * H.ia2)) * 0.5);
+        const double Rr = exp_node((kPi2 * (ub - lb)) * (0.125 * H.ia2));
+        H.q0 = q0;
+        H.R = Rr;
+        tab = __ballot(own && q0 > 1e-280 && Rr < 1e10) == bo;
+      }
+      bool uni = tab;
+      if (!tab) {  // the per-lane pre-pass and vote
+        unsigned kp, sm;
+        const bool okd = own && l0_decisions(tr, A.P, A.K, H, kp, sm);
+        kp0 = __builtin_amdgcn_readfirstlane(kp);
+        sm0 = __builtin_amdgcn_readfirstlane(sm);
+        uni = __ballot(okd && kp == kp0 && sm == sm0) == bo;
+      }
+      if (uni) {
         int kmax = 0;  // the largest K among the small-time nodes
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
@@ -125,8 +163,6 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T) {
           if (((sm0 >> j) & 1u) != 0u && kj > kmax) kmax = kj;
         }
         const UniformTab& U = T.U[b];
-        double lb, ub;
-        tree_root<MODE>(tr, A.P, lb, ub);
         const bool safe = uniform_guard((tr.x - ub) * H.ia2, (tr.v * tr.v) * (tr.x - lb), A.P.sv,
                                         U.k[kmax].bound, U.amax);
         if (__ballot(own && safe) == bo) {
@@ -135,6 +171,8 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T) {
             oc = lean_uniform_level0(tr, A.P, A.K, zgrid_uniform(R, b), U, &R.S[b][0][0], H, kp0,
                                      sm0, p, ne0, pend0, bail);
           done = __ballot(own && bail) == 0ull;
+          // counting build: the waves the table settled
+          if (COUNT && done && tab && lane == 0) atomicAdd(&W.prof[0], 1);
         }
       }
     }
@@ -152,7 +190,8 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T) {
         oc = eng_level0_t<MODE, false, true>(trial_setup_b(x0, A.P, true), A.P, A.K, R.G[1], p, f0,
                                              ne0, pend0, &R.S[1][0][0]);
     }
-    // counting build: the lean waves that took the generic site
+    // counting build: the lean waves that took the generic site (prof[0]: the
+    // ones the table settled, above)
     if (COUNT && MODE == kAdaptTZ && lane == 0) atomicAdd(&W.prof[3], 1);
   }
   if (__ballot(oc == kTree) != 0ull) {
@@ -192,7 +231,11 @@ void launch_direct(bool count, int out, const TrialArgs& A, const Work& W, hipSt
   });
 }
 
-void launch_lean(int mode, bool count, int out, const TrialArgs& A, const Work& W, hipStream_t s) {
+void launch_lean(int mode, bool count, int out, const TrialArgs& A, const Work& W, hipStream_t s,
+                 const DecisionTab* dt) {
+  DecisionTab D;  // by value, as the other tables: each lane reads its own edge
+  if (dt) D = *dt;
+  else decision_tab_clear(D);
   RootGrids R;
   root_grids(A.P, R);
   UniformTabs T;  // read by the 2-D family's uniform waves only
@@ -201,7 +244,7 @@ void launch_lean(int mode, bool count, int out, const TrialArgs& A, const Work& 
     with_build<false>(count, out, [&](auto c, auto o) {
       hipLaunchKernelGGL((lean_kernel<decltype(m)::value, decltype(c)::value, decltype(o)::value>),
                          dim3((A.n + kLeanBlock - 1) / kLeanBlock), dim3(kLeanBlock), 0, s, A, W, R,
-                         T);
+                         T, D);
     });
   });
 }

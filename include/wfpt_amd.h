@@ -715,8 +715,10 @@ int wfpt_profile_read(wfpt_ctx *ctx, double *kernel_ms, int64_t *launches, int64
  * node segments the chunk engine ran (one per node present in a listed
  * chunk). A resident full-DDM call whose level 0 is the lean pass adds to
  * counts[3] the number of its waves (64-trial chunks) that took the generic
- * per-lane site instead of the uniform-wave one (every slot 0..10 has a
- * writer: counts[8] is the z walks after level 0; slot 3 is the one a
+ * per-lane site instead of the uniform-wave one, and to counts[0] the number
+ * of its waves whose five series decisions came from the decision table and
+ * that completed on the uniform-wave site (every slot 0..10 has a writer:
+ * counts[8] is the z walks after level 0; slots 0 and 3 are the ones a
  * resident call leaves alone). */
 int wfpt_profile_lists(wfpt_ctx *ctx, int64_t counts[16], int reset);
 /* Diagnostic builds (WFPT_PHASE_TIMING): the last engine launch's per-wave
