@@ -87,6 +87,8 @@ _REG = [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD]  # ctx, ds, terms, n_terms, coe
 _GEN_CDF = [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD]
 _GEN_DRIFT = [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64]
 _GEN_RLDDM = [_VP, _PP, _PD, _I64, _PI64, _PS, _D, _D, _I64, _U64]
+# ctx, ds, terms, n_terms, coef, params, S, dt, intra_sv, max_steps, seed
+_GEN_REG = [_VP, _VP, _PT, _I32, _PD, _PP, _I64, _D, _D, _I64, _U64]
 _SIGNATURES = {
     "wfpt_last_error": (_CP, []),
     "wfpt_device_count": (_I, [_PI]),
@@ -157,6 +159,10 @@ _SIGNATURES = {
     "wfpt_wiener_like_reg_ex": (_I, _REG + [_PD, _PD]),
     "wfpt_wiener_like_reg_groups": (_I, _REG),
     "wfpt_wiener_like_reg_groups_ex": (_I, _REG + [_PD, _PD]),
+    "wfpt_gen_rts_reg_drift": (_I, _GEN_REG + [_PD, _PI64, _PI64]),
+    "wfpt_gen_rts_reg_drift_ex": (_I, _GEN_REG + [_I32, _I64, _PD, _PI64, _PI64, _PD, _PD, _PD,
+                                                  _PD, _PI64, _PI64]),
+    "wfpt_gen_rts_reg_drift_stats": (_I, _GEN_REG + [_I64, _PD, _PI64, _PI64, _PD, _I32, _PD]),
     # RT samplers and per-row RT statistics
     "wfpt_gen_rts_nodes": (_I, _GEN_CDF),
     "wfpt_gen_rts_nodes_ex": (_I, _GEN_CDF + [_PD, _PD, _PI64, _PD, _PD]),

@@ -423,6 +423,16 @@ int counts_to_offsets(const char* name, const int64_t* counts, int64_t R,
 // (wfpt.pyx:123-125), defined in capi_rl.cpp.
 double rl_rate(double alpha);
 
+// ---- defined in capi_sim.cpp ----------------------------------------------
+// The percentile arguments of a statistics request: "<name>: ..." WFPT_ERR_ARG.
+int stats_check_q(const char* name, const double* q, int32_t nq, const double* out);
+// The statistics of R rows of draws that are already in device memory (row r
+// is d_rts[off[r] .. off[r + 1]), off on the host) into host_out [R x (8 + 2
+// nq)]: plans the tiers by row length, launches them on the context's stream
+// and returns after it has drained. The context is locked; c->sim.off is used.
+int stats_device_rows(wfpt_ctx* c, const char* name, const double* d_rts, const int64_t* off,
+                      int64_t R, const double* q, int32_t nq, double* host_out);
+
 }  // namespace capi
 }  // namespace wfpt
 

@@ -1,10 +1,12 @@
-// capi_reg.cpp — the regression likelihoods of the C ABI
+// capi_reg.cpp — the regression family of the C ABI: the likelihoods
 // (hddm/models/hddm_regression.py:26-36 into wfpt.pyx:244-274;
-// reg_kernels.hip).
+// reg_kernels.hip) and the posterior predictive's trial-wise
+// drift sampler (hddm_regression.py:39-56; reg_sim_kernels.hip).
 #include "capi_internal.hpp"
 #include "capi_layout.hpp"
 #include "reg_internal.h"
 #include "rl_internal.h"  // kRlNodeMax: the per-group sum is the RL unit's launch_rl_node_sum
+#include "stats_internal.h"
 
 using namespace wfpt::capi;
 
@@ -159,9 +161,235 @@ int reg_outputs(wfpt_ctx* c, const wfpt_reg_ds* d, int32_t n_terms, double* out_
   return WFPT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The regressor's posterior predictive (reg_sim_kernel; hddm_regression.py:39-56
+// over generate.py:208-319)
+
+struct RegSimDebug {
+  double *par, *y0, *delay, *drift;
+  int64_t *n_steps, *wave_steps;
+};
+struct RegStatsReq {
+  const double* q;
+  int32_t nq;
+  double* out;  // [S x G x (8 + 2 nq)]
+};
+
+int gen_rts_reg_drift_impl(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                           int32_t n_terms, const double* coef, const wfpt_params* params,
+                           int64_t S, double dt, double intra_sv, int64_t max_steps,
+                           uint64_t seed, int32_t wave_draws, int64_t workspace_bytes,
+                           double* out, int64_t* n_unfinished, int64_t* n_invalid,
+                           const RegSimDebug& D, const RegStatsReq* sr) {
+  const std::string name = sr ? "gen_rts_reg_drift_stats" : "gen_rts_reg_drift";
+  if (int rc = reg_check_terms(terms, n_terms)) return rc;
+  if (!c || !d || !coef || !params || !n_unfinished || !n_invalid)
+    return fail(WFPT_ERR_ARG, "null pointer (context / dataset / coef / params / n_unfinished / "
+                              "n_invalid)");
+  if (!out && !sr) return fail(WFPT_ERR_ARG, "null pointer (out)");
+  if (S < 1) return fail(WFPT_ERR_ARG, name + ": S < 1");
+  if (!(dt > 0) || !std::isfinite(dt)) return fail(WFPT_ERR_ARG, name + ": dt <= 0");
+  if (!(intra_sv > 0) || !std::isfinite(intra_sv))
+    return fail(WFPT_ERR_ARG, name + ": intra_sv <= 0");
+  if (max_steps < 1 || max_steps > (int64_t)1 << 31)
+    return fail(WFPT_ERR_ARG, name + ": max_steps outside [1, 2^31]");
+  if (wave_draws < 0 || wave_draws % 64 != 0)
+    return fail(WFPT_ERR_ARG, name + ": wave_draws must be a multiple of 64 (0: default)");
+  if (workspace_bytes < 0) return fail(WFPT_ERR_ARG, name + ": negative workspace_bytes");
+  const double root = std::sqrt(dt);
+  const double step = root * intra_sv, scale = root / intra_sv;  // generate.py:258, 279
+  if (!(step > 0) || !std::isfinite(step) || !std::isfinite(scale))
+    return fail(WFPT_ERR_ARG, name + ": sqrt(dt) * intra_sv is not a usable step");
+  if (sr)
+    if (int rc = stats_check_q(name.c_str(), sr->q, sr->nq, sr->out)) return rc;
+  if (int rc = reg_check_call(c, d, terms, n_terms)) return rc;
+  const int64_t n = d->n;
+  const int32_t G = d->n_groups, C = d->C;
+  if (n >= (int64_t)1 << 31)
+    return fail(WFPT_ERR_ARG, name + ": the data set must hold < 2^31 trials");
+  // Sweeps per tile: as many as the workspace holds draws of (the sampler's
+  // 1 GiB by default), and few enough for the statistics' 32-bit row index.
+  // The counter keying makes the tiling invisible in the result.
+  const int64_t ws = workspace_bytes > 0 ? workspace_bytes : (int64_t)1 << 30;
+  int64_t spt = std::max<int64_t>(1, ws / 8 / std::max<int64_t>(n, 1));
+  spt = std::min(spt, S);
+  spt = std::min(spt, std::max<int64_t>(1, (((int64_t)1 << 31) - 1) / G));
+  // Elements per wave: one per lane until that gives every SIMD four waves
+  // (1024 SIMDs), then up to 16 per lane (gen_rts_drift_nodes' rule, per tile).
+  auto wave_of = [&](int64_t tt) {
+    return wave_draws > 0 ? (int64_t)wave_draws
+                          : 64 * std::min<int64_t>(16, std::max<int64_t>(1, tt / (64 * 4096)));
+  };
+  const int64_t tt_max = spt * n, waves_max = (tt_max + wave_of(tt_max) - 1) / wave_of(tt_max);
+  if (waves_max >= (int64_t)1 << 31)
+    return fail(WFPT_ERR_ARG, name + ": too many draws for one launch; lower workspace_bytes");
+  if (D.wave_steps && (wave_draws == 0 || spt < S))
+    return fail(WFPT_ERR_ARG, name + ": out_wave_steps needs an explicit wave_draws and a "
+                                     "workspace that holds every sweep");
+  *n_unfinished = 0;
+  *n_invalid = 0;
+  if (n == 0 && !sr) return WFPT_OK;
+  WFPT_RANGE("wfpt_gen_rts_reg_drift");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  std::vector<wfpt::Params> par((size_t)S * G);
+  for (int64_t r = 0; r < S * G; ++r) par[r] = to_params(&params[r]);
+  const bool dbg = D.par || D.y0 || D.delay || D.drift;
+  HIP_TRY(c->reg.coef.reserve(std::max<int64_t>(spt * G * C, 1)));
+  HIP_TRY(c->reg.par.reserve(spt * G));
+  HIP_TRY(c->sim.out.reserve(std::max<int64_t>(tt_max, 1)));
+  HIP_TRY(c->stats.count.reserve(2));
+  if (dbg) HIP_TRY(c->sim.u.reserve(std::max<int64_t>(10 * tt_max, 1)));
+  if (D.n_steps || D.wave_steps) HIP_TRY(c->sim.idx.reserve(tt_max + waves_max));
+  HIP_TRY(hipMemsetAsync(c->stats.count.p, 0, 2 * sizeof(unsigned long long), c->stream));
+  if (c->profile)
+    for (int k = 0; k < 2; ++k)
+      if (!c->sim.ev[k]) HIP_TRY(hipEventCreate(&c->sim.ev[k]));
+  const std::vector<int64_t>& perm = d->caller_host;  // empty: the caller's order is the stored one
+  std::vector<double> h;
+  std::vector<int64_t> hi;
+  std::vector<int64_t> goff;
+  const int K = wfpt::stats_cols(sr ? sr->nq : 0);
+  for (int64_t s0 = 0; s0 < S; s0 += spt) {
+    const int64_t st = std::min(spt, S - s0), tt = st * n;
+    const int64_t wd = wave_of(tt), waves = (tt + wd - 1) / wd;
+    HIP_TRY(hipMemcpyAsync(c->reg.coef.p, coef + s0 * G * C, (size_t)st * G * C * sizeof(double),
+                           hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->reg.par.p, par.data() + s0 * G, (size_t)st * G * sizeof(wfpt::Params),
+                           hipMemcpyHostToDevice, c->stream));
+    wfpt::RegSimCall R;
+    R.n = n;
+    R.C = C;
+    R.G = G;
+    R.n_terms = n_terms;
+    R.wave_draws = (int32_t)wd;
+    R.X = d->X.p;
+    R.group = d->group.p;
+    R.caller = d->caller.p;
+    R.coef = c->reg.coef.p;
+    R.P = c->reg.par.p;
+    R.s0 = s0;
+    R.total = tt;
+    R.dt = dt;
+    R.step = step;
+    R.scale = scale;
+    R.max_steps = (uint32_t)max_steps;
+    R.seed = seed;
+    R.out = c->sim.out.p;
+    R.par = D.par ? c->sim.u.p : nullptr;
+    R.y0 = D.y0 ? c->sim.u.p + 7 * tt : nullptr;
+    R.delay = D.delay ? c->sim.u.p + 8 * tt : nullptr;
+    R.drift = D.drift ? c->sim.u.p + 9 * tt : nullptr;
+    R.n_steps = D.n_steps ? c->sim.idx.p : nullptr;
+    R.wave_steps = D.wave_steps ? c->sim.idx.p + tt : nullptr;
+    R.counts = c->stats.count.p;
+    for (int k = 0; k < wfpt::kRegMaxTerms; ++k)
+      R.term[k] = k < n_terms ? wfpt::RegTerm{terms[k].param, terms[k].link, terms[k].col0,
+                                              terms[k].ncol}
+                              : wfpt::RegTerm{0, 0, 0, 0};
+    if (c->profile) HIP_TRY(hipEventRecord(c->sim.ev[0], c->stream));
+    wfpt::launch_reg_sim(R, c->stream);
+    HIP_TRY(hipGetLastError());
+    if (c->profile) {
+      HIP_TRY(hipEventRecord(c->sim.ev[1], c->stream));
+      HIP_TRY(hipEventSynchronize(c->sim.ev[1]));
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, c->sim.ev[0], c->sim.ev[1]));
+      c->k_ms += ms;
+      c->launches += 1;
+    }
+    if (sr) {  // row (s, g) of the tile: the stored range of group g in sweep s
+      goff.resize((size_t)st * G + 1);
+      for (int64_t s = 0; s < st; ++s)
+        for (int32_t j = 0; j < G; ++j) goff[s * G + j] = s * n + d->off_host[j];
+      goff[st * G] = tt;
+      if (int rc = stats_device_rows(c, name.c_str(), c->sim.out.p, goff.data(), st * G, sr->q,
+                                     sr->nq, sr->out + s0 * G * K))
+        return rc;
+    } else {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (tt == 0) continue;
+    // the tile's per-element arrays, stored order on the device, into the
+    // caller's order: element (s, p) is trial perm[p] of sweep s0 + s
+    auto fetch = [&](double* dst, const double* dev) -> int {
+      if (perm.empty()) {
+        HIP_TRY(hipMemcpy(dst, dev, tt * sizeof(double), hipMemcpyDeviceToHost));
+        return WFPT_OK;
+      }
+      h.resize((size_t)tt);
+      HIP_TRY(hipMemcpy(h.data(), dev, tt * sizeof(double), hipMemcpyDeviceToHost));
+      for (int64_t s = 0; s < st; ++s)
+        for (int64_t p = 0; p < n; ++p) dst[s * n + perm[p]] = h[s * n + p];
+      return WFPT_OK;
+    };
+    const std::pair<double*, const double*> copies[] = {
+        {out, R.out}, {D.y0, R.y0}, {D.delay, R.delay}, {D.drift, R.drift}};
+    for (const auto& cp : copies)
+      if (cp.first)
+        if (int rc = fetch(cp.first + s0 * n, cp.second)) return rc;
+    if (D.par) {  // (S, n, 7) on the host, field-major on the device
+      h.resize((size_t)7 * tt);
+      HIP_TRY(hipMemcpy(h.data(), R.par, 7 * tt * sizeof(double), hipMemcpyDeviceToHost));
+      for (int f = 0; f < 7; ++f)
+        for (int64_t s = 0; s < st; ++s)
+          for (int64_t p = 0; p < n; ++p)
+            D.par[((s0 + s) * n + (perm.empty() ? p : perm[p])) * 7 + f] = h[f * tt + s * n + p];
+    }
+    if (D.n_steps) {
+      hi.resize((size_t)tt);
+      HIP_TRY(hipMemcpy(hi.data(), R.n_steps, tt * sizeof(int64_t), hipMemcpyDeviceToHost));
+      for (int64_t s = 0; s < st; ++s)
+        for (int64_t p = 0; p < n; ++p)
+          D.n_steps[(s0 + s) * n + (perm.empty() ? p : perm[p])] = hi[s * n + p];
+    }
+    if (D.wave_steps)
+      HIP_TRY(hipMemcpy(D.wave_steps, R.wave_steps, waves * sizeof(int64_t),
+                        hipMemcpyDeviceToHost));
+  }
+  unsigned long long counts[2] = {0, 0};
+  HIP_TRY(hipMemcpy(counts, c->stats.count.p, sizeof(counts), hipMemcpyDeviceToHost));
+  *n_invalid = (int64_t)counts[0];
+  *n_unfinished = (int64_t)counts[1];
+  return WFPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int wfpt_gen_rts_reg_drift_ex(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                              int32_t n_terms, const double* coef, const wfpt_params* params,
+                              int64_t S, double dt, double intra_sv, int64_t max_steps,
+                              uint64_t seed, int32_t wave_draws, int64_t workspace_bytes,
+                              double* out, int64_t* n_unfinished, int64_t* n_invalid,
+                              double* out_params, double* out_y0, double* out_delay,
+                              double* out_drift, int64_t* out_n_steps, int64_t* out_wave_steps) {
+  const RegSimDebug D{out_params, out_y0, out_delay, out_drift, out_n_steps, out_wave_steps};
+  return gen_rts_reg_drift_impl(c, d, terms, n_terms, coef, params, S, dt, intra_sv, max_steps,
+                                seed, wave_draws, workspace_bytes, out, n_unfinished, n_invalid, D,
+                                nullptr);
+}
+
+int wfpt_gen_rts_reg_drift(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                           int32_t n_terms, const double* coef, const wfpt_params* params,
+                           int64_t S, double dt, double intra_sv, int64_t max_steps, uint64_t seed,
+                           double* out, int64_t* n_unfinished, int64_t* n_invalid) {
+  return gen_rts_reg_drift_impl(c, d, terms, n_terms, coef, params, S, dt, intra_sv, max_steps,
+                                seed, 0, 0, out, n_unfinished, n_invalid, RegSimDebug{}, nullptr);
+}
+
+int wfpt_gen_rts_reg_drift_stats(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                                 int32_t n_terms, const double* coef, const wfpt_params* params,
+                                 int64_t S, double dt, double intra_sv, int64_t max_steps,
+                                 uint64_t seed, int64_t workspace_bytes, double* out,
+                                 int64_t* n_unfinished, int64_t* n_invalid, const double* q,
+                                 int32_t nq, double* stats_out) {
+  const RegStatsReq sr{q, nq, stats_out};
+  return gen_rts_reg_drift_impl(c, d, terms, n_terms, coef, params, S, dt, intra_sv, max_steps,
+                                seed, 0, workspace_bytes, out, n_unfinished, n_invalid,
+                                RegSimDebug{}, &sr);
+}
 
 int wfpt_reg_dataset_create(wfpt_ctx* c, const double* rt, int64_t n, const double* X, int32_t C,
                             const int32_t* group_id, int32_t n_groups, wfpt_reg_ds** out) {

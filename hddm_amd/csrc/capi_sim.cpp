@@ -8,6 +8,18 @@
 
 using namespace wfpt::capi;
 
+int wfpt::capi::stats_check_q(const char* name, const double* q, int32_t nq, const double* out) {
+  if (nq < 0 || nq > wfpt::kStatsMaxQ)
+    return fail(WFPT_ERR_ARG, std::string(name) + ": nq outside 0..16");
+  if ((nq > 0 && !q) || !out)
+    return fail(WFPT_ERR_ARG, std::string(name) + ": null pointer (q / stats_out)");
+  for (int32_t k = 0; k < nq; ++k)
+    if (!(q[k] >= 0 && q[k] <= 100))
+      return fail(WFPT_ERR_ARG, std::string(name) + ": percentile " + std::to_string(k) +
+                                    " outside [0, 100]");
+  return WFPT_OK;
+}
+
 namespace {
 
 // The statistics a sampler call is asked for on top of its draws.
@@ -31,18 +43,6 @@ struct StatsPlan {
   int64_t global_first = 0, global_P = 0;
   bool identity = false;
 };
-
-int stats_check_q(const char* name, const double* q, int32_t nq, const double* out) {
-  if (nq < 0 || nq > wfpt::kStatsMaxQ)
-    return fail(WFPT_ERR_ARG, std::string(name) + ": nq outside 0..16");
-  if ((nq > 0 && !q) || !out)
-    return fail(WFPT_ERR_ARG, std::string(name) + ": null pointer (q / stats_out)");
-  for (int32_t k = 0; k < nq; ++k)
-    if (!(q[k] >= 0 && q[k] <= 100))
-      return fail(WFPT_ERR_ARG, std::string(name) + ": percentile " + std::to_string(k) +
-                                    " outside [0, 100]");
-  return WFPT_OK;
-}
 
 // off: R + 1 rising offsets. tier 0: by row length; 1 / 2 / 3 force the wave /
 // block / global tier, and a row the forced tier cannot hold is WFPT_ERR_ARG.
@@ -676,6 +676,17 @@ int gen_rlddm_rows_impl(wfpt_ctx* c, const wfpt_params* rows, const double* rl_r
 }
 
 }  // namespace
+
+int wfpt::capi::stats_device_rows(wfpt_ctx* c, const char* name, const double* d_rts,
+                                  const int64_t* off, int64_t R, const double* q, int32_t nq,
+                                  double* host_out) {
+  StatsPlan plan;
+  if (int rc = stats_plan(name, off, R, q, nq, 0, &plan)) return rc;
+  HIP_TRY(c->sim.off.reserve(R + 1));
+  HIP_TRY(hipMemcpyAsync(c->sim.off.p, off, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
+                         c->stream));
+  return stats_run(c, plan, d_rts, c->sim.off.p, off, R, host_out);
+}
 
 extern "C" {
 

@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "reg_internal.h"
-#include "wfpt_crlibm.hpp"
+#include "reg_predict.hpp"
 #include "wfpt_device.hpp"
 
 #pragma clang fp contract(off)
@@ -23,12 +23,10 @@ namespace {
 
 constexpr int kRegBlock = 256;
 
-// The order of the predictor is part of the contract (reg_internal.h): one
-// product, one sum per column, left to right. The empty asm keeps each product
-// out of a fused multiply-add whatever the contraction setting, as
-// rl_scan_kernel guards its update. A column is contiguous over trials, so a
-// wave reads 512 consecutive bytes per column; the coefficient row is the
-// same address for every lane of a group.
+// The predictor (its order is part of the contract, reg_internal.h) is
+// reg_predict.hpp's, shared with the posterior predictive's kernel. A column
+// is contiguous over trials, so a wave reads 512 consecutive bytes per column;
+// the coefficient row is the same address for every lane of a group.
 __global__ __launch_bounds__(kRegBlock) void reg_fill_kernel(RegFill F) {
   const int64_t i = (int64_t)blockIdx.x * kRegBlock + threadIdx.x;
   if (i >= F.n) return;
@@ -37,23 +35,7 @@ __global__ __launch_bounds__(kRegBlock) void reg_fill_kernel(RegFill F) {
   const int64_t ci = F.pred_in ? (F.caller ? F.caller[i] : i) : 0;
 #pragma unroll 1
   for (int k = 0; k < F.n_terms; ++k) {
-    const RegTerm T = F.term[k];
-    const double* col = F.X + (int64_t)T.col0 * F.n + i;
-    double eta = col[0] * b[T.col0];
-    asm volatile("" : "+v"(eta));
-    for (int c = 1; c < T.ncol; ++c) {
-      double prod = col[(int64_t)c * F.n] * b[T.col0 + c];
-      asm volatile("" : "+v"(prod));
-      eta = eta + prod;
-    }
-    double y = eta;
-    if (T.link == kRegExp) {
-      y = wfpt_cr::cr_exp(eta);
-    } else if (T.link == kRegInvLogit) {
-      const double e = wfpt_cr::cr_exp(-eta);
-      const double den = 1.0 + e;
-      y = 1.0 / den;
-    }
+    const double y = reg_predict(F.term[k], F.X + i, F.n, b);
     F.arr[(int64_t)k * F.n + i] = y;
     if (F.pred_in) F.pred_in[(int64_t)k * F.n + ci] = y;
   }

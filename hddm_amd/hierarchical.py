@@ -622,6 +622,24 @@ class HDDM:
         stats = flat.row_stats(self.signed_rt, self.node_codes, quantiles)
         return float(_opt._quantile_scores(flat, method, flat.current()[None], *stats)[0])
 
+    @staticmethod
+    def _picked_sweeps(samples, kept):
+        """The indices of `samples` evenly spaced ones of `kept` kept sweeps
+        (all of them when fewer were kept)."""
+        if kept < 1:
+            raise RuntimeError("post_pred_gen: sample() kept no sweep")
+        samples = int(samples)
+        if samples < 1:
+            raise ValueError("samples must be >= 1")
+        return np.unique(np.linspace(0, kept - 1, min(samples, kept)).round().astype(np.int64))
+
+    def _observed_stats(self, quantiles):
+        """rt_stats_rows of the observed nodes: (n_nodes, K)."""
+        order = np.argsort(self.node_codes, kind="stable")
+        offsets = np.zeros(self.n_nodes + 1, dtype=np.int64)
+        np.cumsum(self.node_counts, out=offsets[1:])
+        return _wfpt.rt_stats_rows(self.signed_rt[order], offsets, quantiles)
+
     def post_pred_rows(self, samples=500):
         """The kept sweeps a posterior predictive draws from and their node
         parameters: (picked, table) with `picked` the indices of `samples`
@@ -630,13 +648,7 @@ class HDDM:
         if not hasattr(self, "trace") or not isinstance(getattr(self, "trace_subj", None), dict) \
                 or not isinstance(self.trace_subj.get("a"), np.ndarray):
             raise RuntimeError("post_pred_gen needs the traces: run sample() first")
-        kept = self.trace_subj["a"].shape[0]
-        if kept < 1:
-            raise RuntimeError("post_pred_gen: sample() kept no sweep")
-        samples = int(samples)
-        if samples < 1:
-            raise ValueError("samples must be >= 1")
-        picked = np.unique(np.linspace(0, kept - 1, min(samples, kept)).round().astype(np.int64))
+        picked = self._picked_sweeps(samples, self.trace_subj["a"].shape[0])
         subj = {fam: self.trace_subj[fam][picked] for fam in self.FAMILIES}
         inter = {name: self.trace[name][picked][:, None] if name in self.include
                  else self.inter[name] for name in INTER}
@@ -701,11 +713,8 @@ class HDDM:
                                                np.tile(self.node_counts, S), method=method,
                                                quantiles=quantiles, seed=seed, **kw)
         sampled = sampled.reshape(S, self.n_nodes, -1)
-        order = np.argsort(self.node_codes, kind="stable")
-        offsets = np.zeros(self.n_nodes + 1, dtype=np.int64)
-        np.cumsum(self.node_counts, out=offsets[1:])
-        observed = _wfpt.rt_stats_rows(self.signed_rt[order], offsets, quantiles)
-        table = ppc.summarize(observed, sampled, _wfpt.rt_stats_names(quantiles))
+        table = ppc.summarize(self._observed_stats(quantiles), sampled,
+                              _wfpt.rt_stats_names(quantiles))
         return (table, sampled) if return_sampled else table
 
 

@@ -21,6 +21,7 @@ slice update over subjects as HDDM's subject nodes (hierarchical.py).
 * slice width 0.05 for every coefficient node (hddm_regression.py:284).
 * links run on the device and are named: identity, exp, invlogit.
 """
+import functools
 import re
 import time
 
@@ -116,6 +117,27 @@ def _parse_models(models):
             raise ValueError(f"HDDMRegressor: outcome {outcome!r} has two models")
         out.append({"outcome": outcome, "rhs": rhs, "link": link})
     return out
+
+
+def _drift_only(method):
+    if method != "drift":
+        raise ValueError("HDDMRegressor's posterior predictive simulates every trial as a "
+                         "diffusion path (method='drift'); a per-trial CDF grid is not offered")
+
+
+def _needs_trial_sampler(fn):
+    """The posterior predictive runs on the model's resident data set. A model
+    whose data set does not offer the trial-wise sampler (a host stand-in of
+    wfpt.RegDataset, or no data set at all) refuses before its arguments are
+    looked at, as the subclasses' other unsupported methods do."""
+    @functools.wraps(fn)
+    def method(self, *args, **kw):
+        if not hasattr(getattr(self, "dataset", None), "gen_rts_drift"):
+            raise NotImplementedError(
+                "the regressor's posterior predictive needs a data set with the on-device "
+                "trial-wise sampler (wfpt.RegDataset.gen_rts_drift)")
+        return fn(self, *args, **kw)
+    return method
 
 
 class HDDMRegressor(HDDM):
@@ -329,7 +351,76 @@ class HDDMRegressor(HDDM):
         group.update(inter)
         return group, subj
 
+    # -- posterior predictive --------------------------------------------------
+    @_needs_trial_sampler
+    def post_pred_rows(self, samples=500):
+        """The kept sweeps a posterior predictive draws from and their node
+        rows: (picked, coef_tables (S, n_nodes, C), param_tables (S, n_nodes,
+        8)), `picked` by HDDM.post_pred_rows' rule (evenly spaced kept sweeps).
+        A group-only coefficient comes from its trace, a subject-level one
+        from the subject traces through the node's subject."""
+        if not isinstance(getattr(self, "trace", None), dict) \
+                or not isinstance(getattr(self, "trace_subj", None), dict):
+            raise RuntimeError("post_pred_gen needs the traces: run sample() first")
+        picked = self._picked_sweeps(samples, len(self.trace[self.coef_names[0]]))
+        B = np.empty((picked.size, self.n_nodes, self.n_coef))
+        for j, nm in enumerate(self.coef_names):
+            B[:, :, j] = self.trace[nm][picked][:, None] if self.group_only_regressors \
+                else self.trace_subj[nm][picked][:, self.node_subj]
+        subj = {fam: self.trace_subj[fam][picked] for fam in self.FAMILIES}
+        inter = {name: self.trace[name][picked][:, None] if name in self.include
+                 else self.inter[name] for name in INTER}
+        return picked, B, self._table_of((picked.size,), subj, inter)
+
+    @_needs_trial_sampler
+    def post_pred_gen(self, samples=500, seed=None, dt=1e-4, method="drift"):
+        """Posterior predictive data (kabuki.analyze.post_pred_gen over
+        wfpt_reg_like's random(), hddm_regression.py:39-56): for each of
+        `samples` evenly spaced kept sweeps, one RT per trial of the data,
+        simulated as a diffusion path with time step dt at the trial's own
+        regressed parameters by ONE RegDataset.gen_rts_drift call (the
+        parameters are formed on the device; the reference loops over trials
+        and needs keep_regressor_trace=True). The draws come from the DDM
+        alone: p_outlier's mixture is not simulated.
+
+        Returns a DataFrame with columns sample (index of the kept sweep), node
+        (index into node_keys), trial (row of the model's data frame), rt
+        (signed) and response (1 upper / 0 lower)."""
+        import pandas as pd
+        _drift_only(method)
+        picked, B, P = self.post_pred_rows(samples)
+        if seed is None:
+            seed = int(self.rng.integers(0, 2 ** 63))
+        rts = self.dataset.gen_rts_drift(self.reg_model, B, P, dt=dt, seed=seed).ravel()
+        n = self.n_trials
+        return pd.DataFrame({"sample": np.repeat(picked, n),
+                             "node": np.tile(self.node_codes, picked.size),
+                             "trial": np.tile(np.arange(n), picked.size),
+                             "rt": rts, "response": (rts > 0).astype(np.int64)})
+
+    @_needs_trial_sampler
+    def post_pred_stats(self, samples=500, seed=None, dt=1e-4, method="drift",
+                        quantiles=(10, 30, 50, 70, 90), return_sampled=False):
+        """The posterior predictive check as HDDM.post_pred_stats:
+        post_pred_gen's draws (same arguments, same seed: the same draws)
+        reduced to gen_ppc_stats' statistics per (sweep, node) on the device by
+        ONE RegDataset.gen_rts_drift_stats call (no draw is copied to the
+        host), the observed nodes by one wfpt.rt_stats_rows call, and
+        ppc.summarize compares the two. p_outlier's mixture is not simulated.
+
+        Returns ppc.summarize's DataFrame indexed by (node, stat); with
+        return_sampled=True also the sampled statistics (len(picked), n_nodes,
+        K) in wfpt.rt_stats_names' order."""
+        from . import ppc
+        _drift_only(method)
+        picked, B, P = self.post_pred_rows(samples)
+        if seed is None:
+            seed = int(self.rng.integers(0, 2 ** 63))
+        sampled = self.dataset.gen_rts_drift_stats(self.reg_model, B, P, dt=dt, seed=seed,
+                                                   quantiles=quantiles)
+        table = ppc.summarize(self._observed_stats(quantiles), sampled,
+                              _wfpt.rt_stats_names(quantiles))
+        return (table, sampled) if return_sampled else table
+
     node_logp_multi = _refuses("HDDMRegressor scores one table per call")
     optimize = quantile_objective = _refuses("the regressor's point fits are not implemented")
-    post_pred_rows = post_pred_gen = post_pred_stats = _refuses(
-        "the regressor's posterior predictive is not implemented")

@@ -32,7 +32,10 @@ RLDDM sequences in closed loop on the device (hddm/generate.py:430-516: every
 trial's drift comes from the Q values the earlier simulated trials left), and
 `gen_rlddm_stats_rows` reduces its draws likewise. `RegDataset(rt, design)` keeps a
 design matrix resident and forms HDDMRegressor's trial-wise parameters
-link(design . coefficients) on the device (hddm_regression.py:26-36).
+link(design . coefficients) on the device (hddm_regression.py:26-36);
+`RegDataset.gen_rts_drift` / `gen_rts_drift_stats` simulate one diffusion path
+per (sweep, trial) at those trial-wise parameters, formed on the device as the
+walk picks the trial up (the regression node's random(), hddm_regression.py:39-56).
 
 Shared pieces, each stated once: the samplers' argument rules (`_sampler_table`,
 `_cdf_prep`, `_drift_prep` / `_drift_seed`, `_check_drawn`, `_check_finished`)
@@ -1252,6 +1255,122 @@ class RegDataset(_Resident):
         if not terms:
             return out
         return out, tr, {m[0]: pr[k] for k, m in enumerate(model)}
+
+    # The posterior predictive's trial-wise drift sampler
+    # (wfpt_gen_rts_reg_drift).
+
+    def _sim_prep(self, model, coef_tables, params, dt, intra_sv, seed, max_t, unfinished,
+                  invalid, wave_draws, max_workspace):
+        """The checked arguments of gen_rts_drift[_stats], none of which needs
+        the device: (terms, n_terms, coef (S, G, C), params (S, G, 8), S, dt,
+        intra_sv, max_steps, seed, wave_draws, workspace bytes)."""
+        T, nt = _reg_terms(model, self.n_cols)
+        G, C = self.n_groups, self.n_cols
+        bt = np.ascontiguousarray(coef_tables, dtype=np.float64)
+        pm = np.ascontiguousarray(params, dtype=np.float64)
+        bt = bt[None] if bt.ndim == 2 else bt
+        pm = pm[None] if pm.ndim == 2 else pm
+        if bt.ndim != 3 or bt.shape[0] < 1 or bt.shape[1:] != (G, C):
+            raise ValueError(f"coef_tables must have shape (S, {G}, {C}) with S >= 1, or "
+                             f"({G}, {C})")
+        S = bt.shape[0]
+        if pm.shape != (S, G, 8):
+            raise ValueError(f"params must have shape ({S}, {G}, 8)")
+        dt, intra_sv, max_steps, _ = _drift_prep(S * G, dt, intra_sv, None, max_t, unfinished)
+        if invalid not in ("raise", "nan"):
+            raise ValueError("invalid must be 'raise' or 'nan'")
+        wd = 0 if wave_draws is None else int(wave_draws)
+        if wd < 0 or wd % 64:
+            raise ValueError("wave_draws must be a positive multiple of 64")
+        ws = 0 if max_workspace is None else int(max_workspace)
+        if ws < 0:
+            raise ValueError("max_workspace must be positive")
+        return T, nt, bt, pm, S, dt, intra_sv, max_steps, _drift_seed(seed), wd, ws
+
+    def _sim_done(self, rc, nun, ninv, S, max_steps, max_t, unfinished, invalid):
+        _lib.check(rc)
+        if ninv.value and invalid == "raise":
+            raise RuntimeError(f"wfpt_amd: {ninv.value} of {S * self.n} (sweep, trial) pairs have "
+                               "parameters that cannot be simulated (a non-finite parameter, "
+                               "a <= 0, or a start point outside [0, 1])")
+        _check_finished(nun.value, S * self.n, max_steps, max_t, unfinished)
+
+    def gen_rts_drift(self, model, coef_tables, params, dt=1e-4, intra_sv=1., seed=None,
+                      max_t=20., unfinished='raise', invalid='raise', return_debug=False,
+                      wave_draws=None, max_workspace=None):
+        """The regression node's random() (hddm_regression.py:39-56: one
+        simulated diffusion path per trial at the trial's own parameters,
+        generate.py:208-319) for S sweeps in one call (wfpt_gen_rts_reg_drift):
+        the trial-wise parameters are formed on the device from the resident
+        design matrix at the moment a lane walks the (sweep, trial).
+
+        model: wiener_like_reg_groups' term list. coef_tables (S, G, C) and
+        params (S, G, 8): sweep s's coefficient and parameter row of each
+        group (2-D: one sweep; a regressed parameter's column and p_outlier
+        are ignored). Returns the (S, n) signed RTs in the caller's order.
+
+        seed: the device's Philox4x32-10 streams (None: from NumPy's global
+        RNG). Trial i of sweep s is bit for bit draw s of row i of
+        gen_rts_from_drift_nodes over the trials' parameters: it depends on
+        (seed, s, i) only, not on the grouping. A walk cut after
+        ceil(max_t / dt) steps is NaN (unfinished='raise': RuntimeError with
+        the count); so is a trial whose parameters cannot be walked, e.g. a
+        predicted a <= 0 (invalid='raise': RuntimeError with the count).
+
+        return_debug: also a dict of `params` (S, n, 7) the formed v, sv, a,
+        z, sz, t, st, and `y0`, `delay`, `drift`, `n_steps` (S, n).
+        wave_draws (elements handed to one wave, a multiple of 64; with
+        return_debug then also `wave_steps`) and max_workspace (device bytes
+        for the draws, default 1 GiB: more sweeps run in tiles) change no
+        value."""
+        T, nt, bt, pm, S, dt, intra_sv, max_steps, seed, wd, ws = self._sim_prep(
+            model, coef_tables, params, dt, intra_sv, seed, max_t, unfinished, invalid,
+            wave_draws, max_workspace)
+        n = self.n
+        out = np.empty((S, n), dtype=np.float64)
+        nun, ninv = ctypes.c_int64(), ctypes.c_int64()
+        head = (self.ctx.handle, self.handle, T, nt, _lib.dptr(bt), pm.ctypes.data_as(_lib._PP), S,
+                dt, intra_sv, max_steps, seed)
+        if return_debug or wd or ws:
+            dbg = {}
+            if return_debug:
+                dbg["params"] = np.empty((S, n, 7))
+                dbg.update((k, np.empty((S, n))) for k in ("y0", "delay", "drift"))
+                dbg["n_steps"] = np.empty((S, n), dtype=np.int64)
+                if wd:
+                    dbg["wave_steps"] = np.empty(-(-S * n // wd), dtype=np.int64)
+            i64 = {k: _i64ptr(dbg[k]) if k in dbg else None for k in ("n_steps", "wave_steps")}
+            rc = _lib.wfpt_gen_rts_reg_drift_ex(
+                *head, wd, ws, _lib.dptr(out), ctypes.byref(nun), ctypes.byref(ninv),
+                _optr(dbg.get("params")), _optr(dbg.get("y0")), _optr(dbg.get("delay")),
+                _optr(dbg.get("drift")), i64["n_steps"], i64["wave_steps"])
+        else:
+            rc = _lib.wfpt_gen_rts_reg_drift(*head, _lib.dptr(out), ctypes.byref(nun),
+                                             ctypes.byref(ninv))
+        self._sim_done(rc, nun, ninv, S, max_steps, max_t, unfinished, invalid)
+        return (out, dbg) if return_debug else out
+
+    def gen_rts_drift_stats(self, model, coef_tables, params, dt=1e-4, intra_sv=1., seed=None,
+                            max_t=20., unfinished='raise', invalid='raise',
+                            quantiles=PPC_QUANTILES, return_draws=False, max_workspace=None):
+        """gen_rts_drift's draws (same arguments, same seed: the same draws)
+        reduced to rt_stats_rows' statistics per (sweep, group) while they are
+        still in device memory (wfpt_gen_rts_reg_drift_stats): returns (S, G,
+        8 + 2 len(quantiles)) in rt_stats_names' order, and with
+        return_draws=True also the (S, n) draws."""
+        q = _check_quantiles(quantiles)
+        T, nt, bt, pm, S, dt, intra_sv, max_steps, seed, _, ws = self._sim_prep(
+            model, coef_tables, params, dt, intra_sv, seed, max_t, unfinished, invalid, None,
+            max_workspace)
+        stats = np.empty((S, self.n_groups, 8 + 2 * q.size))
+        out = np.empty((S, self.n), dtype=np.float64) if return_draws else None
+        nun, ninv = ctypes.c_int64(), ctypes.c_int64()
+        rc = _lib.wfpt_gen_rts_reg_drift_stats(
+            self.ctx.handle, self.handle, T, nt, _lib.dptr(bt), pm.ctypes.data_as(_lib._PP), S, dt,
+            intra_sv, max_steps, seed, ws, _optr(out), ctypes.byref(nun), ctypes.byref(ninv),
+            _lib.dptr(q), q.size, _lib.dptr(stats))
+        self._sim_done(rc, nun, ninv, S, max_steps, max_t, unfinished, invalid)
+        return (stats, out) if return_draws else stats
 
 
 def _rl_host(x, response, feedback, split_by, x_optional=False):

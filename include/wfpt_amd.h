@@ -364,6 +364,67 @@ int wfpt_wiener_like_reg_groups_ex(wfpt_ctx *ctx, const wfpt_reg_ds *ds,
                                    const wfpt_knobs *k, double *out_logp, double *out_trial,
                                    double *out_pred);
 
+/* The regressor's posterior predictive: one simulated RT per (sweep, trial),
+ * each at the trial's own regressed parameters (wfpt_reg_like's random(),
+ * hddm_regression.py:39-56, which calls gen_rts(size=1, method='drift') per
+ * trial; the walk is _gen_rts_from_simulated_drift, generate.py:208-319, as in
+ * wfpt_gen_rts_drift_nodes, without the in-trial switch).
+ *   coef    S * n_groups * C: sweep s's coefficient row of group g at
+ *           (s * n_groups + g) * C
+ *   params  S * n_groups rows: the non-regressed fields of a trial come from
+ *           row s * n_groups + its group (a regressed field and p_outlier are
+ *           ignored)
+ *   out     S * n signed RTs in the caller's order: out[s * n + i] is trial i
+ * A trial's parameters are formed on the device when a lane picks the (sweep,
+ * trial) up, by the order and link contract above: bit for bit what
+ * wfpt_wiener_like_reg_groups_ex returns in out_pred for sweep s's rows.
+ * Random numbers: wfpt_gen_rts_drift_nodes' streams at counter {s lo, s hi, i,
+ * stream}: out[s * n + i] is bit for bit draw s of row i of a
+ * wfpt_gen_rts_drift_nodes table that holds the trials' parameters in the
+ * caller's order. It depends on (seed, s, i) and the parameters only, not on
+ * the grouping, the stored order, wave_draws or workspace_bytes.
+ * A trial whose formed parameters cannot be walked (one is not finite, a <= 0,
+ * z - sz / 2 < 0 or z + sz / 2 > 1: only the device sees them) is NaN and
+ * counted in *n_invalid; a walk that has not crossed after max_steps steps is
+ * NaN and counted in *n_unfinished.
+ * WFPT_ERR_ARG before any device work: null pointers, S < 1, dt <= 0,
+ * intra_sv <= 0, max_steps outside [1, 2^31], the term-list errors of
+ * wfpt_wiener_like_reg, a data set of another context or of 2^31 trials or
+ * more. */
+int wfpt_gen_rts_reg_drift(wfpt_ctx *ctx, const wfpt_reg_ds *ds, const wfpt_reg_term *terms,
+                           int32_t n_terms, const double *coef, const wfpt_params *params,
+                           int64_t S, double dt, double intra_sv, int64_t max_steps,
+                           uint64_t seed, double *out, int64_t *n_unfinished,
+                           int64_t *n_invalid);
+/* As wfpt_gen_rts_reg_drift (hddm_regression.py:39-56, generate.py:208-319),
+ * for tests and measurements. wave_draws: (sweep, trial) elements handed to one
+ * wave, a multiple of 64 (0: the library's choice). workspace_bytes: device
+ * bytes for the draws (0: 1 GiB); more sweeps than fit run in tiles. Neither
+ * changes a value. Per (sweep, trial) in the caller's order, each nullable:
+ * out_params [S * n * 7] the formed v, sv, a, z, sz, t, st; out_y0, out_delay,
+ * out_drift (NaN for an invalid trial); out_n_steps (0 for an invalid trial).
+ * out_wave_steps [ceil(S * n / wave_draws)]: needs wave_draws > 0 and a
+ * workspace that holds every sweep. */
+int wfpt_gen_rts_reg_drift_ex(wfpt_ctx *ctx, const wfpt_reg_ds *ds, const wfpt_reg_term *terms,
+                              int32_t n_terms, const double *coef, const wfpt_params *params,
+                              int64_t S, double dt, double intra_sv, int64_t max_steps,
+                              uint64_t seed, int32_t wave_draws, int64_t workspace_bytes,
+                              double *out, int64_t *n_unfinished, int64_t *n_invalid,
+                              double *out_params, double *out_y0, double *out_delay,
+                              double *out_drift, int64_t *out_n_steps, int64_t *out_wave_steps);
+/* wfpt_gen_rts_reg_drift (hddm_regression.py:39-56, generate.py:208-319)
+ * followed by the statistics of its draws (utils.py:241-265) while they are
+ * still in device memory: row (s, g) holds sweep s's draws of group g's trials,
+ * stats_out [S * n_groups * (8 + 2 nq)] is what wfpt_rt_stats_rows gives for
+ * them. out may be NULL: no draw is copied to the host; both NaN counts are
+ * returned either way. A NaN counts in its row's n and in neither boundary. */
+int wfpt_gen_rts_reg_drift_stats(wfpt_ctx *ctx, const wfpt_reg_ds *ds,
+                                 const wfpt_reg_term *terms, int32_t n_terms, const double *coef,
+                                 const wfpt_params *params, int64_t S, double dt, double intra_sv,
+                                 int64_t max_steps, uint64_t seed, int64_t workspace_bytes,
+                                 double *out, int64_t *n_unfinished, int64_t *n_invalid,
+                                 const double *q, int32_t nq, double *stats_out);
+
 /* ---- DMAT / Tuerlinckx CDF ---------------------------------------------- */
 /* Per-trial CDF of signed RTs with the outlier mixture, exactly
  * cdfdif_wrapper.dmat_cdf_array(x, v, sv, a, z, sz, t, st, p_outlier, w_outlier)
