@@ -177,6 +177,13 @@ _SIGNATURES = {
     "wfpt_gen_rlddm_rows_stats": (_I, _GEN_RLDDM + [_PD, _PI64, _PI64, _I64, _PD, _I32, _PD]),
     "wfpt_rt_stats_rows": (_I, [_VP, _PD, _PI64, _I64, _PD, _I32, _PD]),
     "wfpt_rt_stats_rows_ex": (_I, [_VP, _PD, _PI64, _I64, _PD, _I32, _I32, _PD]),
+    # model comparison: per-sweep sums + per-trial statistics over S sweeps
+    "wfpt_pointwise_nodes": (_I, [_VP, _VP, _PP, _I64, _PK, _I64, _PD, _PD, _PI64]),
+    "wfpt_pointwise_rlddm_nodes": (_I, [_VP, _VP, _PD, _PP, _I64, _PK, _I64, _PD, _PD, _PI64,
+                                        _PI64]),
+    "wfpt_pointwise_reg_groups": (_I, [_VP, _VP, _PT, _I32, _PD, _PP, _I64, _PK, _I64, _PD, _PD,
+                                       _PI64]),
+    "wfpt_pointwise_profile": (_I, [_VP, _PD, _I]),
 }
 # diagnostics only: A/B runs may load an older library build without them
 _OPTIONAL = ("wfpt_profile_lists", "wfpt_debug_waves")
@@ -289,6 +296,13 @@ class Context:
         a = (_D * 4)()
         check(wfpt_profile_stages(self.handle, a, 1 if reset else 0))
         return dict(zip(("density", "scan", "normalise", "draws"), a))
+
+    def pointwise_profile(self, reset=False):
+        """Device ms of the model-comparison pass's accumulate kernel since the
+        last reset (wfpt_pointwise_profile; profiled passes only)."""
+        ms = _D()
+        check(wfpt_pointwise_profile(self.handle, ctypes.byref(ms), 1 if reset else 0))
+        return ms.value
 
     def profile_lists(self, reset=False):
         """Deferred-pass list sizes (include/wfpt_amd.h: wfpt_profile_lists)."""

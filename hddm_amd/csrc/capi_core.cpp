@@ -895,6 +895,91 @@ int nodes_check(wfpt_ctx* c, const wfpt_ds* d, const wfpt_params* per_node, cons
   if (!d->node.p) return fail(WFPT_ERR_ARG, "dataset was created without node ids");
   return WFPT_OK;
 }
+
+// ---- the model-comparison pass (pointwise_kernels.hip) ------
+
+int64_t pointwise_tile(int64_t max_workspace, int64_t len, int64_t S, int64_t nodes) {
+  const int64_t ws = max_workspace > 0 ? max_workspace : (int64_t)1 << 30;
+  int64_t T = std::max<int64_t>(1, ws / (8 * std::max<int64_t>(len, 1)));
+  if (nodes > 0) T = std::min<int64_t>(T, std::max<int64_t>(1, ((int64_t)INT32_MAX / 2) / nodes));
+  return std::min<int64_t>(T, std::max<int64_t>(S, 1));
+}
+
+static wfpt::PointwiseState pointwise_state(wfpt_ctx* c) {
+  const int64_t len = c->pw.len;
+  double* s = c->pw.st.p;
+  return wfpt::PointwiseState{s, s + len, s + 2 * len, s + 3 * len, c->pw.cnt.p,
+                              c->pw.cnt.p + len};
+}
+
+int pointwise_begin(wfpt_ctx* c, int64_t len) {
+  c->pw.len = len;
+  const size_t n = (size_t)std::max<int64_t>(len, 1);
+  HIP_TRY(c->pw.st.reserve(4 * n));
+  HIP_TRY(c->pw.cnt.reserve(2 * n));
+  HIP_TRY(c->pw.out.reserve(4 * n));
+  // all zero bytes is the empty state (k = 0: the first finite term sets m and r)
+  HIP_TRY(hipMemsetAsync(c->pw.st.p, 0, 4 * n * sizeof(double), c->stream));
+  HIP_TRY(hipMemsetAsync(c->pw.cnt.p, 0, 2 * n * sizeof(int32_t), c->stream));
+  if (c->profile && !c->pw.ev[0]) {
+    HIP_TRY(hipEventCreate(&c->pw.ev[0]));
+    HIP_TRY(hipEventCreate(&c->pw.ev[1]));
+  }
+  return WFPT_OK;
+}
+
+int pointwise_add(wfpt_ctx* c, const double* lp, int64_t T) {
+  if (c->pw.len <= 0 || T <= 0) return WFPT_OK;
+  if (c->profile) HIP_TRY(hipEventRecord(c->pw.ev[0], c->stream));
+  wfpt::launch_pointwise_accumulate(lp, T, c->pw.len, pointwise_state(c), c->stream);
+  HIP_TRY(hipGetLastError());
+  if (c->profile) {  // a profiled pass waits for every tile's kernel: its time alone
+    float ms = 0.f;
+    HIP_TRY(hipEventRecord(c->pw.ev[1], c->stream));
+    HIP_TRY(hipEventSynchronize(c->pw.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, c->pw.ev[0], c->pw.ev[1]));
+    c->pw.ms += ms;
+  }
+  return WFPT_OK;
+}
+
+int pointwise_finish(wfpt_ctx* c, int64_t S, const int64_t* to, double* out_stats,
+                     int64_t* out_ninf_total) {
+  const int64_t len = c->pw.len;
+  *out_ninf_total = 0;
+  if (len <= 0) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return WFPT_OK;
+  }
+  wfpt::launch_pointwise_finish(pointwise_state(c), len, S, c->pw.out.p, c->stream);
+  HIP_TRY(hipGetLastError());
+  if (!to) {
+    HIP_TRY(hipMemcpyAsync(out_stats, c->pw.out.p, 4 * len * sizeof(double),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  } else {
+    std::vector<double> h(4 * (size_t)len);
+    HIP_TRY(hipMemcpyAsync(h.data(), c->pw.out.p, 4 * len * sizeof(double),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int f = 0; f < 4; ++f)
+      for (int64_t i = 0; i < len; ++i) out_stats[f * len + to[i]] = h[f * len + i];
+  }
+  int64_t total = 0;
+  for (int64_t i = 0; i < len; ++i) total += (int64_t)out_stats[3 * len + i];
+  *out_ninf_total = total;
+  return WFPT_OK;
+}
+
+void pointwise_all_inf(int64_t len, int64_t S, double* out_stats, int64_t* out_ninf_total) {
+  for (int64_t i = 0; i < len; ++i) {
+    out_stats[i] = -INFINITY;
+    out_stats[len + i] = std::nan("");
+    out_stats[2 * len + i] = -INFINITY;
+    out_stats[3 * len + i] = (double)S;
+  }
+  *out_ninf_total = len * S;
+}
 }  // namespace capi
 }  // namespace wfpt
 
@@ -975,6 +1060,55 @@ int wfpt_wiener_like_nodes_multi_ex(wfpt_ctx* c, const wfpt_ds* d, const wfpt_pa
 int wfpt_wiener_like_nodes_multi(wfpt_ctx* c, const wfpt_ds* d, const wfpt_params* tables,
                                  int32_t n_tables, const wfpt_knobs* k, double* out) {
   return wfpt_wiener_like_nodes_multi_ex(c, d, tables, n_tables, k, out, nullptr);
+}
+
+int wfpt_pointwise_nodes(wfpt_ctx* c, const wfpt_ds* d, const wfpt_params* tables, int64_t S,
+                         const wfpt_knobs* k, int64_t max_workspace, double* out_sums,
+                         double* out_stats, int64_t* out_ninf_total) {
+  if (!out_stats || !out_ninf_total) return fail(WFPT_ERR_ARG, "null pointer");
+  if (int rc = nodes_check(c, d, tables, k, out_sums)) return rc;
+  if (S < 1) return fail(WFPT_ERR_ARG, "S < 1");
+  const wfpt::Knobs K = to_knobs(k);
+  WFPT_RANGE("wfpt_pointwise_nodes");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const int32_t m = d->n_nodes;
+  const int64_t n = d->n;
+  const int64_t tile = pointwise_tile(max_workspace, n, S, m);
+  if (int rc = pointwise_begin(c, n)) return rc;
+  for (int64_t s0 = 0; s0 < S; s0 += tile) {
+    // the multi-table node call's sequence on sweeps [s0, s0 + T): the publish
+    // returns once the tile's sums are final, its rare trials settled in c->lp
+    const int32_t T = (int32_t)std::min<int64_t>(tile, S - s0);
+    const int64_t rows = (int64_t)T * m;
+    wfpt::NodeSum ns{};
+    if (int rc = nodes_launch(c, d, tables + s0 * m, K, &ns, T)) return nodes_recover(c, rc);
+    if (rows > 0) {
+      if (int rc = nodes_publish(c, d, ns, T)) return rc;
+    } else {
+      if (hipStreamSynchronize(c->stream) != hipSuccess)
+        return nodes_recover(c, fail(WFPT_ERR_HIP, "node pass failed on the device"));
+      (void)hipMemset(c->ncnt.p, 0, 4 * sizeof(int));
+    }
+    if (int rc = finish_profile(c)) return rc;
+    std::memcpy(out_sums + s0 * m, c->mnode.h, (size_t)rows * sizeof(double));
+    if (int rc = pointwise_add(c, c->lp.p, T)) return rc;
+  }
+  std::vector<int64_t> perm;
+  if (d->perm.p && n > 0) {
+    perm.resize(n);
+    HIP_TRY(hipMemcpyAsync(perm.data(), d->perm.p, n * sizeof(int64_t), hipMemcpyDeviceToHost,
+                           c->stream));
+  }
+  return pointwise_finish(c, S, perm.empty() ? nullptr : perm.data(), out_stats, out_ninf_total);
+}
+
+int wfpt_pointwise_profile(wfpt_ctx* c, double* accumulate_ms, int reset) {
+  if (!c || !accumulate_ms) return fail(WFPT_ERR_ARG, "null pointer");
+  std::lock_guard<std::mutex> lk(c->mu);
+  *accumulate_ms = c->pw.ms;
+  if (reset) c->pw.ms = 0.0;
+  return WFPT_OK;
 }
 
 int wfpt_wiener_like_nodes_local(wfpt_ctx* c, const wfpt_ds* d, const wfpt_params* per_node,

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/wfpt_amd.h"
+#include "pointwise_internal.h"
 #include "wfpt_device.hpp"
 #include "wfpt_internal.h"
 
@@ -202,6 +203,21 @@ struct StatsWork {
   DevBuf<unsigned long long> count;  // NaN draws of a drift call whose draws stay on the device
 };
 
+// ... of the model-comparison pass (pointwise_kernels.hip): the per-trial
+// accumulator state, one array per field, and the finished statistics
+struct PointwiseWork {
+  DevBuf<double> st;    // [4 x len] m | r | mean | M2
+  DevBuf<int32_t> cnt;  // [2 x len] k | n_inf
+  DevBuf<double> out;   // [4 x len] lppd | p_waic | mean | n_inf
+  int64_t len = 0;      // trials of the pass in progress
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  double ms = 0.0;      // profiled time of the accumulate kernel
+  ~PointwiseWork() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 }  // namespace capi
 }  // namespace wfpt
 
@@ -305,6 +321,7 @@ struct wfpt_ctx {
   wfpt::capi::RegWork reg;
   wfpt::capi::SimWork sim;
   wfpt::capi::StatsWork stats;
+  wfpt::capi::PointwiseWork pw;
 };
 
 struct wfpt_ds : wfpt::capi::DsBase {
@@ -422,6 +439,26 @@ int counts_to_offsets(const char* name, const int64_t* counts, int64_t R,
 // The learning rate of the unbounded alpha as every RL entry forms it
 // (wfpt.pyx:123-125), defined in capi_rl.cpp.
 double rl_rate(double alpha);
+
+// The model-comparison pass, shared by the three
+// wfpt_pointwise_* entries; the context is locked by the caller.
+// Sweeps per tile: max(1, max_workspace / (8 len)), 1 GiB when max_workspace
+// <= 0, at most S and at most (INT32_MAX / 2) / nodes tables per node call.
+int64_t pointwise_tile(int64_t max_workspace, int64_t len, int64_t S, int64_t nodes);
+// Sizes and clears the state of `len` trials.
+int pointwise_begin(wfpt_ctx* c, int64_t len);
+// T sweeps of terms (sweep t's trial i at lp[t len + i], device memory) into the
+// state; enqueued on the context's stream, behind the kernels that wrote lp.
+int pointwise_add(wfpt_ctx* c, const double* lp, int64_t T);
+// The statistics after S sweeps: out_stats[f len + to[i]] = field f (lppd,
+// p_waic, mean, n_inf) of stored trial i; to (host, nullable: identity) is the
+// caller's position of a stored trial. *out_ninf_total = the n_inf summed.
+// Returns after the stream has drained.
+int pointwise_finish(wfpt_ctx* c, int64_t S, const int64_t* to, double* out_stats,
+                     int64_t* out_ninf_total);
+// A pass that runs no device work (p_outlier outside [0, 1]: every term is
+// -inf): the statistics of `len` trials that saw S zero densities each.
+void pointwise_all_inf(int64_t len, int64_t S, double* out_stats, int64_t* out_ninf_total);
 
 // ---- defined in capi_sim.cpp ----------------------------------------------
 // The percentile arguments of a statistics request: "<name>: ..." WFPT_ERR_ARG.

@@ -161,6 +161,39 @@ int reg_outputs(wfpt_ctx* c, const wfpt_reg_ds* d, int32_t n_terms, double* out_
   return WFPT_OK;
 }
 
+// The groups call after its checks, the context locked: the G per-group sums
+// into out_logp, every trial's term left in c->lp (stored order).
+int reg_groups_locked(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                      int32_t n_terms, const double* coef, const wfpt_params* per_group,
+                      const wfpt::Knobs& K, double p_outlier, bool want_pred, double* out_logp) {
+  const int32_t G = d->n_groups;
+  const int64_t n = d->n;
+  int term_of[7] = {-1, -1, -1, -1, -1, -1, -1};
+  for (int32_t t = 0; t < n_terms; ++t) term_of[terms[t].param] = t;
+  // v, sv, a, z and t per trial from the group rows unless regressed; sz and st
+  // stay scalars of the pass unless regressed, as in the single call, so a
+  // group's trials take the kernel the single call on that group takes
+  int expand = 0;
+  for (int f : {0, 1, 2, 3, 5})
+    if (term_of[f] < 0) expand |= 1 << f;
+  std::vector<wfpt::Params> par(G);
+  for (int32_t j = 0; j < G; ++j) par[j] = to_params(&per_group[j]);
+  HIP_TRY(c->reg.par.reserve(G));
+  HIP_TRY(hipMemcpyAsync(c->reg.par.p, par.data(), G * sizeof(wfpt::Params),
+                         hipMemcpyHostToDevice, c->stream));
+  if (int rc = reg_fill(c, d, terms, n_terms, coef, G, true, expand, want_pred))
+    return rc;
+  double* field[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int f = 0, slot = n_terms; f < 7; ++f) {
+    if (term_of[f] >= 0) field[f] = c->reg.arr.p + (int64_t)term_of[f] * n;
+    else if (expand & (1 << f)) field[f] = c->reg.arr.p + (int64_t)slot++ * n;
+  }
+  if (int rc = score_runs(c, d->x.p, field, per_group, G, d->off_host.data(), d->off.p,
+                          c->reg.npart, K, p_outlier, out_logp))
+    return rc;
+  return WFPT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // The regressor's posterior predictive (reg_sim_kernel; hddm_regression.py:39-56
 // over generate.py:208-319)
@@ -477,31 +510,42 @@ int wfpt_wiener_like_reg_groups_ex(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt
   WFPT_RANGE("wfpt_wiener_like_reg_groups");
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  const int64_t n = d->n;
-  int term_of[7] = {-1, -1, -1, -1, -1, -1, -1};
-  for (int32_t t = 0; t < n_terms; ++t) term_of[terms[t].param] = t;
-  // v, sv, a, z and t per trial from the group rows unless regressed; sz and st
-  // stay scalars of the pass unless regressed, as in the single call, so a
-  // group's trials take the kernel the single call on that group takes
-  int expand = 0;
-  for (int f : {0, 1, 2, 3, 5})
-    if (term_of[f] < 0) expand |= 1 << f;
-  std::vector<wfpt::Params> par(G);
-  for (int32_t j = 0; j < G; ++j) par[j] = to_params(&per_group[j]);
-  HIP_TRY(c->reg.par.reserve(G));
-  HIP_TRY(hipMemcpyAsync(c->reg.par.p, par.data(), G * sizeof(wfpt::Params),
-                         hipMemcpyHostToDevice, c->stream));
-  if (int rc = reg_fill(c, d, terms, n_terms, coef, G, true, expand, out_pred != nullptr))
-    return rc;
-  double* field[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int f = 0, slot = n_terms; f < 7; ++f) {
-    if (term_of[f] >= 0) field[f] = c->reg.arr.p + (int64_t)term_of[f] * n;
-    else if (expand & (1 << f)) field[f] = c->reg.arr.p + (int64_t)slot++ * n;
-  }
-  if (int rc = score_runs(c, d->x.p, field, per_group, G, d->off_host.data(), d->off.p,
-                          c->reg.npart, K, p_outlier, out_logp))
+  if (int rc = reg_groups_locked(c, d, terms, n_terms, coef, per_group, K, p_outlier,
+                                 out_pred != nullptr, out_logp))
     return rc;
   return reg_outputs(c, d, n_terms, out_trial, out_pred);
+}
+
+int wfpt_pointwise_reg_groups(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,
+                              int32_t n_terms, const double* coef, const wfpt_params* per_group,
+                              int64_t S, const wfpt_knobs* k, int64_t max_workspace,
+                              double* out_sums, double* out_stats, int64_t* out_ninf_total) {
+  if (int rc = reg_check_terms(terms, n_terms)) return rc;
+  if (!c || !d || !coef || !per_group || !k || !out_sums || !out_stats || !out_ninf_total)
+    return fail(WFPT_ERR_ARG, "null pointer");
+  if (S < 1) return fail(WFPT_ERR_ARG, "S < 1");
+  if (int rc = reg_check_call(c, d, terms, n_terms)) return rc;
+  const int32_t G = d->n_groups;
+  if (d->group_max > wfpt::kRlNodeMax)
+    return fail(WFPT_ERR_UNSUPPORTED, "a group holds more trials than the per-group sum takes");
+  for (int64_t s = 0; s < S; ++s)  // the per-trial-parameter pass takes one p_outlier
+    for (int32_t j = 1; j < G; ++j)
+      if (per_group[s * G + j].p_outlier != per_group[s * G].p_outlier)
+        return fail(WFPT_ERR_UNSUPPORTED, "the groups call needs one p_outlier for all groups");
+  const wfpt::Knobs K = to_knobs(k);
+  (void)max_workspace;  // the groups call scores one table: a tile is one sweep
+  WFPT_RANGE("wfpt_pointwise_reg_groups");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  if (int rc = pointwise_begin(c, d->n)) return rc;
+  for (int64_t s = 0; s < S; ++s) {  // the state stays on the device between sweeps
+    if (int rc = reg_groups_locked(c, d, terms, n_terms, coef + s * G * d->C, per_group + s * G, K,
+                                   per_group[s * G].p_outlier, false, out_sums + s * G))
+      return rc;
+    if (int rc = pointwise_add(c, c->lp.p, 1)) return rc;
+  }
+  return pointwise_finish(c, S, d->caller_host.empty() ? nullptr : d->caller_host.data(),
+                          out_stats, out_ninf_total);
 }
 
 int wfpt_wiener_like_reg_groups(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,

@@ -291,6 +291,51 @@ wfpt::RlRow rl_row(double q, double alpha, double pos_alpha, double v) {
   return R;
 }
 
+// The multi-table node batch after its checks, the context locked: the sums of
+// the T x n_nodes nodes into out_logp, every scored trial's term left in c->lp
+// (table t's compact trial i at t m + i).
+int rl_nodes_multi_locked(wfpt_ctx* c, const wfpt_rl_ds* d, const double* rl_tables,
+                          const wfpt_params* tables, int32_t n_tables, const wfpt::Knobs& K,
+                          double p_outlier, bool want_drift, double* out_logp) {
+  const int32_t nn = d->n_nodes;
+  const int64_t T = n_tables, G = T * nn, m = d->m;
+  std::vector<wfpt::RlRow> rows(G);
+  std::vector<wfpt::Params> par(G);
+  for (int64_t j = 0; j < G; ++j) {
+    rows[j] = rl_row(rl_tables[3 * j], rl_tables[3 * j + 1], rl_tables[3 * j + 2], tables[j].v);
+    par[j] = to_params(&tables[j]);
+  }
+  // one copy each for all tables
+  HIP_TRY(c->rl.rows.reserve(G));
+  HIP_TRY(c->rl.par.reserve(G));
+  HIP_TRY(hipMemcpyAsync(c->rl.rows.p, rows.data(), G * sizeof(wfpt::RlRow),
+                         hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->rl.par.p, par.data(), G * sizeof(wfpt::Params),
+                         hipMemcpyHostToDevice, c->stream));
+  if (int rc = rl_replicate(c, d, n_tables)) return rc;
+  // The one-table call's sequence over T x the work: table t's scored trials
+  // are trials [t m, (t + 1) m) of every per-trial array, its nodes groups
+  // [t n_nodes, (t + 1) n_nodes) of score_runs. The scoring kernels work trial
+  // by trial and the per-node sum counts its blocks from the node's first
+  // trial, so no bit depends on where a table starts.
+  constexpr int mask = 0x2e;  // sv, a, z, t per trial; sz and st scalars of the pass
+  const int64_t tm = T * m;
+  HIP_TRY(c->rl.arr.reserve(std::max<int64_t>(4 * tm, 1)));
+  if (int rc = rl_scan(c, d, wfpt::RlRow{}, c->rl.rows.p, nullptr, nullptr, want_drift,
+                       n_tables))
+    return rc;
+  wfpt::launch_rl_fill_multi(d->node_c.p, wfpt::RlTables{n_tables, nn, m, d->n}, c->rl.par.p, mask,
+                             c->rl.arr.p, c->stream);
+  HIP_TRY(hipGetLastError());
+  double* field[7] = {c->rl.drift.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int f = 1, slot = 0; f < 7; ++f)
+    if (mask & (1 << f)) field[f] = c->rl.arr.p + (int64_t)slot++ * tm;
+  if (int rc = score_runs(c, d->x_rep.p, field, tables, (int32_t)G, d->off_rep_host.data(),
+                          d->off_rep.p, c->rl.npart, K, p_outlier, out_logp))
+    return rc;
+  return WFPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -516,41 +561,53 @@ int wfpt_wiener_like_rlddm_nodes_multi_ex(wfpt_ctx* c, const wfpt_rl_ds* d,
   WFPT_RANGE("wfpt_wiener_like_rlddm_nodes_multi");
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  std::vector<wfpt::RlRow> rows(G);
-  std::vector<wfpt::Params> par(G);
-  for (int64_t j = 0; j < G; ++j) {
-    rows[j] = rl_row(rl_tables[3 * j], rl_tables[3 * j + 1], rl_tables[3 * j + 2], tables[j].v);
-    par[j] = to_params(&tables[j]);
-  }
-  // one copy each for all tables
-  HIP_TRY(c->rl.rows.reserve(G));
-  HIP_TRY(c->rl.par.reserve(G));
-  HIP_TRY(hipMemcpyAsync(c->rl.rows.p, rows.data(), G * sizeof(wfpt::RlRow),
-                         hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->rl.par.p, par.data(), G * sizeof(wfpt::Params),
-                         hipMemcpyHostToDevice, c->stream));
-  if (int rc = rl_replicate(c, d, n_tables)) return rc;
-  // The one-table call's sequence over T x the work: table t's scored trials
-  // are trials [t m, (t + 1) m) of every per-trial array, its nodes groups
-  // [t n_nodes, (t + 1) n_nodes) of score_runs. The scoring kernels work trial
-  // by trial and the per-node sum counts its blocks from the node's first
-  // trial, so no bit depends on where a table starts.
-  constexpr int mask = 0x2e;  // sv, a, z, t per trial; sz and st scalars of the pass
-  const int64_t tm = T * m;
-  HIP_TRY(c->rl.arr.reserve(std::max<int64_t>(4 * tm, 1)));
-  if (int rc = rl_scan(c, d, wfpt::RlRow{}, c->rl.rows.p, nullptr, nullptr, out_drift != nullptr,
-                       n_tables))
-    return rc;
-  wfpt::launch_rl_fill_multi(d->node_c.p, wfpt::RlTables{n_tables, nn, m, d->n}, c->rl.par.p, mask,
-                             c->rl.arr.p, c->stream);
-  HIP_TRY(hipGetLastError());
-  double* field[7] = {c->rl.drift.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int f = 1, slot = 0; f < 7; ++f)
-    if (mask & (1 << f)) field[f] = c->rl.arr.p + (int64_t)slot++ * tm;
-  if (int rc = score_runs(c, d->x_rep.p, field, tables, (int32_t)G, d->off_rep_host.data(),
-                          d->off_rep.p, c->rl.npart, K, p_outlier, out_logp))
+  if (int rc = rl_nodes_multi_locked(c, d, rl_tables, tables, n_tables, K, p_outlier,
+                                     out_drift != nullptr, out_logp))
     return rc;
   return rl_outputs(c, d, out_trial, out_drift, T);
+}
+
+int wfpt_pointwise_rlddm_nodes(wfpt_ctx* c, const wfpt_rl_ds* d, const double* rl_tables,
+                               const wfpt_params* tables, int64_t S, const wfpt_knobs* k,
+                               int64_t max_workspace, double* out_sums, double* out_stats,
+                               int64_t* out_index, int64_t* out_ninf_total) {
+  if (!c || !d || !rl_tables || !tables || !k || !out_sums || !out_stats || !out_index ||
+      !out_ninf_total)
+    return fail(WFPT_ERR_ARG, "null pointer");
+  if (S < 1) return fail(WFPT_ERR_ARG, "S < 1");
+  if (int rc = rl_check_ds(c, d, true)) return rc;
+  const int32_t nn = d->n_nodes;
+  if (nn <= 0) return fail(WFPT_ERR_ARG, "RL dataset was created without node ids");
+  if (d->node_max > wfpt::kRlNodeMax)
+    return fail(WFPT_ERR_UNSUPPORTED, "a node holds more scored trials than the per-node sum takes");
+  const int64_t m = d->m, G = S * nn;
+  for (int64_t j = 1; j < G; ++j)  // the per-trial-parameter pass takes one p_outlier
+    if (tables[j].p_outlier != tables[0].p_outlier)
+      return fail(WFPT_ERR_UNSUPPORTED,
+                  "the RL node batch needs one p_outlier for all nodes of all tables");
+  const double p_outlier = tables[0].p_outlier;
+  std::copy(d->c2caller.begin(), d->c2caller.end(), out_index);
+  if (!p_outlier_in_range(p_outlier)) {  // wfpt.pyx:102-103, every node of every sweep
+    for (int64_t j = 0; j < G; ++j) out_sums[j] = -INFINITY;
+    pointwise_all_inf(m, S, out_stats, out_ninf_total);
+    return WFPT_OK;
+  }
+  const wfpt::Knobs K = to_knobs(k);
+  WFPT_RANGE("wfpt_pointwise_rlddm_nodes");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  // a tile is one multi-table batch: its lanes, rows and records are ints
+  const int64_t widest = std::max<int64_t>({(int64_t)nn, m, (int64_t)d->n_seg});
+  const int64_t tile = pointwise_tile(max_workspace, m, S, widest);
+  if (int rc = pointwise_begin(c, m)) return rc;
+  for (int64_t s0 = 0; s0 < S; s0 += tile) {
+    const int32_t T = (int32_t)std::min<int64_t>(tile, S - s0);
+    if (int rc = rl_nodes_multi_locked(c, d, rl_tables + 3 * s0 * nn, tables + s0 * nn, T, K,
+                                       p_outlier, false, out_sums + s0 * nn))
+      return rc;
+    if (int rc = pointwise_add(c, c->lp.p, T)) return rc;
+  }
+  return pointwise_finish(c, S, nullptr, out_stats, out_ninf_total);
 }
 
 int wfpt_wiener_like_rlddm_nodes_multi(wfpt_ctx* c, const wfpt_rl_ds* d, const double* rl_tables,

@@ -38,6 +38,7 @@ import numpy as np
 from scipy import special
 
 from . import wfpt as _wfpt
+from .compare import Pointwise
 
 WIENER_PARAMS = {"err": 1e-4, "n_st": 2, "n_sz": 2, "use_adaptive": 1, "simps_err": 1e-3,
                  "w_outlier": 0.1}  # base.py:712-716
@@ -259,7 +260,7 @@ def _refuses(reason):
     return method
 
 
-class HDDM:
+class HDDM(Pointwise):
     """HDDM(data, depends_on={'v': 'cond'}).sample(n) on one MI355X.
 
     data: pandas DataFrame with columns rt (seconds), response (1 upper / 0
@@ -622,6 +623,13 @@ class HDDM:
         stats = flat.row_stats(self.signed_rt, self.node_codes, quantiles)
         return float(_opt._quantile_scores(flat, method, flat.current()[None], *stats)[0])
 
+    # -- model comparison (compare.Pointwise: pointwise_loglik, dic_info, dic, waic)
+    def _pw_score(self, picked):
+        return self.dataset.pointwise_nodes(self._pw_ddm_table(picked), **self.wp)
+
+    def _pw_mean_logp(self, picked):
+        return self.dataset.wiener_like_nodes(self._pw_ddm_table(picked, mean=True), **self.wp)
+
     @staticmethod
     def _picked_sweeps(samples, kept):
         """The indices of `samples` evenly spaced ones of `kept` kept sweeps
@@ -816,6 +824,8 @@ class HDDMChains(HDDM):
     optimize = quantile_objective = _refuses("HDDMChains: point fits take one chain (HDDM)")
     post_pred_rows = post_pred_gen = post_pred_stats = _refuses(
         "HDDMChains: posterior predictive draws take one chain (HDDM)")
+    pointwise_loglik = dic_info = waic = _refuses(
+        "HDDMChains: model comparison takes one chain (HDDM); pooling chains is not implemented")
 
     def _unit_group_c(self, fam):
         """(C, units) group mean of each unit's level, per chain."""

@@ -351,6 +351,29 @@ class HDDMRegressor(HDDM):
         group.update(inter)
         return group, subj
 
+    # -- model comparison ------------------------------------------------------
+    def _pw_coef_table(self, picked, mean=False):
+        """coef_table for the picked sweeps, (S, n_nodes, C), or at the mean
+        over them of every coefficient."""
+        B = np.empty((() if mean else (picked.size,)) + (self.n_nodes, self.n_coef))
+        for j, nm in enumerate(self.coef_names):
+            if self.group_only_regressors:
+                val = self.trace[nm][picked]
+                B[..., j] = float(np.mean(val)) if mean else val[:, None]
+            else:
+                val = self.trace_subj[nm][picked]
+                B[..., j] = (val.mean(axis=0) if mean else val)[..., self.node_subj]
+        return B
+
+    def _pw_score(self, picked):
+        return self.dataset.pointwise_reg_groups(self.reg_model, self._pw_coef_table(picked),
+                                                 self._pw_ddm_table(picked), **self.wp)
+
+    def _pw_mean_logp(self, picked):
+        return self.dataset.wiener_like_reg_groups(
+            self.reg_model, self._pw_coef_table(picked, mean=True),
+            self._pw_ddm_table(picked, mean=True), **self.wp)
+
     # -- posterior predictive --------------------------------------------------
     @_needs_trial_sampler
     def post_pred_rows(self, samples=500):

@@ -134,6 +134,28 @@ class HDDMrl(HDDM):
         self._count_call(time.perf_counter() - t0, ",".join(sorted(overs[0])) + f" x{len(overs)}")
         return out
 
+    # -- model comparison ----------------------------------------------------
+    def _pw_rl_table(self, picked, mean=False):
+        """rl_table for the picked sweeps, (S, n_nodes, 3), or at the mean over
+        them of alpha / pos_alpha on their sampled (unbounded) scale."""
+        R = np.empty((() if mean else (picked.size,)) + (self.n_nodes, 3))
+        R[..., 0] = self.node_q
+        R[..., 2] = NO_POS_ALPHA
+        for fam in self.rl_families:
+            val = self.trace_subj[fam][picked]
+            val = val.mean(axis=0) if mean else val
+            R[..., _RL_COL[fam]] = val[..., self.node_unit[fam]]
+        return R
+
+    def _pw_score(self, picked):
+        return self.dataset.pointwise_rlddm_nodes(self._pw_rl_table(picked),
+                                                  self._pw_ddm_table(picked), **self.wp)
+
+    def _pw_mean_logp(self, picked):
+        return self.dataset.wiener_like_rlddm_nodes(self._pw_rl_table(picked, mean=True),
+                                                    self._pw_ddm_table(picked, mean=True),
+                                                    **self.wp)
+
     def _record(self, nodes):
         """HDDM._record with the learning-rate keys after the a / v / t keys:
         ..., t_std, alpha, alpha_std[, pos_alpha, pos_alpha_std], then sv / sz / st."""

@@ -743,6 +743,12 @@ def _id_array(ids, count):
     return ids, count, ids.ctypes.data_as(_lib._PI32)
 
 
+def _pointwise_result(sums, stats, trial, ninf_total):
+    """The dict every pointwise_* method returns."""
+    return {"sums": sums, "lppd": stats[0], "p_waic": stats[1], "mean": stats[2],
+            "n_inf": stats[3].astype(np.int64), "trial": trial, "n_inf_total": int(ninf_total)}
+
+
 class Dataset(_Resident):
     """RTs resident in HBM for repeated likelihood calls (MCMC: data fixed,
     parameters change per proposal). Optional `node_id` groups trials into
@@ -928,6 +934,31 @@ class Dataset(_Resident):
             _lib.check(rc)
         return out
 
+    def pointwise_nodes(self, tables, err=1e-4, n_st=2, n_sz=2, use_adaptive=1, simps_err=1e-3,
+                        w_outlier=0.1, max_workspace=None):
+        """The model-comparison pass over S kept sweeps: tables (S, n_nodes, 8)
+        -> a dict of `sums` (S, n_nodes), row s bit for bit
+        wiener_like_nodes(tables[s]), and per trial, reduced over the sweeps on
+        the device, `lppd` (log mean density), `p_waic` (sample variance of the
+        log terms), `mean` (mean log term) and `n_inf` (sweeps with a zero
+        density), in the caller's trial order (`trial` = arange(n)). The S x n
+        terms stay in device memory, scored in tiles of max_workspace bytes
+        (default 1 GiB)."""
+        tb = np.ascontiguousarray(tables, dtype=np.float64)
+        if self.n_nodes == 0:
+            raise ValueError("dataset was created without node ids")
+        if tb.ndim != 3 or tb.shape[1:] != (self.n_nodes, 8) or tb.shape[0] < 1:
+            raise ValueError(f"tables must have shape (S, {self.n_nodes}, 8), S >= 1")
+        S = tb.shape[0]
+        K = self._knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        sums = np.empty((S, self.n_nodes), dtype=np.float64)
+        stats = np.empty((4, self.n), dtype=np.float64)
+        ninf = ctypes.c_int64()
+        _lib.check(_lib.wfpt_pointwise_nodes(
+            self.ctx.handle, self.handle, tb.ctypes.data_as(_lib._PP), S, ctypes.byref(K),
+            int(max_workspace or 0), _lib.dptr(sums), _lib.dptr(stats), ctypes.byref(ninf)))
+        return _pointwise_result(sums, stats, np.arange(self.n, dtype=np.int64), ninf.value)
+
     def wiener_like_nodes(self, params, err=1e-4, n_st=2, n_sz=2, use_adaptive=1,
                           simps_err=1e-3, w_outlier=0.1, trials=False):
         """params: array (n_nodes, 8) of v, sv, a, z, sz, t, st, p_outlier.
@@ -1037,6 +1068,9 @@ class RLDataset(_Resident):
         if node_id is not None:
             node, self.n_nodes, nptr = _id_array(node_id, n_nodes)
             _same_length(n, node_id=node)
+        # the scored trials: all but the first of each (node, condition) segment
+        key = np.stack([node if node is not None else np.zeros(n, dtype=np.int64), split_by])
+        self.n_scored = n - (np.unique(key, axis=1).shape[1] if n else 0)
         h = _lib._VP()
         _lib.check(_lib.wfpt_rl_dataset_create(
             self.ctx.handle, _optr(rt), _i64ptr(response), _lib.dptr(feedback), _i64ptr(split_by),
@@ -1126,6 +1160,33 @@ class RLDataset(_Resident):
             self.ctx.handle, self.handle, _lib.dptr(rr), pm.ctypes.data_as(_lib._PP), T,
             ctypes.byref(K), _lib.dptr(out), ptr, pdr))
         return (out, tr, dr) if terms else out
+
+    def pointwise_rlddm_nodes(self, rl_tables, params, err=1e-4, n_st=2, n_sz=2, use_adaptive=1,
+                              simps_err=1e-3, w_outlier=0.1, max_workspace=None):
+        """Dataset.pointwise_nodes over the multi-table RL node batch: rl_tables
+        (S, n_nodes, 3), params (S, n_nodes, 8), one p_outlier throughout. The
+        per-trial entries cover the scored trials only (all but each segment's
+        first); `trial` is the caller's index of each entry."""
+        if self.n_nodes == 0:
+            raise ValueError("dataset was created without node ids")
+        rr = np.ascontiguousarray(rl_tables, dtype=np.float64)
+        pm = np.ascontiguousarray(params, dtype=np.float64)
+        if rr.ndim != 3 or rr.shape[0] < 1 or rr.shape[1:] != (self.n_nodes, 3):
+            raise ValueError(f"rl_tables must have shape (S, {self.n_nodes}, 3) with S >= 1")
+        S = rr.shape[0]
+        if pm.shape != (S, self.n_nodes, 8):
+            raise ValueError(f"params must have shape ({S}, {self.n_nodes}, 8)")
+        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        sums = np.empty((S, self.n_nodes), dtype=np.float64)
+        m = self.n_scored
+        stats = np.empty((4, m), dtype=np.float64)
+        index = np.empty(m, dtype=np.int64)
+        ninf = ctypes.c_int64()
+        _lib.check(_lib.wfpt_pointwise_rlddm_nodes(
+            self.ctx.handle, self.handle, _lib.dptr(rr), pm.ctypes.data_as(_lib._PP), S,
+            ctypes.byref(K), int(max_workspace or 0), _lib.dptr(sums), _lib.dptr(stats),
+            _i64ptr(index), ctypes.byref(ninf)))
+        return _pointwise_result(sums, stats, index, ninf.value)
 
 
 # ---------------------------------------------------------------------------
@@ -1255,6 +1316,33 @@ class RegDataset(_Resident):
         if not terms:
             return out
         return out, tr, {m[0]: pr[k] for k, m in enumerate(model)}
+
+    def pointwise_reg_groups(self, model, coef_tables, params, err=1e-4, n_st=2, n_sz=2,
+                             use_adaptive=1, simps_err=1e-3, w_outlier=0.1, max_workspace=None):
+        """Dataset.pointwise_nodes over the regression groups call: coef_tables
+        (S, G, C), params (S, G, 8), one p_outlier per sweep. `sums` is (S, G);
+        the per-trial entries are in the caller's trial order. The groups call
+        scores one table, so a tile is one sweep; the accumulator state stays
+        on the device between sweeps."""
+        model = list(model)
+        T, nt = _reg_terms(model, self.n_cols)
+        G = self.n_groups
+        bt = np.ascontiguousarray(coef_tables, dtype=np.float64)
+        pm = np.ascontiguousarray(params, dtype=np.float64)
+        if bt.ndim != 3 or bt.shape[0] < 1 or bt.shape[1:] != (G, self.n_cols):
+            raise ValueError(f"coef_tables must have shape (S, {G}, {self.n_cols}) with S >= 1")
+        S = bt.shape[0]
+        if pm.shape != (S, G, 8):
+            raise ValueError(f"params must have shape ({S}, {G}, 8)")
+        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        sums = np.empty((S, G), dtype=np.float64)
+        stats = np.empty((4, self.n), dtype=np.float64)
+        ninf = ctypes.c_int64()
+        _lib.check(_lib.wfpt_pointwise_reg_groups(
+            self.ctx.handle, self.handle, T, nt, _lib.dptr(bt), pm.ctypes.data_as(_lib._PP), S,
+            ctypes.byref(K), int(max_workspace or 0), _lib.dptr(sums), _lib.dptr(stats),
+            ctypes.byref(ninf)))
+        return _pointwise_result(sums, stats, np.arange(self.n, dtype=np.int64), ninf.value)
 
     # The posterior predictive's trial-wise drift sampler
     # (wfpt_gen_rts_reg_drift; DESIGN.md §23).

@@ -425,6 +425,60 @@ int wfpt_gen_rts_reg_drift_stats(wfpt_ctx *ctx, const wfpt_reg_ds *ds,
                                  double *out, int64_t *n_unfinished, int64_t *n_invalid,
                                  const double *q, int32_t nq, double *stats_out);
 
+/* ---- model comparison: pointwise log-likelihood statistics ---------------- */
+/* DIC and WAIC need, for S kept posterior sweeps, the per-sweep node sums and,
+ * per trial, a reduction over the sweeps of that trial's log term l_s. The
+ * S x n matrix of terms never leaves the device: the sweeps are scored in
+ * tiles of T = max(1, max_workspace / (8 len)) sweeps (max_workspace <= 0: 1
+ * GiB; T x nodes <= INT32_MAX / 2) by the family's existing batch call, and
+ * after each tile one kernel folds its terms into a per-trial state, one lane
+ * per trial, the sweeps in rising order (pointwise_update.hpp states the rule):
+ *   l == -inf:  n_inf += 1                        nothing else changes
+ *   else k += 1
+ *     k == 1:   m = l; r = 1
+ *     l <= m:   r = r + exp(l - m)
+ *     else:     r = r * exp(m - l) + 1; m = l
+ *     d = l - mean; mean = mean + d / k; M2 = M2 + d * (l - mean)
+ *   finish:     lppd = m + log(r) - log(S)        S counts the -inf sweeps too
+ *               p_waic = k >= 2 ? M2 / (k - 1) : 0
+ *               k == 0: lppd = -inf, mean = -inf, p_waic = NaN
+ * with correctly rounded exp and log and no fused multiply-add, so the result
+ * does not depend on the tiling and equals a host build of the rule bit for
+ * bit. A NaN term makes the trial's lppd, p_waic and mean NaN.
+ * out_sums[S * nodes]: row s is bit for bit what the family's one-call entry
+ * returns for table s. out_stats[4 * len]: lppd at [i], p_waic at [len + i],
+ * the mean term at [2 len + i], n_inf (a whole number) at [3 len + i].
+ * *out_ninf_total: the (sweep, trial) pairs with a zero density.
+ * WFPT_ERR_ARG before any device work: a null pointer, S < 1, a data set
+ * without node ids or of another context; the family's own WFPT_ERR_UNSUPPORTED
+ * cases apply (one p_outlier per sweep's batch, node sizes). */
+/* tables[S * n_nodes]: sweep s's row of node j at [s n_nodes + j]. len = the
+ * data set's size; out_stats is in the caller's trial order. */
+int wfpt_pointwise_nodes(wfpt_ctx *ctx, const wfpt_ds *ds, const wfpt_params *tables, int64_t S,
+                         const wfpt_knobs *k, int64_t max_workspace, double *out_sums,
+                         double *out_stats, int64_t *out_ninf_total);
+/* Over the multi-table RL node batch: rl_tables[3 * S * n_nodes], tables[S *
+ * n_nodes] as in wfpt_wiener_like_rlddm_nodes_multi. len = m_scored, the trials
+ * that are scored (all but each segment's first), in the data set's compact
+ * order; out_index[m_scored] is the caller's index of each entry. A p_outlier
+ * outside [0, 1] makes every sum -inf and every term a zero density. */
+int wfpt_pointwise_rlddm_nodes(wfpt_ctx *ctx, const wfpt_rl_ds *ds, const double *rl_tables,
+                               const wfpt_params *tables, int64_t S, const wfpt_knobs *k,
+                               int64_t max_workspace, double *out_sums, double *out_stats,
+                               int64_t *out_index, int64_t *out_ninf_total);
+/* Over the regression groups call: coef[S * n_groups * C], per_group[S *
+ * n_groups]. That call scores one table, so a tile is one sweep (max_workspace
+ * is not used); the state stays on the device between sweeps. len = n;
+ * out_stats is in the caller's trial order. */
+int wfpt_pointwise_reg_groups(wfpt_ctx *ctx, const wfpt_reg_ds *ds, const wfpt_reg_term *terms,
+                              int32_t n_terms, const double *coef, const wfpt_params *per_group,
+                              int64_t S, const wfpt_knobs *k, int64_t max_workspace,
+                              double *out_sums, double *out_stats, int64_t *out_ninf_total);
+/* Device ms of the accumulate kernel since the last reset, summed over the
+ * tiles of profiled passes (wfpt_profile_enable with WFPT_PROF_EVENTS; such a
+ * pass waits for each tile's kernel). */
+int wfpt_pointwise_profile(wfpt_ctx *ctx, double *accumulate_ms, int reset);
+
 /* ---- DMAT / Tuerlinckx CDF ---------------------------------------------- */
 /* Per-trial CDF of signed RTs with the outlier mixture, exactly
  * cdfdif_wrapper.dmat_cdf_array(x, v, sv, a, z, sz, t, st, p_outlier, w_outlier)
