@@ -84,6 +84,7 @@ _LIKE = [_VP, _VP, _PP, _PK, _PD]  # ctx, dataset, params | table, knobs, out
 _MULTI = [_PPD, _PD, _PK, _D, _PD]  # per-trial arrays, scalars, knobs, p_outlier, out
 _RL_HOST = [_VP, _PD, _PI64, _PD, _PI64, _I64, _D]  # ctx, rt, response, feedback, split_by, n, q
 _REG = [_VP, _VP, _PT, _I32, _PD, _PP, _PK, _PD]  # ctx, ds, terms, n_terms, coef, params, ...
+_RL_REG = [_VP, _VP, _PT, _I32, _PD, _PD, _PD, _PP, _PK, _PD]
 _GEN_CDF = [_VP, _PD, _I64, _PP, _I64, _PI64, _PD, _PD, _U64, _I64, _PD]
 _GEN_DRIFT = [_VP, _PP, _I64, _PD, _PI64, _D, _D, _I64, _U64]
 _GEN_RLDDM = [_VP, _PP, _PD, _I64, _PI64, _PS, _D, _D, _I64, _U64]
@@ -159,6 +160,12 @@ _SIGNATURES = {
     "wfpt_wiener_like_reg_ex": (_I, _REG + [_PD, _PD]),
     "wfpt_wiener_like_reg_groups": (_I, _REG),
     "wfpt_wiener_like_reg_groups_ex": (_I, _REG + [_PD, _PD]),
+    # RL regression likelihood: ctx, ds, terms, n_terms, coef, q, alpha, params, knobs, out
+    "wfpt_rl_reg_dataset_create": (_I, [_VP, _PD, _PI64, _PD, _PI64, _I64, _PD, _I32, _PI32, _I32,
+                                        _PVP]),
+    "wfpt_rl_reg_dataset_destroy": (None, [_VP]),
+    "wfpt_wiener_like_rl_reg_groups": (_I, _RL_REG),
+    "wfpt_wiener_like_rl_reg_groups_ex": (_I, _RL_REG + [_PD, _PD, _PD, _PD]),
     "wfpt_gen_rts_reg_drift": (_I, _GEN_REG + [_PD, _PI64, _PI64]),
     "wfpt_gen_rts_reg_drift_ex": (_I, _GEN_REG + [_I32, _I64, _PD, _PI64, _PI64, _PD, _PD, _PD,
                                                   _PD, _PI64, _PI64]),

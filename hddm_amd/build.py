@@ -19,14 +19,15 @@ LIB = os.path.join(LIBDIR, "libwfpt_amd.so")
 SOURCES = ["wfpt_node.hip", "wfpt_sum.hip", "wfpt_engine.hip", "wfpt_fold.hip",
            "wfpt_level0.hip", "cdfdif_kernels.hip", "rl_kernels.hip", "sim_kernels.hip",
            "rl_sim_kernels.hip", "reg_sim_kernels.hip", "reg_kernels.hip", "stats_kernels.hip",
-           "pointwise_kernels.hip",
+           "pointwise_kernels.hip", "rl_reg_kernels.hip",
            "capi_core.cpp", "capi_comm.cpp", "capi_rl.cpp", "capi_reg.cpp", "capi_sim.cpp",
+           "capi_rl_reg.cpp",
            "wfpt_rendezvous.cpp"]
 DEPS = SOURCES + ["wfpt_device.hpp", "wfpt_kernel_common.hpp", "wfpt_engine.hpp",
                   "wfpt_internal.h", "rl_internal.h", "sim_internal.h", "reg_internal.h",
                   "stats_internal.h", "sim_philox.hpp", "rl_update.hpp", "reg_predict.hpp",
                   "pointwise_internal.h", "pointwise_update.hpp", "capi_internal.hpp",
-                  "capi_layout.hpp", "wfpt_crlibm.hpp", "wfpt_exact.hpp"]
+                  "capi_layout.hpp", "wfpt_crlibm.hpp", "wfpt_exact.hpp", "rl_reg_internal.h"]
 ARCH = os.environ.get("WFPT_OFFLOAD_ARCH", "gfx950")
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

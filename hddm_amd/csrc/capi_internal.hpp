@@ -436,6 +436,10 @@ int score_runs(wfpt_ctx* c, const double* dx, double* const field[7], const wfpt
 // is "<name>: negative count in row r".
 int counts_to_offsets(const char* name, const int64_t* counts, int64_t R,
                       std::vector<int64_t>* off);
+// The checks of a regression term list that need no data set (defined in
+// capi_reg.cpp): max_param 6 for the regression entries, 7 (alpha) for the RL
+// regression entries.
+int reg_check_terms(const wfpt_reg_term* terms, int32_t n_terms, int max_param = 6);
 // The learning rate of the unbounded alpha as every RL entry forms it
 // (wfpt.pyx:123-125), defined in capi_rl.cpp.
 double rl_rate(double alpha);

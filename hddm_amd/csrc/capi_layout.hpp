@@ -30,7 +30,9 @@ struct RlHostLayout {
   std::vector<int64_t> node_off;      // [n_nodes + 1] compact range of each node
 };
 // by_runs: segments are the runs of equal adjacent split_by values, every
-// trial scored (wfpt.pyx:300-318); else the (node, condition) groups, conditions
+// trial scored (wfpt.pyx:300-318), with node ids the runs inside each node,
+// trials node-major (a node boundary always starts a segment: the RL
+// regression data set, capi_rl_reg.cpp); else the (node, condition) groups, conditions
 // rising as np.unique gives them, the caller's order kept inside a group
 // (wfpt.pyx:114-116), each group's first trial unscored. rt, node_id: nullable.
 RlHostLayout rl_layout_host(const double* rt, const int64_t* response, const double* feedback,

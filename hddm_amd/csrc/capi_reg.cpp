@@ -69,23 +69,22 @@ RegHostLayout reg_layout_host(const double* rt, int64_t n, const double* X, int3
   return H;
 }
 
-}  // namespace capi
-}  // namespace wfpt
-
-namespace {
-
-// The checks of a term list that need no data set: parameter 0..6, each named
-// once, a known link, ncol >= 1, col0 >= 0.
-int reg_check_terms(const wfpt_reg_term* terms, int32_t n_terms) {
-  if (n_terms < 0 || n_terms > wfpt::kRegMaxTerms)
-    return fail(WFPT_ERR_ARG, "n_terms must be 0..7 (one term per parameter)");
+// The checks of a term list that need no data set: parameter 0..max_param,
+// each named once, a known link, ncol >= 1, col0 >= 0.
+int reg_check_terms(const wfpt_reg_term* terms, int32_t n_terms, int max_param) {
+  const bool rl = max_param > 6;  // the RL regression entries: 7 = alpha (capi_rl_reg.cpp)
+  if (n_terms < 0 || n_terms > max_param + 1)
+    return fail(WFPT_ERR_ARG, rl ? "n_terms must be 0..8 (one term per parameter)"
+                                 : "n_terms must be 0..7 (one term per parameter)");
   if (n_terms > 0 && !terms) return fail(WFPT_ERR_ARG, "null pointer (terms)");
   unsigned seen = 0;
   for (int32_t k = 0; k < n_terms; ++k) {
     const wfpt_reg_term& T = terms[k];
     const std::string at = " (term " + std::to_string(k) + ")";
-    if (T.param < 0 || T.param > 6)
-      return fail(WFPT_ERR_ARG, "term parameter outside 0..6 (v, sv, a, z, sz, t, st)" + at);
+    if (T.param < 0 || T.param > max_param)
+      return fail(WFPT_ERR_ARG,
+                  (rl ? "term parameter outside 0..7 (v, sv, a, z, sz, t, st, alpha)"
+                      : "term parameter outside 0..6 (v, sv, a, z, sz, t, st)") + at);
     if (seen & (1u << T.param)) return fail(WFPT_ERR_ARG, "a parameter is named twice" + at);
     seen |= 1u << T.param;
     if (T.link != WFPT_LINK_IDENTITY && T.link != WFPT_LINK_EXP && T.link != WFPT_LINK_INVLOGIT)
@@ -95,6 +94,11 @@ int reg_check_terms(const wfpt_reg_term* terms, int32_t n_terms) {
   }
   return WFPT_OK;
 }
+
+}  // namespace capi
+}  // namespace wfpt
+
+namespace {
 
 // The rest of an entry's checks, still before any device work.
 int reg_check_call(wfpt_ctx* c, const wfpt_reg_ds* d, const wfpt_reg_term* terms,

@@ -72,6 +72,9 @@ RlHostLayout rl_layout_host(const double* rt, const int64_t* response, const dou
       if (node_id && node_id[a] != node_id[b]) return node_id[a] < node_id[b];
       return split_by[a] < split_by[b];
     });
+  else if (node_id)  // node-major, the caller's order (and so its runs) kept inside a node
+    std::stable_sort(idx.begin(), idx.end(),
+                     [&](int64_t a, int64_t b) { return node_id[a] < node_id[b]; });
   std::vector<int64_t> seg_start;
   for (int64_t j = 0; j < n; ++j) {
     const int64_t a = idx[j], b = j ? idx[j - 1] : 0;

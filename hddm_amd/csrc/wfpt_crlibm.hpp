@@ -158,6 +158,30 @@ WFPT_HD double cr_exp(double x) {
   return dd_ldexp_round(p, k);
 }
 
+// B**x rounded once, B the double nearest the reference's literal
+// 2.718281828459 (wfpt.pyx:123, :317), which is not e: ln B = 1 - 1.67e-14.
+// kLnRlBase is the logarithm of that double (2.71828182845899979369...), not
+// of the decimal string, as a double-double (decimal at 80 digits). y = x ln B
+// is formed exactly in two_prod form plus the low part's product, exp(y.hi) in
+// double-double as in cr_exp, then corrected by exp(y.lo) = 1 + y.lo +
+// y.lo^2 / 2 (|y.lo| < 2^-43: the cubic term lies below 2^-129). NaN passes
+// through; overflow gives +inf and underflow 0, as pow does.
+constexpr double kLnRlBaseH = 0x1.fffffffffff69p-1, kLnRlBaseL = 0x1.b4644421d81bep-55;
+
+WFPT_HD double cr_pow_rlbase(double x) {
+  if (x != x) return x;
+  const double y0 = x * kLnRlBaseH;
+  if (y0 > 709.79) return INFINITY;
+  if (y0 < -746.0) return 0.0;
+  dd y = two_prod(x, kLnRlBaseH);
+  y.lo += x * kLnRlBaseL;
+  y = fast_two_sum(y.hi, y.lo);
+  int k;
+  const dd p = exp_dd(y.hi, &k);
+  const dd c = two_sum(y.lo, 0.5 * (y.lo * y.lo));
+  return dd_ldexp_round(dd_add(p, dd_mul(p, c)), k);
+}
+
 // log(m), m in [sqrt(1/2), sqrt(2)), as a double-double.
 WFPT_HD dd log_mant_dd(double m) {
   const double u = m - 1.0;  // exact (Sterbenz)

@@ -28,8 +28,8 @@ import time
 import numpy as np
 
 from . import wfpt as _wfpt
-from .hierarchical import (HDDM, INTER, LOGPDF, MODEL, SLICE_WIDTHS, _refuses, halfnormal_logpdf,
-                           logpdf, normal_logpdf, slice_step)
+from .hierarchical import (HDDM, INTER, LOGPDF, SLICE_WIDTHS, _refuses, halfnormal_logpdf, logpdf,
+                           normal_logpdf, slice_step)
 
 LINKS = ("identity", "exp", "invlogit")
 COEF_SLICE_WIDTH = 0.05  # hddm_regression.py:284
@@ -94,7 +94,9 @@ def design_matrix(formula_rhs, data):
 
 # ---------------------------------------------------------------- the model
 
-def _parse_models(models):
+def _parse_models(models, cls="HDDMRegressor", outcomes=("v", "a", "t")):
+    """The model descriptors of a regressor class `cls` whose likelihood takes
+    `outcomes` as trial-wise parameters (rl_regression.py adds alpha)."""
     if isinstance(models, (str, dict)):
         models = [models]
     out = []
@@ -103,18 +105,18 @@ def _parse_models(models):
             m = {"model": m}
         link = m.get("link_func", "identity")
         if callable(link):
-            raise TypeError("HDDMRegressor: the link runs on the device, so link_func is a "
+            raise TypeError(f"{cls}: the link runs on the device, so link_func is a "
                             f"name, one of {LINKS}, not a Python callable")
         if link not in LINKS:
-            raise ValueError(f"HDDMRegressor: unknown link_func {link!r}; expected one of {LINKS}")
+            raise ValueError(f"{cls}: unknown link_func {link!r}; expected one of {LINKS}")
         if "~" not in m["model"]:
-            raise ValueError(f"HDDMRegressor: model {m['model']!r} is not 'outcome ~ terms'")
+            raise ValueError(f"{cls}: model {m['model']!r} is not 'outcome ~ terms'")
         outcome, rhs = (s.strip() for s in m["model"].split("~", 1))
-        if outcome not in ("v", "a", "t"):
-            raise NotImplementedError(
-                f"HDDMRegressor: outcome {outcome!r} is not supported at model level (v, a, t)")
+        if outcome not in outcomes:
+            raise NotImplementedError(f"{cls}: outcome {outcome!r} is not supported at model "
+                                      f"level ({', '.join(outcomes)})")
         if any(d["outcome"] == outcome for d in out):
-            raise ValueError(f"HDDMRegressor: outcome {outcome!r} has two models")
+            raise ValueError(f"{cls}: outcome {outcome!r} has two models")
         out.append({"outcome": outcome, "rhs": rhs, "link": link})
     return out
 
@@ -148,17 +150,22 @@ class HDDMRegressor(HDDM):
     `{outcome}_{design column}`. The non-regressed families stay as in HDDM.
     """
 
+    # the outcomes a model may name and the families of the model without any
+    # regression, in HDDM's order (rl_regression.py adds alpha to both)
+    OUTCOMES, ALL_FAMILIES = ("v", "a", "t"), ("a", "v", "t")
+
     def __init__(self, data, models, group_only_regressors=True, include=(), p_outlier=0.05,
                  wiener_params=None, seed=None, device=None, depends_on=None):
         import pandas as pd
-        self.model_descrs = _parse_models(models)
+        cls = type(self).__name__
+        self.model_descrs = _parse_models(models, cls, self.OUTCOMES)
         self.reg_outcomes = [d["outcome"] for d in self.model_descrs]
         for k in (depends_on or {}):
             if k in self.reg_outcomes:  # hddm_regression.py:214-216
-                raise ValueError(f"HDDMRegressor: '{k}' is a regression outcome and cannot be "
+                raise ValueError(f"{cls}: '{k}' is a regression outcome and cannot be "
                                  "used in depends_on")
         self.group_only_regressors = bool(group_only_regressors)
-        self.FAMILIES = tuple(f for f in ("a", "v", "t") if f not in self.reg_outcomes)
+        self.FAMILIES = tuple(f for f in self.ALL_FAMILIES if f not in self.reg_outcomes)
         frame = pd.DataFrame(data).reset_index(drop=True)
         mats, col0 = [], 0
         self.coef_names, self.coef_outcome, self.coef_intercept = [], [], []
@@ -194,7 +201,7 @@ class HDDMRegressor(HDDM):
         super()._init_values()
         self.coef, self.coef_std, self.coef_subj = {}, {}, {}
         for nm, out, inter in zip(self.coef_names, self.coef_outcome, self.coef_intercept):
-            g0, s0 = MODEL[out].start[:2] if inter else (0.0, 0.0)
+            g0, s0 = self.MODEL[out].start[:2] if inter else (0.0, 0.0)
             if self.group_only_regressors:
                 # the group node feeds the likelihood directly: start where a
                 # subject node would (t below every RT)
@@ -244,18 +251,18 @@ class HDDMRegressor(HDDM):
         j = self.coef_names.index(nm)
         g = float(self.coef[nm] if g is None else g)
         std = float(self.coef_std[nm] if std is None else std)
-        kind = MODEL[self.coef_outcome[j]].subject if self.coef_intercept[j] else "normal"
+        kind = self.MODEL[self.coef_outcome[j]].subject if self.coef_intercept[j] else "normal"
         return LOGPDF[kind](x, g, std)
 
     def _coef_std_prior(self, nm, s):
         j = self.coef_names.index(nm)
         if self.coef_intercept[j]:
-            return float(halfnormal_logpdf(s, MODEL[self.coef_outcome[j]].std_sd))
+            return float(halfnormal_logpdf(s, self.MODEL[self.coef_outcome[j]].std_sd))
         return -np.log(100.0 - 1e-10) if 1e-10 <= s <= 100.0 else -np.inf
 
     def _coef_lower(self, nm):
         j = self.coef_names.index(nm)
-        return MODEL[self.coef_outcome[j]].lower if self.coef_intercept[j] else None
+        return self.MODEL[self.coef_outcome[j]].lower if self.coef_intercept[j] else None
 
     def logp(self):
         """Joint log density of the model at the current values."""
@@ -263,7 +270,7 @@ class HDDMRegressor(HDDM):
         for fam in self.FAMILIES:
             lp += float(np.sum(self.subj_prior(fam, self.subj[fam])))
             lp += float(np.sum(self._group_prior(fam, self.group[fam])))
-            lp += float(halfnormal_logpdf(self.std[fam], MODEL[fam].std_sd))
+            lp += float(halfnormal_logpdf(self.std[fam], self.MODEL[fam].std_sd))
         for nm in self.coef_names:
             lp += float(self._coef_group_prior(nm, self.coef[nm]))
             if not self.group_only_regressors:

@@ -59,7 +59,8 @@ __all__ = ["pdf_array", "wiener_like", "full_pdf", "wiener_like_multi", "wiener_
            "Dataset", "prob_ub", "wiener_like_rlddm", "wiener_like_rl", "wiener_like_multi_rlddm",
            "RLDataset", "wiener_like_rlddm_nodes", "wiener_like_rlddm_nodes_multi",
            "wiener_like_rlddm_terms",
-           "wiener_like_rl_terms", "wiener_like_multi_rlddm_terms", "RegDataset"]
+           "wiener_like_rl_terms", "wiener_like_multi_rlddm_terms", "RegDataset",
+           "RLRegDataset"]
 
 
 def _check_x(x, name="x"):
@@ -1197,10 +1198,11 @@ REG_LINKS = {"identity": _lib.LINK_IDENTITY, "exp": _lib.LINK_EXP,
              "invlogit": _lib.LINK_INVLOGIT}
 
 
-def _reg_terms(model, n_cols):
+def _reg_terms(model, n_cols, params=REG_PARAMS):
     """[(param_name, col0, ncol, link_name), ...] -> a wfpt_reg_term array.
     Checks that need no device: known names, one term per parameter, column
-    ranges inside the design matrix."""
+    ranges inside the design matrix. params: the names a term may predict, in
+    wfpt_reg_term.param order (RLRegDataset adds alpha)."""
     model = list(model)
     arr = (_lib.RegTerm * max(len(model), 1))()
     seen = set()
@@ -1209,8 +1211,8 @@ def _reg_terms(model, n_cols):
             name, col0, ncol, link = term
         except (TypeError, ValueError):
             raise ValueError("a model term is (param_name, col0, ncol, link_name)")
-        if name not in REG_PARAMS:
-            raise ValueError(f"unknown parameter {name!r}; expected one of {REG_PARAMS}")
+        if name not in params:
+            raise ValueError(f"unknown parameter {name!r}; expected one of {params}")
         if name in seen:
             raise ValueError(f"parameter {name!r} is named twice")
         seen.add(name)
@@ -1221,7 +1223,7 @@ def _reg_terms(model, n_cols):
         if ncol < 1 or col0 < 0 or col0 + ncol > n_cols:
             raise ValueError(f"columns [{col0}, {col0 + ncol}) of term {name!r} lie outside "
                              f"the design matrix's {n_cols} columns")
-        arr[k] = _lib.RegTerm(REG_PARAMS.index(name), REG_LINKS[link], col0, ncol)
+        arr[k] = _lib.RegTerm(params.index(name), REG_LINKS[link], col0, ncol)
     return arr, len(model)
 
 
@@ -1459,6 +1461,129 @@ class RegDataset(_Resident):
             _lib.dptr(q), q.size, _lib.dptr(stats))
         self._sim_done(rc, nun, ninv, S, max_steps, max_t, unfinished, invalid)
         return (stats, out) if return_draws else stats
+
+
+# ---------------------------------------------------------------------------
+# RL regression likelihood (hddm/models/hddm_rl_regression.py:25-38)
+
+RL_REG_PARAMS = REG_PARAMS + ("alpha",)
+
+
+class RLRegDataset(_Resident):
+    """The fixed inputs of the RL regression likelihood resident in HBM: signed
+    RTs, responses, feedback, conditions and the design matrix. Per call only
+    the coefficients and a few rows per group go to the device; the trial-wise
+    parameters link(design . coefficients), the learning rate's `alpha` among
+    them, are formed there. Optional `group_id` groups the trials into
+    `n_groups` groups (subjects), each scored as one wiener_like_multi_rlddm
+    call (wfpt.pyx:277-320) would score its trials: Q restarts at every
+    adjacent change of split_by inside a group and at every group boundary.
+    |rt| == 999 and a response outside {0, 1} are rejected (ValueError)."""
+    _destroy = staticmethod(_lib.wfpt_rl_reg_dataset_destroy)
+
+    def __init__(self, rt, response, feedback, split_by, design, group_id=None, n_groups=None,
+                 device=None, ctx=None):
+        rt = np.ascontiguousarray(np.asarray(rt, dtype=np.float64).ravel())
+        n = rt.shape[0]
+        response = np.ascontiguousarray(np.asarray(response, dtype=np.int64).ravel())
+        feedback = np.ascontiguousarray(np.asarray(feedback, dtype=np.float64).ravel())
+        split_by = np.ascontiguousarray(np.asarray(split_by, dtype=np.int64).ravel())
+        _same_length(n, response=response, feedback=feedback, split_by=split_by)
+        self.columns = list(getattr(design, "columns", ()))
+        X = np.ascontiguousarray(np.asarray(design, dtype=np.float64))
+        if X.ndim != 2 or X.shape[0] != n or X.shape[1] < 1:
+            raise ValueError(f"design must have shape ({n}, C) with C >= 1, got {X.shape}")
+        if np.any((response != 0) & (response != 1)):
+            raise ValueError("response must be 0 or 1")
+        if np.any(np.abs(rt) == 999.):
+            raise ValueError("|rt| == 999: the RL likelihoods have no missing-response code")
+        node, self.n_groups, nptr = None, 1, None
+        if group_id is not None:
+            node, self.n_groups, nptr = _id_array(group_id, n_groups)
+            _same_length(n, group_id=node)
+            if self.n_groups < 1:
+                raise ValueError("group ids need n_groups >= 1")
+            if node.size and (node.min() < 0 or node.max() >= self.n_groups):
+                raise ValueError(f"group ids must lie in [0, {self.n_groups})")
+        self.n = n
+        self.n_cols = int(X.shape[1])
+        self.grouped = group_id is not None
+        self.ctx = ctx if ctx is not None else _lib.context(device)
+        h = _lib._VP()
+        _lib.check(_lib.wfpt_rl_reg_dataset_create(
+            self.ctx.handle, _lib.dptr(rt), _i64ptr(response), _lib.dptr(feedback),
+            _i64ptr(split_by), n, _lib.dptr(X), self.n_cols, nptr, self.n_groups,
+            ctypes.byref(h)))
+        self.handle = h
+
+    def _check_groups(self, model, coef_table, q, alpha, params):
+        """The arguments of a groups call as contiguous arrays, every shape
+        checked before any device work."""
+        T, nt = _reg_terms(model, self.n_cols, RL_REG_PARAMS)
+        G = self.n_groups
+        bt = np.ascontiguousarray(coef_table, dtype=np.float64)
+        pm = np.ascontiguousarray(params, dtype=np.float64)
+        if bt.shape != (G, self.n_cols):
+            raise ValueError(f"coef_table must have shape ({G}, {self.n_cols})")
+        if pm.shape != (G, 8):
+            raise ValueError(f"params must have shape ({G}, 8)")
+        rows = []
+        for name, val in (("q", q), ("alpha", alpha)):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(val, dtype=np.float64), (G,))
+                                     if np.ndim(val) == 0 else np.asarray(val, dtype=np.float64))
+            if a.shape != (G,):
+                raise ValueError(f"{name} must have one entry per group ({G})")
+            rows.append(a)
+        return T, nt, bt, rows[0], rows[1], pm
+
+    def wiener_like_rl_reg_groups(self, model, coef_table, q, alpha, params, err=1e-4, n_st=2,
+                                  n_sz=2, use_adaptive=1, simps_err=1e-3, w_outlier=0.1,
+                                  terms=False):
+        """One RL regression node per group in one fill launch, one Q scan and
+        one scoring pass: `model` is a list of (param_name, col0, ncol,
+        link_name) with param_name one of v, sv, a, z, sz, t, st, alpha;
+        coef_table (G, C) one coefficient row per group; q (G,) the start of
+        both Q values; alpha (G,) the unbounded learning-rate parameter,
+        ignored when alpha is regressed; params (G, 8) of v, sv, a, z, sz, t,
+        st, p_outlier (one p_outlier for all groups), v the drift scaling
+        unless regressed. Returns the (G,) per-group sums; terms=True: (sums,
+        per-trial terms, {param: predicted array}, drifts, learning rates) in
+        the caller's order, the alpha prediction after the link and before
+        squashing. A regressed alpha's rate is correctly rounded and can
+        differ from the reference's libm value by an ulp of the power
+        (DESIGN.md §25)."""
+        model = list(model)
+        T, nt, bt, qa, al, pm = self._check_groups(model, coef_table, q, alpha, params)
+        K = _lib.make_knobs(err, n_st, n_sz, use_adaptive, simps_err, w_outlier)
+        out = np.empty(self.n_groups, dtype=np.float64)
+        tr = pr = dr = ra = None
+        if terms:
+            tr, dr, ra = (np.empty(self.n, dtype=np.float64) for _ in range(3))
+            pr = np.empty((max(nt, 1), self.n), dtype=np.float64)
+        _lib.check(_lib.wfpt_wiener_like_rl_reg_groups_ex(
+            self.ctx.handle, self.handle, T, nt, _lib.dptr(bt), _lib.dptr(qa), _lib.dptr(al),
+            pm.ctypes.data_as(_lib._PP), ctypes.byref(K), _lib.dptr(out), _optr(tr), _optr(pr),
+            _optr(dr), _optr(ra)))
+        if not terms:
+            return out
+        return out, tr, {m[0]: pr[k] for k, m in enumerate(model)}, dr, ra
+
+    def wiener_like_rl_reg(self, model, coef, q, alpha, v, sv, a, z, sz, t, st, err, n_st=10,
+                           n_sz=10, use_adaptive=1, simps_err=1e-3, p_outlier=0, w_outlier=0,
+                           terms=False):
+        """The reference's node (hddm_rl_regression.py:25-38) over all resident
+        trials of a data set made without group ids: one coefficient vector,
+        scalar q, alpha and parameters. Returns the sum; terms=True as
+        wiener_like_rl_reg_groups."""
+        if self.grouped:
+            raise ValueError("wiener_like_rl_reg needs a data set made without group ids")
+        b = np.ascontiguousarray(np.asarray(coef, dtype=np.float64).ravel())
+        if b.shape != (self.n_cols,):
+            raise ValueError(f"coef must have one entry per design column ({self.n_cols})")
+        P = np.array([[v, sv, a, z, sz, t, st, p_outlier]], dtype=np.float64)
+        r = self.wiener_like_rl_reg_groups(model, b[None, :], [float(q)], [float(alpha)], P, err,
+                                           n_st, n_sz, use_adaptive, simps_err, w_outlier, terms)
+        return (float(r[0][0]),) + r[1:] if terms else float(r[0])
 
 
 def _rl_host(x, response, feedback, split_by, x_optional=False):

@@ -17,6 +17,8 @@
  *   wfpt_wiener_like_nodes_multi <- the same for several parameter tables (chains)
  *                             hddm/likelihoods.py:52-73 via base.py:754-757
  *   wfpt_wiener_like_multi <- wfpt.wiener_like_multi   src/wfpt.pyx:244-274
+ *   wfpt_wiener_like_rl_reg_groups <- HDDMrlRegressor's wienerRL_multi_like per subject,
+ *                             batched  hddm/models/hddm_rl_regression.py:25-38
  *   wfpt_dmat_cdf_array    <- cdfdif_wrapper.dmat_cdf_array
  *                             src/cdfdif_wrapper.pyx:16-53, src/cdfdif.c:59-221
  *   wfpt_gen_rts_nodes     <- wfpt.gen_rts_from_cdf, one call for many rows
@@ -313,7 +315,8 @@ int wfpt_wiener_like_rlddm_nodes_multi_ex(wfpt_ctx *ctx, const wfpt_rl_ds *ds,
 #define WFPT_LINK_EXP 1
 #define WFPT_LINK_INVLOGIT 2
 typedef struct {
-  int32_t param, link, col0, ncol; /* param 0..6 = v, sv, a, z, sz, t, st */
+  int32_t param, link, col0, ncol; /* param 0..6 = v, sv, a, z, sz, t, st; 7 = alpha in
+                                      the wfpt_wiener_like_rl_reg_groups* entries only */
 } wfpt_reg_term;
 typedef struct wfpt_reg_ds wfpt_reg_ds;
 /* Uploads n signed RTs and the row-major (n, C) design matrix X once (the
@@ -363,6 +366,65 @@ int wfpt_wiener_like_reg_groups_ex(wfpt_ctx *ctx, const wfpt_reg_ds *ds,
                                    const double *coef, const wfpt_params *per_group,
                                    const wfpt_knobs *k, double *out_logp, double *out_trial,
                                    double *out_pred);
+
+/* ---- RL regression likelihood (hddm/models/hddm_rl_regression.py) ---------
+ * HDDMrlRegressor's node (hddm_rl_regression.py:25-38) forms trial-wise
+ * parameters, the learning rate's alpha among them, as link(design matrix .
+ * coefficients) and passes them to wfpt.wiener_like_multi_rlddm
+ * (src/wfpt.pyx:277-320), once per subject node with a fresh Q pair. Here the
+ * design matrix, responses, feedback and segment layout are resident and only
+ * a coefficient table and a few rows per group go up per call.
+ *   wfpt_wiener_like_rl_reg_groups* <- one such node per subject, batched
+ * Uploads n signed RTs, responses (0 / 1), feedback, conditions and the
+ * row-major (n, C) design matrix once. Trials are stored group-major, the
+ * caller's order kept inside a group (wfpt_reg_dataset_create). A segment (one
+ * Q recurrence) is a maximal run of equal adjacent split_by inside a group; a
+ * group boundary always starts a segment; every trial is scored, a segment's
+ * first at drift 0 (wiener_like_multi_rlddm's segments). WFPT_ERR_ARG: n < 0,
+ * C < 1, a null array with n > 0, a response outside {0, 1}, |rt| == 999, a
+ * group id out of range. The caller's arrays are not retained. */
+typedef struct wfpt_rl_reg_ds wfpt_rl_reg_ds;
+int wfpt_rl_reg_dataset_create(wfpt_ctx *ctx, const double *rt, const int64_t *response,
+                               const double *feedback, const int64_t *split_by, int64_t n,
+                               const double *X, int32_t C, const int32_t *group_id,
+                               int32_t n_groups, wfpt_rl_reg_ds **out);
+void wfpt_rl_reg_dataset_destroy(wfpt_rl_reg_ds *ds);
+/* One RL regression node per group: coef[n_groups * C], q[n_groups] the start
+ * of both Q values, alpha[n_groups] the unbounded learning-rate parameter,
+ * per_group[n_groups], out_logp[n_groups]. In these entries only,
+ * wfpt_reg_term.param may also be 7 = alpha (at most 8 terms). alpha[g] is
+ * ignored when alpha is regressed; per_group[g].v is the drift scaling unless v
+ * is regressed. Three launches, in this order: a trial-parallel fill (the
+ * terms by the order and link contract above, the non-regressed fields from
+ * the group rows); the Q recurrence, one lane per segment, which writes each
+ * trial's drift (q_up - q_low) * v into the scoring pass's v slot; the scoring
+ * pass and per-group sums of wfpt_wiener_like_reg_groups, whose p_outlier, sz /
+ * st and 2^22-trials-per-group rules apply. A group's sum does not depend on
+ * the other groups of the call; a group without trials sums to 0.0.
+ * Learning-rate contract: rate = e / (1 + e), e = 2.718281828459**alpha (the
+ * double nearest that literal), the sum and the quotient each rounded once. A
+ * non-regressed alpha[g] is squashed on the host with libm's pow, bit for bit
+ * what wfpt_wiener_like_multi_rlddm does with a scalar alpha. A regressed
+ * alpha is squashed on the device, per trial, with the power correctly
+ * rounded: it differs from the reference's libm value by one ulp of the power
+ * where libm misrounds (DESIGN.md §25 has the measured share).
+ * _ex outputs (each nullable, the caller's order): out_trial[n] each trial's
+ * log term; out_pred[n_terms * n] term k's prediction of trial i at [k * n +
+ * i], the alpha term's after the link and before squashing; out_drift[n];
+ * out_rate[n] each trial's learning rate.
+ * WFPT_ERR_ARG, before any device work: null pointers and the term-list
+ * errors of wfpt_wiener_like_reg with parameters 0..7. */
+int wfpt_wiener_like_rl_reg_groups(wfpt_ctx *ctx, const wfpt_rl_reg_ds *ds,
+                                   const wfpt_reg_term *terms, int32_t n_terms,
+                                   const double *coef, const double *q, const double *alpha,
+                                   const wfpt_params *per_group, const wfpt_knobs *k,
+                                   double *out_logp);
+int wfpt_wiener_like_rl_reg_groups_ex(wfpt_ctx *ctx, const wfpt_rl_reg_ds *ds,
+                                      const wfpt_reg_term *terms, int32_t n_terms,
+                                      const double *coef, const double *q, const double *alpha,
+                                      const wfpt_params *per_group, const wfpt_knobs *k,
+                                      double *out_logp, double *out_trial, double *out_pred,
+                                      double *out_drift, double *out_rate);
 
 /* The regressor's posterior predictive: one simulated RT per (sweep, trial),
  * each at the trial's own regressed parameters (wfpt_reg_like's random(),
