@@ -947,6 +947,40 @@ __device__ inline double exp_val(double x) {
   return ldexp(p, (int)k);
 }
 
+// N exponentials at once for the uniform site (lean_uniform_level0): per
+// argument exactly exp_val's operations on the same operands in the same
+// order, so every result has exp_val's bits, but written level by level
+// across the N independent chains. The next instruction of a lone wave then
+// never reads the result of the one before it: no hazard no-ops between the
+// dependent v_fma_f64 of the last chains, and each coefficient is
+// materialised once per level, not once per chain.
+template <int N>
+__device__ inline void exp_val_n(const double (&x)[N], double (&y)[N]) {
+  constexpr double kC[9] = {2.763263963904103e-07,  2.755724091857897e-06, 2.4801485482328494e-05,
+                            1.9841269890047113e-04, 1.3888888952314775e-03, 8.333333333319601e-03,
+                            4.16666666664881e-02,   1.666666666666668e-01,  5.000000000000019e-01};
+  double k[N], r[N], p[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) k[i] = rint(x[i] * 1.4426950408889634);
+#pragma unroll
+  for (int i = 0; i < N; ++i) r[i] = fma(-k[i], 6.9314718055994529e-01, x[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) r[i] = fma(-k[i], 2.3190468138462996e-17, r[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) p[i] = 2.5110037605963777e-08;
+#pragma unroll
+  for (int l = 0; l < 9; ++l) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) p[i] = horner(p[i], r[i], kC[l]);
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) p[i] = fma(p[i], r[i], 1.0);
+#pragma unroll
+  for (int i = 0; i < N; ++i) p[i] = fma(p[i], r[i], 1.0);
+#pragma unroll
+  for (int i = 0; i < N; ++i) y[i] = ldexp(p[i], (int)k[i]);
+}
+
 // Large-time sines of a grid (pdf.pxi:61-62: sin(k pi w) at the grid's 5
 // nodes), k = 1..kSinK, exactly as tnode_pdf_sv_grid5's recurrence produces
 // them: sin / cos of nodes 1..3 rotated from node 0 (node 4 direct), then
@@ -2117,11 +2151,22 @@ __device__ inline bool l0_decisions(const Trial& tr, const Params& P, const Knob
   return ok;
 }
 
+// The clean test's running minimum (lean_uniform_level0) as one v_min_f64.
+// fmin() first quiets every operand the compiler cannot prove canonical (a
+// v_max_f64 x, x per series value); the test does not care whether a NaN
+// operand is passed over or returned.
+__device__ inline double min_raw(double a, double b) {
+  double d;
+  asm("v_min_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+}
+
 // small_grid2d with wave-uniform K, past its guard (uniform_guard passed):
 // the same exponents, exponentials and products per lane, the (grid, K)
-// operands from the table. c: the drift exponents of z nodes 0..2.
-__device__ inline bool small_grid2d_u(double m, double f, double c0, double c1, double c2,
-                                      const UniformTab& U, int K, double (&out)[5]) {
+// operands from the table. c: the drift exponents of z nodes 0..2. smin: the
+// running minimum of the series values (lean_uniform_level0's clean test).
+__device__ inline void small_grid2d_u(double m, double f, double c0, double c1, double c2,
+                                      const UniformTab& U, int K, double (&out)[5], double& smin) {
   const UniformK& C = U.k[K];
   const int lower = -((K - 1) >> 1), upper = K >> 1;  // -floor((K-1)/2.), ceil((K-1)/2.)
   const double d1 = c1 - c0;
@@ -2132,8 +2177,11 @@ __device__ inline bool small_grid2d_u(double m, double f, double c0, double c1, 
   const double aP = (4.0 * m) * C.u0p1;
   const double aQk = 8.0 * m;
   const double aQjk = (4.0 * m) * C.h;
-  double E0 = exp_val(a00), R0 = exp_val(aR), P = exp_val(aP);
-  const double Qj = exp_val(aQj), Qk = exp_val(aQk), Qjk = exp_val(aQjk);
+  const double ax[6] = {a00, aR, aP, aQj, aQk, aQjk};
+  double ey[6];
+  exp_val_n<6>(ax, ey);
+  double E0 = ey[0], R0 = ey[1], P = ey[2];
+  const double Qj = ey[3], Qk = ey[4], Qjk = ey[5];
   double s[5];
 #pragma unroll
   for (int i = 0; i < 5; ++i) s[i] = 0.0;
@@ -2152,21 +2200,37 @@ __device__ inline bool small_grid2d_u(double m, double f, double c0, double c1, 
     P = P * Qk;
     R0 = R0 * Qjk;
   }
-  bool clean = true;
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     out[i] = s[i] * f;
-    clean = clean & (s[i] > 0) & !__builtin_isinf(out[i]);
+    smin = min_raw(smin, s[i]);
   }
-  return clean;
 }
 
 // eng_level0_t<kAdaptTZ, false, true> of one trial of a uniform wave: kpack,
 // smask (wave-uniform: l0_decisions of every lane agree), H the lane's own
-// hints, uniform_guard passed. bail: a node was not clean (a non-positive
-// series value, an infinite product), which the fix-up code of
+// hints, uniform_guard passed. bail: a node may not have been clean (a
+// non-positive series value, an infinite product), which the fix-up code of
 // tnode_pdf_sv_grid5 handles: the caller reruns the whole wave on
 // eng_level0_t and discards this result.
+//
+// The clean test. eng_level0_t's node is clean when each of its five series
+// values is > 0 and none of the five products f_i is infinite. Here the 25
+// series values feed one running fmin (smin) and the products are not tested
+// at all: bail = !(smin > 0) || the root's S2 is not finite. That bails
+// whenever some node is not clean (and possibly more often, never less; a
+// bail only reruns the wave on the generic site, whose bits are the
+// contract, so a superset is safe and a subset would not be):
+//   * a series value <= 0 makes smin <= 0 or NaN (v_min_f64 passes over a NaN
+//     operand or returns it, never a larger value);
+//   * a NaN series value makes its product f_i NaN, an infinite product is
+//     non-finite already, and non-finiteness survives every later operation
+//     on the way to the root's S2: a sum with a non-finite addend and a
+//     product with a non-finite factor are non-finite (inf - inf and inf * 0
+//     give NaN). f_i is a factor of f_i * iZz, that an addend of the node's
+//     Sl or Sr (simp5p), those the addends of its S2, S2 an addend of
+//     simp_value, that a factor of y, and each of the five y an addend of
+//     the root's Sl or Sr, whose sum is the root's S2.
 __device__ inline int lean_uniform_level0(const Trial& tr, const Params& P, const Knobs& K,
                                           const ZGrid& G, const UniformTab& U, const double* stab,
                                           const L0Hints& H, unsigned kpack, unsigned smask,
@@ -2182,7 +2246,7 @@ __device__ inline int lean_uniform_level0(const Trial& tr, const Params& P, cons
   const double iZz = 1.0 / ((tr.z + tr.sz / 2.) - (tr.z - tr.sz / 2.));
   const double h = ub - lb;
   int flags = 0;
-  bool clean = true;
+  double smin = __builtin_inf();
   double X = 0.0, Y = 0.0, Z = 0.0, y4 = 0.0;
   // unrolled like eng_level0_t's node loop (a rolled loop measured 3% slower):
   // tc, qh(j) and the Simpson bookkeeping fold per node
@@ -2208,7 +2272,7 @@ __device__ inline int lean_uniform_level0(const Trial& tr, const Params& P, cons
       const double r = rsqrt(tt), r2 = r * r;
       const double rn = kInvSqrt2Pi * (r2 * r);
       const double m = -0.5 * r2;
-      clean = small_grid2d_u(m, rn * sc, c0, c1, c2, U, Kj, f) && clean;
+      small_grid2d_u(m, rn * sc, c0, c1, c2, U, Kj, f, smin);
     } else {
       // (H.q0 >= 0: the recurrence's q, as tnode_setup_r takes it from qh(j))
       const double m = H.qh(j);
@@ -2230,13 +2294,16 @@ __device__ inline int lean_uniform_level0(const Trial& tr, const Params& P, cons
       // the drift factors (|c| < 600 by uniform_guard: the `moderate` form)
       const double d1 = c1 - c0;
       const double d2 = (c2 - c1) - d1;
-      double ex = exp_val(c0);
-      double rr = exp_val(d1);
-      const double qd = exp_val(d2);
+      const double dx[3] = {c0, d1, d2};
+      double dy[3];
+      exp_val_n<3>(dx, dy);
+      double ex = dy[0];
+      double rr = dy[1];
+      const double qd = dy[2];
 #pragma unroll
       for (int i = 0; i < 5; ++i) {
         f[i] = (pp[i] * ex) * sc;
-        clean = clean & (pp[i] > 0) & !__builtin_isinf(f[i]);
+        smin = min_raw(smin, pp[i]);
         ex = ex * rr;
         rr = rr * qd;
       }
@@ -2255,14 +2322,14 @@ __device__ inline int lean_uniform_level0(const Trial& tr, const Params& P, cons
     X = (j == 0 || j == 2) ? y : (j == 3 ? x4 : X);
     y4 = y;
   }
-  bail = !clean;
-  if (flags & kFlagExact) return kExact;
-  if (pend) return kTree;
   Simp s;
   s.S = (h / 6) * (Y + y4);
   s.Sl = Z;
   s.Sr = (h / 12) * (X + y4);
   s.S2 = s.Sl + s.Sr;
+  bail = !(smin > 0) || !__builtin_isfinite(s.S2);
+  if (flags & kFlagExact) return kExact;
+  if (pend) return kTree;
   const bool refine = simpson_refine(s.S, s.S2, K.simps_err, K.n_st, flags);
   if (flags & kFlagExact) return kExact;
   if (refine) return kTree;
