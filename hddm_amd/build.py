@@ -23,7 +23,9 @@ SOURCES = ["wfpt_node.hip", "wfpt_sum.hip", "wfpt_engine.hip", "wfpt_fold.hip",
            "capi_core.cpp", "capi_comm.cpp", "capi_rl.cpp", "capi_reg.cpp", "capi_sim.cpp",
            "capi_rl_reg.cpp",
            "wfpt_rendezvous.cpp"]
-DEPS = SOURCES + ["wfpt_device.hpp", "wfpt_kernel_common.hpp", "wfpt_engine.hpp",
+DEPS = SOURCES + ["wfpt_types.hpp", "wfpt_math.hpp", "wfpt_series.hpp", "wfpt_quad.hpp",
+                  "wfpt_zgrid.hpp", "wfpt_grid.hpp", "wfpt_level0.hpp", "wfpt_lean_tables.hpp",
+                  "wfpt_lean.hpp", "wfpt_kernel_common.hpp", "wfpt_engine.hpp",
                   "wfpt_internal.h", "rl_internal.h", "sim_internal.h", "reg_internal.h",
                   "stats_internal.h", "sim_philox.hpp", "rl_update.hpp", "reg_predict.hpp",
                   "pointwise_internal.h", "pointwise_update.hpp", "capi_internal.hpp",

@@ -21,8 +21,9 @@
 
 #include "../../include/wfpt_amd.h"
 #include "pointwise_internal.h"
-#include "wfpt_device.hpp"
 #include "wfpt_internal.h"
+#include "wfpt_lean_tables.hpp"
+#include "wfpt_types.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -251,7 +252,7 @@ struct wfpt_ctx {
   DevBuf<int> fin_ticket;    // its last-block ticket (0 at rest)
   DevBuf<int> prof;          // 16 refinement work counters (PROF_EVALS)
   DevBuf<unsigned long long> phase;  // engine phase cycles (diagnostic builds)
-  // The lean pass's series-decision table (wfpt_device.hpp: decision_tab). It
+  // The lean pass's series-decision table (wfpt_lean_tables.hpp: decision_tab). It
   // depends on err alone and costs ~0.2 ms of bisection, so it is kept here,
   // keyed by err's bit pattern, and rebuilt only when err changes. It travels
   // to the kernel by value, so there is nothing to upload.

@@ -14,7 +14,7 @@
 
 #include "reg_internal.h"
 #include "reg_predict.hpp"
-#include "wfpt_device.hpp"
+#include "wfpt_types.hpp"
 
 #pragma clang fp contract(off)
 

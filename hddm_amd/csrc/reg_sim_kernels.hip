@@ -11,7 +11,7 @@
 #include "reg_internal.h"
 #include "reg_predict.hpp"
 #include "sim_philox.hpp"
-#include "wfpt_device.hpp"
+#include "wfpt_types.hpp"
 
 #pragma clang fp contract(off)
 

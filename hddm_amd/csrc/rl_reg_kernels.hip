@@ -18,7 +18,7 @@
 #include "reg_predict.hpp"
 #include "rl_reg_internal.h"
 #include "rl_update.hpp"
-#include "wfpt_device.hpp"
+#include "wfpt_types.hpp"
 
 #pragma clang fp contract(off)
 

@@ -18,7 +18,8 @@
 
 #include "sim_internal.h"
 #include "sim_philox.hpp"
-#include "wfpt_device.hpp"
+#include "wfpt_quad.hpp"
+#include "wfpt_types.hpp"
 
 #pragma clang fp contract(off)
 

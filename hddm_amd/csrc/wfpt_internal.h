@@ -8,11 +8,10 @@
 #include <type_traits>
 
 #include "../../include/wfpt_amd.h"
+#include "wfpt_lean_tables.hpp"
+#include "wfpt_types.hpp"
 
 namespace wfpt {
-struct Params;
-struct Knobs;
-struct DecisionTab;
 
 // Deferred-trial state of one call, slot-indexed (slot = chunk * 64 + rank
 // of the trial among its chunk's deferred trials; nslots = chunks * 64). The

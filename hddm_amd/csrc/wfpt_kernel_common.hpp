@@ -20,7 +20,7 @@
 //                         boundary-uniform root grids in scalar registers (4
 //                         waves/SIMD; the 2-D family's waves whose lanes agree on
 //                         every t node's series decision keep those in scalar
-//                         registers too: lean_uniform_level0, wfpt_device.hpp):
+//                         registers too: lean_uniform_level0, wfpt_lean.hpp):
 //                         a chunk none of whose trials refines
 //                         ends here (mixture, log, chunk partial); a chunk that
 //                         refines is flagged for the engine's redo pass
@@ -43,8 +43,15 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "wfpt_device.hpp"
+#include "wfpt_grid.hpp"
 #include "wfpt_internal.h"
+#include "wfpt_lean_tables.hpp"
+#include "wfpt_level0.hpp"
+#include "wfpt_math.hpp"
+#include "wfpt_quad.hpp"
+#include "wfpt_series.hpp"
+#include "wfpt_types.hpp"
+#include "wfpt_zgrid.hpp"
 
 #pragma clang fp contract(off)
 

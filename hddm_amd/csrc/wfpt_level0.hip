@@ -5,7 +5,7 @@
 //                        flagged for the engine's redo pass (wfpt_engine.hip).
 //                        The 2-D family has two sites: waves whose lanes agree
 //                        on every t node's series decision (lean_uniform_level0,
-//                        wfpt_device.hpp) and the per-lane one (eng_level0_t).
+//                        wfpt_lean.hpp) and the per-lane one (eng_level0_t).
 //                        A wave learns that its lanes agree from the decision's
 //                        breakpoint table (table_decisions: its two extreme
 //                        |rt| looked up) or, where the table has no answer,
@@ -18,6 +18,7 @@
 //                        pre-pass 170 to 410
 // (One-block calls run level 0 and the finalize in one launch: wfpt_sum.hip.)
 #include "wfpt_kernel_common.hpp"
+#include "wfpt_lean.hpp"
 
 #pragma clang fp contract(off)
 

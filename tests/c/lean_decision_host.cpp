@@ -1,6 +1,6 @@
 // Host program for tests/test_lean_decision_host.py (its own main; built with
 // -fsanitize=address,undefined, never loaded into Python): the lean pass's
-// series-decision table (decision_tab, hddm_amd/csrc/wfpt_device.hpp) against
+// series-decision table (decision_tab, hddm_amd/csrc/wfpt_lean_tables.hpp) against
 // the reference's formula (pdf.pxi:36-60), restated below with the host libm
 // (what the reference itself runs) together with decide64's ambiguity tests.
 #include <algorithm>
@@ -11,7 +11,8 @@
 #include <random>
 #include <vector>
 
-#include "../../hddm_amd/csrc/wfpt_device.hpp"
+#include "../../hddm_amd/csrc/wfpt_lean_tables.hpp"
+#include "../../hddm_amd/csrc/wfpt_zgrid.hpp"
 
 #pragma clang fp contract(off)
 

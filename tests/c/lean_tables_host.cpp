@@ -5,7 +5,7 @@
 // against small_grid2d's per-node `safe`.
 //
 // The lane's expressions are restated below from small_grid2d
-// (hddm_amd/csrc/wfpt_device.hpp), which is device code: the same operations
+// (hddm_amd/csrc/wfpt_grid.hpp), which is device code: the same operations
 // in the same order, contraction off. m is formed as -0.5 / tt here (the
 // device takes it from rsqrt: a few ulp apart, far inside the guard's margin).
 #include <cmath>
@@ -14,7 +14,9 @@
 #include <cstring>
 #include <random>
 
-#include "../../hddm_amd/csrc/wfpt_device.hpp"
+#include "../../hddm_amd/csrc/wfpt_lean_tables.hpp"
+#include "../../hddm_amd/csrc/wfpt_types.hpp"
+#include "../../hddm_amd/csrc/wfpt_zgrid.hpp"
 
 #pragma clang fp contract(off)
 

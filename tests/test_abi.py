@@ -194,6 +194,26 @@ def test_build_lists_cover_csrc():
     assert len(hb.DEPS) == len(set(hb.DEPS)) and len(hb.SOURCES) == len(set(hb.SOURCES))
 
 
+CSRC_HEADERS = sorted(f for f in os.listdir(os.path.join(ROOT, "hddm_amd", "csrc"))
+                      if f.endswith((".hpp", ".h")))
+
+
+@pytest.mark.parametrize("header", CSRC_HEADERS)
+def test_header_includes_what_it_uses(header, tmp_path):
+    """Each header under hddm_amd/csrc compiles as the only include of a
+    translation unit, with the library's flags, in the host and the device pass
+    (-x hip): what it uses it includes itself, whatever order its includers
+    name it in."""
+    from hddm_amd import build as hb
+    if not os.path.exists(hb.HIPCC):
+        pytest.skip("hipcc not present")
+    tu = tmp_path / "only.hip"
+    tu.write_text('#include "%s"\n' % os.path.join(hb.CSRC, header))
+    r = subprocess.run([hb.HIPCC, *hb.CFLAGS, "-fsyntax-only", "-x", "hip", str(tu)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+
+
 @pytest.mark.gpu
 def test_close_detaches_live_datasets_of_every_kind(gpu):
     """One context, one dataset of each kind (plain, RL, regression) at n = 65

@@ -1,5 +1,5 @@
-"""The lean pass's series-decision table (decision_tab, wfpt_device.hpp's host
-side) on the host (no GPU): tests/c/lean_decision_host.cpp is a stand-alone
+"""The lean pass's series-decision table (decision_tab, wfpt_lean_tables.hpp)
+on the host (no GPU): tests/c/lean_decision_host.cpp is a stand-alone
 program (its own main) built under AddressSanitizer +
 UndefinedBehaviorSanitizer and run directly.
 

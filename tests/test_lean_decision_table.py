@@ -16,7 +16,7 @@ not lean_kernel.
 The breakpoints are bisected below from the reference's formula
 (test_lean_uniform.decisions); at err = 1e-4 they are tt = 0.0552731,
 0.153704, 0.216098, 0.449156, 1.54613. The table's guard band is 1e-6
-relative (wfpt_device.hpp: kDecBand).
+relative (wfpt_lean_tables.hpp: kDecBand).
 """
 import math
 

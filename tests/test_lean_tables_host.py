@@ -1,6 +1,6 @@
 """The lean pass's uniform-wave host table and its per-trial range test, on the
 host (no GPU): tests/c/lean_tables_host.cpp is a stand-alone program (its own
-main) built from hddm_amd/csrc/wfpt_device.hpp's host side under
+main) built from hddm_amd/csrc/wfpt_lean_tables.hpp and wfpt_zgrid.hpp under
 AddressSanitizer + UndefinedBehaviorSanitizer.
 
   * uniform_tab: for 1,000 random (z, sz, boundary, v, sv, a) grids every

@@ -436,7 +436,7 @@ def test_extreme_parameters_match_reference(gpu, oracle_lib, p):
 
 @pytest.mark.parametrize("case", ["tiny_tt", "many_terms", "big_drift", "sz_wide", "a_small"])
 def test_small_time_table_paths(gpu, oracle_lib, case):
-    """The small-time grid's 2-D recurrence (wfpt_device.hpp: small_grid2d)
+    """The small-time grid's 2-D recurrence (wfpt_grid.hpp: small_grid2d)
     and its node-by-node fallback: short decision times (8|m| beyond the
     table's exponent bound: the fallback), small err (K up to 8 and past it),
     large drift exponents (sv, v), wide z intervals and small a; per trial
