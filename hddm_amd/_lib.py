@@ -139,6 +139,7 @@ _SIGNATURES = {
     "wfpt_profile_lists": (_I, [_VP, _PI64, _I]),
     "wfpt_debug_waves": (_I, [_VP, _PU64, _I64]),
     "wfpt_debug_partials": (_I, [_VP, _PD, _PI32, _I64]),
+    "wfpt_debug_lean_first": (_I, [_VP, _PI32, _I32, _PI32]),
     "wfpt_last_path": (_I, [_VP, _PI]),
     # reinforcement-learning family
     "wfpt_rl_dataset_create": (_I, [_VP, _PD, _PI64, _PD, _PI64, _I64, _PI32, _I32, _PVP]),
@@ -337,6 +338,13 @@ class Context:
         v = _I()
         check(wfpt_last_path(self.handle, ctypes.byref(v)))
         return v.value
+
+    def lean_first(self):
+        """The chunks the last call's lean pass dispatched first (wfpt_debug_lean_first)."""
+        out = np.zeros(64, dtype=np.int32)
+        n = _I32()
+        check(wfpt_debug_lean_first(self.handle, out.ctypes.data_as(_PI32), 64, ctypes.byref(n)))
+        return [int(v) for v in out[:n.value]]
 
     def partials(self, n):
         """The first n chunk partials {sum, zero word} of the last summing call."""

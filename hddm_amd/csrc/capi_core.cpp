@@ -21,6 +21,9 @@ constexpr int64_t kSplitCap = 16384;  // heavy chunks a dataset records per call
 // are at most 1 / kHeavyFewDiv of its chunks: then they are the launch's
 // tail; when many chunks are heavy, splitting them only adds waves
 constexpr int64_t kHeavyFewDiv = 16;
+// dispatch rounds up to which the lean pass's list of first chunks is used
+// (capi_internal.hpp: lean_first_max)
+constexpr int64_t kLeanFirstRounds = 8;
 
 namespace wfpt {
 namespace capi {
@@ -190,7 +193,10 @@ int run_sum(wfpt_ctx* c, const double* dx, int64_t n, const wfpt::Params& P,
   wfpt::Work W;
   if (int rc = reserve_work(c, n, &W)) return rc;
   const bool adaptive = wfpt::has_deferred_pass(P, K);
-  if (part & wfpt::kPassFast) c->path = 0;  // a call sequence starts
+  if (part & wfpt::kPassFast) {  // a call sequence starts
+    c->path = 0;
+    c->first_last.n = 0;
+  }
   if (c->count && (part & wfpt::kPassFast))
     HIP_TRY(hipMemsetAsync(c->evals.p, 0, sizeof(unsigned long long), c->stream));
   // profiling: ev0..ev1 bracket the level-0 fast kernel (the dominant kernel,
@@ -219,14 +225,22 @@ int run_sum(wfpt_ctx* c, const double* dx, int64_t n, const wfpt::Params& P,
     }
   }
   const wfpt::Split S = eng ? split_of(d) : wfpt::Split{};
+  // the 2-D family's lean pass over more than one dispatch round of a dataset
+  // in stored order: the chunks that hold a breakpoint of the decision table
+  // go first (one binary search per boundary, t node and finite upper edge of
+  // a piece over the host index: 60 at err = 1e-4)
+  const bool lean2d = (part & wfpt::kPassLean) &&
+                      wfpt::select_mode(P.sz, P.st, K.use_adaptive) == wfpt::kAdaptTZ;
+  if (lean2d && c->lean_first && d && d->lean_index.first && d->nw > c->lean_first_min &&
+      d->nw <= c->lean_first_max)
+    wfpt::lean_first_search(*decision_tab_of(c, K.err), d->lean_index, P.a, P.t, P.st,
+                            c->first_last);
   wfpt::launch_trials(c->trial ? 3 : 0, adaptive ? part : wfpt::kPassAll, dx, n, P, K, c->part.p,
                       c->zero.p, c->count ? c->evals.p : nullptr, c->status.p, 0, W, c->stream,
                       prof ? c->ev1 : nullptr, &S, c->trial,
-                      // (only the 2-D family's lean kernel reads the table)
-                      ((part & wfpt::kPassLean) &&
-                       wfpt::select_mode(P.sz, P.st, K.use_adaptive) == wfpt::kAdaptTZ)
-                          ? decision_tab_of(c, K.err)
-                          : nullptr);
+                      // (only the 2-D family's lean kernel reads the table and the list)
+                      lean2d ? decision_tab_of(c, K.err) : nullptr,
+                      lean2d ? &c->first_last : nullptr);
   if (!adaptive) {
     c->path |= WFPT_PATH_FIXED;
   } else {
@@ -512,6 +526,13 @@ int wfpt_open(int device, wfpt_ctx** out) {
   if (const char* lm = std::getenv("WFPT_LEAN")) c->lean = std::strcmp(lm, "0") != 0;
   if (const char* sm = std::getenv("WFPT_SMALL")) c->small = std::strcmp(sm, "0") != 0;
   if (const char* lt = std::getenv("WFPT_LEAN_TREE")) c->lean_tree_max = std::atof(lt);
+  if (const char* lf = std::getenv("WFPT_LEAN_FIRST")) c->lean_first = std::strcmp(lf, "0") != 0;
+  {  // the list pays from more than one dispatch round up to kLeanFirstRounds of them
+    const int64_t slots = wfpt::lean_wave_slots();
+    c->lean_first_min = slots > 0 ? slots : INT64_MAX;
+    c->lean_first_max = slots > 0 ? slots * kLeanFirstRounds : 0;
+    if (const char* fm = std::getenv("WFPT_LEAN_FIRST_MIN")) c->lean_first_min = std::atoll(fm);
+  }
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreate(&c->ev0);
   if (e == hipSuccess) e = hipEventCreate(&c->ev1);
@@ -626,6 +647,10 @@ int wfpt_dataset_create_ex(wfpt_ctx* c, const double* rt, int64_t n, const int32
   if (e == hipSuccess && node_id) e = upload_vec(d->off, off);
   // heavy-chunk record (Split): lists sized for up to kSplitCap chunks
   d->nw = (n + 63) / 64;
+  if (!node_id && !keep_order && n > 0) {  // stored order: the lean pass's dispatch index
+    d->chunk_first.resize(d->nw);
+    wfpt::lean_index(hx.data(), n, d->chunk_first.data(), d->lean_index);
+  }
   d->split_cap = (int)std::min<int64_t>(std::max<int64_t>(d->nw, 1), kSplitCap);
   const size_t cap = d->split_cap;
   auto zeroed = [&](auto& b, size_t count) {
@@ -1492,6 +1517,15 @@ int wfpt_debug_waves(wfpt_ctx* c, uint64_t* out, int64_t max_records) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   const int64_t n = std::min<int64_t>(max_records, wfpt::kPhaseWaves);
   HIP_TRY(hipMemcpy(out, c->phase.p, n * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return WFPT_OK;
+}
+
+int wfpt_debug_lean_first(wfpt_ctx* c, int32_t* chunks, int32_t max_chunks, int32_t* n) {
+  if (!c || !n || (max_chunks > 0 && !chunks) || max_chunks < 0)
+    return fail(WFPT_ERR_ARG, "bad arguments");
+  std::lock_guard<std::mutex> lk(c->mu);
+  *n = c->first_last.n;
+  for (int k = 0; k < c->first_last.n && k < max_chunks; ++k) chunks[k] = c->first_last.c[k];
   return WFPT_OK;
 }
 

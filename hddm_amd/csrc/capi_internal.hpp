@@ -301,6 +301,19 @@ struct wfpt_ctx {
   bool fast_only = true;       // WFPT_FAST_ONLY=0: resident calls always enqueue the slow pass
   bool lean = true;            // WFPT_LEAN=0: resident calls never use the lean level-0 pass
   bool small = true;           // WFPT_SMALL=0: one-block calls keep the separate finalize
+  // WFPT_LEAN_FIRST=0: the lean pass takes every chunk in stored order. Else a
+  // call whose chunks exceed lean_first_min (the device's wave slots at the
+  // lean kernel's 4 waves per SIMD: more than one dispatch round;
+  // WFPT_LEAN_FIRST_MIN overrides it, for tests on small data) dispatches the
+  // chunks predicted to take the generic site first (lean_first_search).
+  // Above lean_first_max chunks (kLeanFirstRounds dispatch rounds) the list is
+  // off again: the gain is one generic wave's excess at the launch's end (4.4
+  // us of C3's 60.9), while the build that reads the list runs its uniform
+  // waves up to 2% slower (0.9 us per 1M trials by the 100M-trial set), which
+  // overtakes the gain near 5M trials = 19 rounds; 8 keeps a factor of two.
+  bool lean_first = true;
+  int64_t lean_first_min = 0, lean_first_max = 0;
+  wfpt::LeanFirst first_last{};  // the last likelihood call's list (wfpt_debug_lean_first)
   // WFPT_LEAN_TREE: the largest fraction of refining chunks (last call) for
   // which the lean pass + engine redo of those chunks beats the engine over
   // every chunk
@@ -359,6 +372,11 @@ struct wfpt_ds : wfpt::capi::DsBase {
   // diagnostic calls are returned in the caller's order; kept in HBM, not in
   // host memory: 8 B per trial); null = identity (WFPT_DS_INPUT_ORDER)
   DevBuf<int64_t> perm;
+  // host: the lean pass's dispatch index of a dataset in stored order (first
+  // |rt| of every chunk, 8 B per chunk; wfpt_lean_tables.hpp: LeanIndex).
+  // Empty for input-order and per-node datasets.
+  std::vector<double> chunk_first;
+  wfpt::LeanIndex lean_index{};
   bool identity = true;  // stored order == the caller's order (perm never allocated)
   void free_device() override {
     wfpt::capi::release_all(x, node, off, perm, hpred[0], hpred[1], hlist[0], hlist[1], hcount,

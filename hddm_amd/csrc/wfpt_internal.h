@@ -90,13 +90,19 @@ int64_t partials_for(int64_t n, const Params& P, const Knobs& K);
 // and counted as deferred), and kPassRedo runs the engine over the flagged
 // chunks (before the fold). fast_done (optional) is recorded right after the
 // level-0 / trial kernel. dtab (optional): the lean pass's series-decision
-// table for K.err (decision_tab; null: its waves decide per lane).
+// table for K.err (decision_tab; null: its waves decide per lane). first
+// (optional): the chunks the lean pass of the 2-D family dispatches first
+// (lean_first_search; null or n = 0: stored order).
 constexpr int kPassFast = 1, kPassDeferred = 2, kPassAll = 3, kPassLean = 4, kPassRedo = 8;
 void launch_trials(int out_kind, int part, const double* x, int64_t n, const Params& P,
                    const Knobs& K, double* out, int* zeros, unsigned long long* evals, int* status,
                    int logp, const Work& W, hipStream_t s, hipEvent_t fast_done = nullptr,
                    const Split* split = nullptr, double* trial = nullptr,
-                   const DecisionTab* dtab = nullptr);
+                   const DecisionTab* dtab = nullptr, const LeanFirst* first = nullptr);
+// Wave slots of the 2-D family's lean kernel on the current device (resident
+// blocks per CU by the runtime's occupancy query x waves per block x CUs; 0:
+// unknown): a lean launch of more chunks than this takes more than one round.
+int64_t lean_wave_slots();
 // out[0..3] = {sum of nb partials, #zero trials, encoded error flags,
 // kResDeferred (defer_bits: some chunk's zero word carries kZeroDefer) |
 // kResTree (*tree_any; then *tree_any = 0)}, out[6] = *tree_any (chunks that

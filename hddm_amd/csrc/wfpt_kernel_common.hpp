@@ -358,8 +358,9 @@ inline void with_build(bool count, int out, F&& f) {
 // wfpt_level0.hip: the level-0 pass of the direct family / the lean pass.
 void launch_direct(bool count, int out, const TrialArgs& A, const Work& W, hipStream_t s);
 // dt: the call's decision table (decision_tab of its err; null: one that never answers)
+// first: the chunks dispatched first (the 2-D family; null: stored order)
 void launch_lean(int mode, bool count, int out, const TrialArgs& A, const Work& W, hipStream_t s,
-                 const DecisionTab* dt);
+                 const DecisionTab* dt, const LeanFirst* first = nullptr);
 // wfpt_engine.hip: S's split units, then one wave per chunk (Split{}: the
 // redo pass over the chunks W.redo flags).
 void launch_engine(int mode, bool count, int out, const TrialArgs& A, const Work& W,

@@ -66,6 +66,41 @@ __device__ inline bool table_decisions(const DecisionTab& D, double xs, double l
   return ok;
 }
 
+// For a wave table_decisions did not settle: true if the table nevertheless
+// proves it non-uniform. The own lanes' |rt| are nondecreasing, both extremes
+// lie inside a piece the table holds at every node, and at some node in two
+// different pieces with different codes: there the first and the last own
+// lane have different reference decisions, so no vote over the lanes' own
+// decisions (l0_decisions) can pass and the per-lane pre-pass is wasted work.
+// The same lookups as table_decisions, redone here (a handful of waves per
+// launch) so that the settled waves' path stays as it is.
+__device__ inline bool table_split(const DecisionTab& D, double xs, double lb, double ub,
+                                   double ia2, unsigned long long own, int lane) {
+  const double prev = __shfl_up(xs, 1);
+  const bool mine = ((own >> lane) & 1ull) != 0ull;
+  if (__ballot(mine && !(prev <= xs)) != 0ull) return false;
+  const int last = __popcll(own) - 1;
+  const double xmin = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xs), 0),
+                                       __builtin_amdgcn_readlane(__double2loint(xs), 0));
+  const double xmax = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xs), last),
+                                       __builtin_amdgcn_readlane(__double2loint(xs), last));
+  const double e = D.edge[lane];
+  const double c = (ub + lb) / 2.;
+  const double d = (lb + c) / 2., f = (c + ub) / 2.;
+  bool inside = true, differ = false;
+#pragma unroll 1
+  for (int j = 0; j < 5; ++j) {
+    const double tc = j == 0 ? lb : j == 1 ? d : j == 2 ? c : j == 3 ? f : ub;
+    const int n0 = __popcll(__ballot(e <= (xmin - tc) * ia2));
+    const int n1 = __popcll(__ballot(e <= (xmax - tc) * ia2));
+    const unsigned c0 = D.code[(n0 >> 1) & (kDecPieces - 1)];
+    const unsigned c1 = D.code[(n1 >> 1) & (kDecPieces - 1)];
+    inside = inside && (n0 & 1) != 0 && (n1 & 1) != 0 && c0 != 0u && c1 != 0u;
+    differ = differ || (n0 != n1 && c0 != c1);
+  }
+  return inside && differ;
+}
+
 // Each lane's own five decisions, by today's operations: l0_hints for t nodes
 // 0 and 4 and its `shared` rule, decide32 for nodes 1..3 otherwise. False
 // (the lane's wave takes eng_level0_t) for invalid parameters, a node with

@@ -235,4 +235,106 @@ inline unsigned decision_lookup(const DecisionTab& T, double tt, int* count = nu
   return (n & 1) ? T.code[(n >> 1) & (kDecPieces - 1)] : 0u;
 }
 
+// Dispatch order of the lean pass. A wave whose 64 |rt| straddle a breakpoint
+// of the table at some t node cannot be uniform: it runs the per-lane site,
+// about twice a uniform wave's time, and one dispatched in the launch's last
+// round ends after every uniform wave. The host predicts those chunks from a
+// small index of the dataset and the kernel dispatches them first
+// (lean_kernel: LeanFirst). A prediction only: a chunk listed wrongly, or
+// missed, changes nothing but the order in which chunks are taken.
+constexpr int kLeanFirstMax = 64;
+struct LeanFirst {
+  int n;  // 0: chunks in their stored order
+  int c[kLeanFirstMax];
+};
+// The index of a dataset in stored order (lower boundary first, |rt| ascending
+// inside a boundary, NaN RTs last among the lower boundary's): the first |rt|
+// of every 64-trial chunk and where the boundaries begin and end.
+struct LeanIndex {
+  const double* first;  // [nw] |rt| of trial 64 c
+  int64_t nw;           // chunks
+  int64_t lower_n;      // lower-boundary trials with a non-NaN RT: [0, lower_n)
+  int64_t upper;        // the first upper-boundary trial (n: none), upper-boundary trials: [upper, n)
+  int64_t n;
+  double upper_first;   // |rt| of trial `upper`
+  double last[2];       // the largest |rt| of each boundary
+};
+// x[n]: the trials in stored order; first: (n + 63) / 64 doubles the index keeps.
+inline void lean_index(const double* x, int64_t n, double* first, LeanIndex& I) {
+  const int64_t nw = (n + 63) / 64;
+  for (int64_t w = 0; w < nw; ++w) first[w] = __builtin_fabs(x[w * 64]);
+  int64_t up = 0;  // the lower boundary: x <= 0, and the NaN RTs
+  while (up < n && !(x[up] > 0)) ++up;
+  int64_t ln = up;
+  while (ln > 0 && x[ln - 1] != x[ln - 1]) --ln;
+  I.first = first;
+  I.nw = nw;
+  I.n = n;
+  I.upper = up;
+  I.lower_n = ln;
+  I.upper_first = up < n ? __builtin_fabs(x[up]) : 0.0;
+  I.last[0] = ln > 0 ? __builtin_fabs(x[ln - 1]) : 0.0;
+  I.last[1] = up < n ? __builtin_fabs(x[n - 1]) : 0.0;
+}
+// The chunk of boundary b (0 lower, 1 upper) that owns |rt| = r: the last one
+// whose first |rt| of that boundary is <= r; -1 outside the boundary's data.
+// (Chunk c owns everything up to chunk c + 1's first |rt|, so an r between
+// two neighbouring chunks' trials names the earlier chunk.)
+inline int64_t lean_chunk_of(const LeanIndex& I, int b, double r) {
+  int64_t lo, hi;  // chunks (lo, hi) are keyed by first[]; chunk lo by k0
+  double k0;
+  if (b == 0) {
+    if (I.lower_n <= 0) return -1;
+    lo = 0;
+    hi = (I.lower_n + 63) / 64;
+    k0 = I.first[0];
+  } else {
+    if (I.upper >= I.n) return -1;
+    lo = I.upper / 64;
+    hi = I.nw;
+    k0 = I.upper_first;
+  }
+  if (!(r >= k0 && r <= I.last[b])) return -1;
+  int64_t l = lo, h = hi;  // first[c] <= r for lo < c <= l, first[c] > r for c >= h
+  while (h - l > 1) {
+    const int64_t m = l + (h - l) / 2;
+    if (I.first[m] <= r) l = m;
+    else h = m;
+  }
+  return l;
+}
+// The chunks that hold a breakpoint: per boundary, t node (the five of
+// table_decisions: lb = t - st / 2, ub = t + st / 2 and the three between) and
+// finite upper edge of a piece, the chunk that owns tc_j + edge a^2. Sorted,
+// without duplicates; of more than kLeanFirstMax the latest in stored order.
+inline void lean_first_search(const DecisionTab& D, const LeanIndex& I, double a, double t,
+                              double st, LeanFirst& F) {
+  F.n = 0;
+  for (int k = 0; k < kLeanFirstMax; ++k) F.c[k] = 0;
+  if (!I.first || I.nw <= 0) return;
+  const double lb = t - st / 2., ub = t + st / 2.;
+  const double c = (ub + lb) / 2.;
+  const double tc[5] = {lb, (lb + c) / 2., c, (c + ub) / 2., ub};
+  const double a2 = a * a;
+  int64_t cand[2 * 5 * kDecPieces];
+  int nc = 0;
+  for (int b = 0; b < 2; ++b)
+    for (int j = 0; j < 5; ++j)
+      for (int p = 0; p < kDecPieces; ++p) {
+        const double e = D.edge[2 * p + 1];
+        if (!(e < __builtin_inf())) continue;
+        const int64_t ch = lean_chunk_of(I, b, tc[j] + e * a2);
+        if (ch < 0) continue;
+        int q = nc;  // insertion, ascending, no duplicates
+        while (q > 0 && cand[q - 1] > ch) --q;
+        if (q > 0 && cand[q - 1] == ch) continue;
+        for (int s = nc; s > q; --s) cand[s] = cand[s - 1];
+        cand[q] = ch;
+        ++nc;
+      }
+  const int skip = nc > kLeanFirstMax ? nc - kLeanFirstMax : 0;
+  F.n = nc - skip;
+  for (int k = 0; k < F.n; ++k) F.c[k] = (int)cand[skip + k];
+}
+
 }  // namespace wfpt

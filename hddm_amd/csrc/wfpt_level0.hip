@@ -88,18 +88,42 @@ void direct_kernel(TrialArgs A, Work W, DirectArgs D) {
 constexpr int kLeanBlock = WFPT_LEAN_BLOCK;
 static_assert(kLeanBlock % 64 == 0 && kLeanBlock <= kFastBlock, "kLeanBlock");
 static_assert(sizeof(TrialArgs) + sizeof(Work) + sizeof(RootGrids) + sizeof(UniformTabs) +
-                      sizeof(DecisionTab) <= 4096,
+                      sizeof(DecisionTab) + sizeof(LeanFirst) <= 4096,
               "lean_kernel's arguments exceed the 4 KB kernel argument segment");
-template <int MODE, bool COUNT, int OUT>
+// FIRST: the build that reads the list F (launched only with F.n > 0). The
+// list's prologue keeps values live that move the kernel's scalar register
+// allocation (sgpr_spill_count 62 -> 82), so a launch without a list runs
+// the build without it, whose stream is the one before the list existed.
+template <int MODE, bool COUNT, int OUT, bool FIRST>
 __global__ __launch_bounds__(kLeanBlock, FastWaves<MODE>::value > 0 ? FastWaves<MODE>::value : 1)
-void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T, DecisionTab D) {
+void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T, DecisionTab D, LeanFirst F) {
 #ifdef WFPT_PHASE_TIMING
   const long long rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  const int64_t i = (int64_t)blockIdx.x * kLeanBlock + threadIdx.x;
   const int lane = threadIdx.x & 63;
+  // Wave w of the grid takes chunk w, unless the host listed chunks to
+  // dispatch first (F.n > 0, the grid is F.n waves longer): then the first
+  // F.n waves take the listed chunks and wave w >= F.n takes chunk w - F.n,
+  // or nothing if that chunk is listed. Each chunk still has exactly one wave.
+  int64_t i = (int64_t)blockIdx.x * kLeanBlock + threadIdx.x;
+  if constexpr (FIRST) {
+    const int w = (int)(i >> 6);
+    if (w < F.n) {
+      i = (int64_t)F.c[w] * 64 + lane;
+    } else {
+      const int listed = F.c[lane];
+      if (__ballot(lane < F.n && listed == w - F.n) != 0ull) return;
+      i -= (int64_t)F.n * 64;
+    }
+  }
   const int64_t c = i >> 6;
   if (c * 64 >= A.n) return;  // a wave past the last chunk (wave-uniform)
+#ifdef WFPT_PHASE_TIMING
+  // the wave of the grid that takes the chunk, where that is not the chunk's
+  // own number (stored here: nothing kept live)
+  if (FIRST && lane == 0 && c < kPhaseWaves)
+    W.phase[c * 8 + 5] = ((unsigned long long)blockIdx.x * kLeanBlock + threadIdx.x) >> 6;
+#endif
   const bool own = i < A.n;
   const double x0 = own ? A.x[i] : 0.0;
   double p = 0.0, f0[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -122,6 +146,9 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T, DecisionTab D)
   // wave one of whose lanes met a value the fix-up code handles, runs the
   // generic site below.
   bool done = false;
+#ifdef WFPT_PHASE_TIMING
+  int site = 2;  // 0: uniform by the table, 1: uniform by the vote, 2: generic
+#endif
   if constexpr (MODE == kAdaptTZ) {
     if (bp == bo || bp == 0ull) {
       const Trial tr = trial_setup_b(x0, A.P, b != 0);
@@ -139,8 +166,8 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T, DecisionTab D)
       H.ia2 = 1.0 / (A.P.a * A.P.a);
       H.D0 = H.D4 = Decision{0, 0, 0};
       H.ok0 = H.ok4 = H.shared = false;
-      bool tab = __ballot(own && tr.valid && tr.x - ub > 0) == bo &&
-                 table_decisions(D, tr.x, lb, ub, H.ia2, bo, lane, kp0, sm0);
+      const bool pre = __ballot(own && tr.valid && tr.x - ub > 0) == bo;
+      bool tab = pre && table_decisions(D, tr.x, lb, ub, H.ia2, bo, lane, kp0, sm0);
       if (tab && sm0 != 31u) {
         const double q0 = exp_node((-kPi2 * ((tr.x - lb) * H.ia2)) * 0.5);
         const double Rr = exp_node((kPi2 * (ub - lb)) * (0.125 * H.ia2));
@@ -149,7 +176,9 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T, DecisionTab D)
         tab = __ballot(own && q0 > 1e-280 && Rr < 1e10) == bo;
       }
       bool uni = tab;
-      if (!tab) {  // the per-lane pre-pass and vote
+      // the per-lane pre-pass and vote, unless the table proves the wave split
+      // between two pieces (table_split: the vote cannot pass)
+      if (!tab && !(pre && table_split(D, tr.x, lb, ub, H.ia2, bo, lane))) {
         unsigned kp, sm;
         const bool okd = own && l0_decisions(tr, A.P, A.K, H, kp, sm);
         kp0 = __builtin_amdgcn_readfirstlane(kp);
@@ -172,6 +201,9 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T, DecisionTab D)
             oc = lean_uniform_level0(tr, A.P, A.K, zgrid_uniform(R, b), U, &R.S[b][0][0], H, kp0,
                                      sm0, p, ne0, pend0, bail);
           done = __ballot(own && bail) == 0ull;
+#ifdef WFPT_PHASE_TIMING
+          if (done) site = tab ? 0 : 1;
+#endif
           // counting build: the waves the table settled
           if (COUNT && done && tab && lane == 0) atomicAdd(&W.prof[0], 1);
         }
@@ -216,6 +248,7 @@ void lean_kernel(TrialArgs A, Work W, RootGrids R, UniformTabs T, DecisionTab D)
     unsigned xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     rec[3] = xcc;
+    rec[4] = (unsigned long long)site;  // the site the wave took
   }
 #endif
 }
@@ -233,7 +266,7 @@ void launch_direct(bool count, int out, const TrialArgs& A, const Work& W, hipSt
 }
 
 void launch_lean(int mode, bool count, int out, const TrialArgs& A, const Work& W, hipStream_t s,
-                 const DecisionTab* dt) {
+                 const DecisionTab* dt, const LeanFirst* first) {
   DecisionTab D;  // by value, as the other tables: each lane reads its own edge
   if (dt) D = *dt;
   else decision_tab_clear(D);
@@ -241,13 +274,42 @@ void launch_lean(int mode, bool count, int out, const TrialArgs& A, const Work& 
   root_grids(A.P, R);
   UniformTabs T;  // read by the 2-D family's uniform waves only
   uniform_tabs(R, T);
+  // the chunks dispatched first: distinct chunks of this call, or none
+  LeanFirst F;
+  F.n = 0;
+  for (int k = 0; k < kLeanFirstMax; ++k) F.c[k] = 0;
+  const int64_t nw = (A.n + 63) / 64;
+  if (first && mode == kAdaptTZ && first->n > 0 && first->n <= kLeanFirstMax) {
+    bool ok = true;
+    for (int k = 0; k < first->n; ++k)  // ascending: in range and without duplicates
+      ok = ok && first->c[k] >= 0 && first->c[k] < nw && (k == 0 || first->c[k] > first->c[k - 1]);
+    if (ok) F = *first;
+  }
+  const int64_t waves = nw + F.n, per = kLeanBlock / 64;
+  const dim3 grid((waves + per - 1) / per);
   with_value<kAdaptT, kAdaptTZ>(mode, [&](auto m) {
     with_build<false>(count, out, [&](auto c, auto o) {
-      hipLaunchKernelGGL((lean_kernel<decltype(m)::value, decltype(c)::value, decltype(o)::value>),
-                         dim3((A.n + kLeanBlock - 1) / kLeanBlock), dim3(kLeanBlock), 0, s, A, W, R,
-                         T, D);
+      if (F.n > 0)  // (the 2-D family only)
+        hipLaunchKernelGGL((lean_kernel<kAdaptTZ, decltype(c)::value, decltype(o)::value, true>),
+                           grid, dim3(kLeanBlock), 0, s, A, W, R, T, D, F);
+      else
+        hipLaunchKernelGGL(
+            (lean_kernel<decltype(m)::value, decltype(c)::value, decltype(o)::value, false>), grid,
+            dim3(kLeanBlock), 0, s, A, W, R, T, D, F);
     });
   });
+}
+
+// Resident waves of the 2-D family's lean kernel on the current device, from
+// the runtime's occupancy of the built kernel (0: unknown).
+int64_t lean_wave_slots() {
+  int dev = 0, cus = 0, blocks = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &blocks, lean_kernel<kAdaptTZ, false, OUT_SUM, true>, kLeanBlock, 0) != hipSuccess)
+    return 0;
+  return (int64_t)cus * blocks * (kLeanBlock / 64);
 }
 
 }  // namespace wfpt

@@ -492,7 +492,8 @@ static void launch_fixed(int mode, bool count, int out, const TrialArgs& A, hipS
 void launch_trials(int out_kind, int part, const double* x, int64_t n, const Params& P,
                    const Knobs& K, double* out, int* zeros, unsigned long long* evals, int* status,
                    int logp, const Work& W, hipStream_t s, hipEvent_t fast_done,
-                   const Split* split, double* trial, const DecisionTab* dtab) {
+                   const Split* split, double* trial, const DecisionTab* dtab,
+                   const LeanFirst* first) {
   if (n <= 0) return;
   Split S{};
   if (split) S = *split;
@@ -515,7 +516,7 @@ void launch_trials(int out_kind, int part, const double* x, int64_t n, const Par
   F.redo = (part & (kPassLean | kPassRedo)) ? W.redo : nullptr;
   if (part & kPassFast) {
     if (mode == kDirect) launch_direct(count, out_kind, A, F, s);
-    else if (part & kPassLean) launch_lean(mode, count, out_kind, A, F, s, dtab);
+    else if (part & kPassLean) launch_lean(mode, count, out_kind, A, F, s, dtab, first);
     else launch_engine(mode, count, out_kind, A, F, T, S, s);
     if (fast_done) (void)hipEventRecord(fast_done, s);
   }

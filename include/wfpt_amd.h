@@ -902,6 +902,11 @@ int wfpt_profile_lists(wfpt_ctx *ctx, int64_t counts[16], int reset);
  * records, 8 words per 64-trial chunk {start, end (100 MHz real-time clock),
  * 5 phase cycle counts, z rounds | t rounds << 32}; zeros otherwise. */
 int wfpt_debug_waves(wfpt_ctx *ctx, uint64_t *out, int64_t max_records);
+/* The chunks the last likelihood call's lean level-0 pass dispatched first
+ * (ascending chunk ids, at most 64; *n = 0: stored order): the chunks the
+ * host predicted to hold a breakpoint of the series decision. Up to
+ * max_chunks of them are written to chunks. */
+int wfpt_debug_lean_first(wfpt_ctx *ctx, int32_t *chunks, int32_t max_chunks, int32_t *n);
 /* The first n per-chunk partials {sum of the chunk's log terms, zero word}
  * the last summing call left on the device (64 stored trials per chunk for
  * the adaptive / direct families; synchronises the stream). Tests compare

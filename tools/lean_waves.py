@@ -4,8 +4,12 @@ WFPT_AMD_LIB=hddm_amd/lib/variants/libwfpt_phase.so).
 
 Prints the launch's span, the wave-duration distribution by position in the
 dataset (deciles of the chunk id: |rt| ascending within each boundary), the
-number of waves in flight over time (the dispatch rounds and the tail) and
-the per-XCD end times.
+number of waves in flight over time (the dispatch rounds and the tail), the
+per-XCD end times, and the end of the launch: the time of the last dispatch
+(the latest wave start), the 32 last-ending waves (chunk id, the wave of the
+grid that took it = its position in dispatch order, the site each took: 0 uniform by the table, 1 uniform by the
+vote, 2 generic) and the end of the last uniform wave. `--out FILE` also
+writes the record to FILE.
 
     WFPT_AMD_LIB=hddm_amd/lib/variants/libwfpt_phase.so python tools/lean_waves.py
 """
@@ -60,7 +64,40 @@ def main():
     out["mean_in_flight_over_span"] = float(live.mean())
     out["xcc_last_end_us"] = {int(k): round(float(en[xcc == k].max()), 1) for k in np.unique(xcc)}
     out["xcc_waves"] = {int(k): int((xcc == k).sum()) for k in np.unique(xcc)}
-    print(json.dumps(out), flush=True)
+    # the end of the launch: which waves set it
+    site = r[:, 4]
+    out["site_waves"] = {int(k): int((site == k).sum()) for k in np.unique(site)}
+    out["site_dur_median_us"] = {int(k): round(float(np.median(du[site == k])), 2)
+                                 for k in np.unique(site)}
+    out["last_dispatch_us"] = float(st.max())
+    uni = site != 2
+    out["last_uniform_end_us"] = float(en[uni].max()) if uni.any() else None
+    out["end_minus_last_uniform_end_us"] = (round(float(en.max() - en[uni].max()), 2)
+                                            if uni.any() else None)
+    gen = np.flatnonzero(site == 2)
+    out["generic_chunks"] = [int(c) for c in gen]
+    out["generic_start_us"] = [round(float(st[c]), 2) for c in gen]
+    out["generic_dur_us"] = [round(float(du[c]), 2) for c in gen]
+    wave = r[:, 5]  # the wave of the grid that took the chunk (listed chunks: the first waves)
+    if wave.max() == 0:  # a launch without a list: wave w takes chunk w
+        wave = np.arange(nw)
+    out["grid_waves"] = int(wave.max()) + 1
+    out["chunks_taken_out_of_order"] = int((wave != np.arange(nw)).sum())
+    out["first_waves_chunks"] = [int(c) for c in np.argsort(wave)[:int(wave.max()) + 1 - nw]]
+    last = np.argsort(en)[::-1][:32]
+    out["last_ending"] = [{"chunk": int(c), "wave": int(wave[c]),
+                           "pos": round(float(wave[c]) / (int(wave.max()) + 1), 4),
+                           "site": int(site[c]),
+                           "start_us": round(float(st[c]), 2), "dur_us": round(float(du[c]), 2),
+                           "end_us": round(float(en[c]), 2)} for c in last]
+    out["generic_among_last_16"] = int((site[last[:16]] == 2).sum())
+    text = json.dumps(out)
+    print(text, flush=True)
+    if "--out" in sys.argv:
+        path = sys.argv[sys.argv.index("--out") + 1]
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fh:
+            fh.write(text + "\n")
 
 
 if __name__ == "__main__":

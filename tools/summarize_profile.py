@@ -39,7 +39,7 @@ def per_launch(path, kernel):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("tag")
-    ap.add_argument("--kernel", default="void wfpt::lean_kernel<3, false, 0>")
+    ap.add_argument("--kernel", default="void wfpt::lean_kernel<3, false, 0, true>")
     ap.add_argument("--trials", type=int, default=1_000_000)
     ap.add_argument("--bytes-per-trial", type=float, default=8.0,
                     help="algorithmic HBM bytes per trial: 8 for the summing kernels (rt in, "
